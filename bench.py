@@ -5,11 +5,13 @@ One "step" = one full pass of the hot path over the BASELINE.json config-3 workl
 samples, tie-free T0 family, 2 groups, 3,000 initial reference genes, n_iter = 128): rank/band transform + pair kernel
 K1 + 128 iteration passes (tallies + statistics), with the expression matrix already resident in HBM when the timed
 region starts and the G x 15 result copied back to the host inside it.  The primary `value` uses n_conv = 0, which
-makes the convergence test of src/RankCompV3.jl:419 never true, i.e. exactly 128 passes (deterministic, worst case);
-the run with the reference's default n_conv = 5 is reported beside it as `converged`, and the tie-rich family (count
-data: two comparisons per pair and sample) as `tie_rich`.
+makes the convergence test of src/RankCompV3.jl:419 never true, i.e. exactly 128 passes (deterministic, worst case).
+A plain run sets up, warms up, times the K steps of that leg and prints the line: the headline, its per-stage timers
+and the K1 / K2 roofline objects, all read from those K steps.  Everything else is measured only with `--full`: the run
+with the reference's default n_conv = 5 is reported beside it as `converged`, and the tie-rich family (count data: two
+comparisons per pair and sample) as `tie_rich`.
 
-More blocks ride on the same line: `float64` (the same shape as Float64 input: the reference's other eltype, ranked
+More `--full` blocks ride on the same line: `float64` (the same shape as Float64 input: the reference's other eltype, ranked
 through the 0.1 tie band), `config4` (BASELINE config 4, 30 000 x 4 000 -- the shape BASELINE.json names for the
 1/2/4/8-GPU scaling -- forced and converging run, K1 roofline, per-rank stage times when N > 1), `cycle_watch` (the
 library's default: whole periods of a loop that repeats itself are skipped) and, since round 5, `from_host`: the DROP-IN
@@ -25,7 +27,11 @@ borrow chains + v_bcnt_u32_b32); the tallies are integer popcounts and the per-g
 `scaling` is "strong": with N GPUs the same 20k x 1k problem is split over the ranks (pair tiles; one RCCL all-gather
 of the ranks' own class-table words inside reo_build_pairs, in-library: reo_comm_init_rank).
 
-python bench.py [--gpus N --steps K --warmup W].  With N > 1 and no WORLD_SIZE in the environment the script launches
+`--dump-outputs DIR` writes what the last timed step returned to its caller -- the G x 15 result (`result.npy`), the
+trace of reference-set sizes (`trace.npy`) and the number of passes (`iterations.npy`), all float64 -- so that two
+builds can be compared output for output; the inputs are generated from fixed seeds and are the same in every run.
+
+python bench.py [--gpus N --steps K --warmup W --full --dump-outputs DIR].  With N > 1 and no WORLD_SIZE in the environment the script launches
 itself under torch.distributed.run (one rank per GPU, rendezvous on 127.0.0.1) BEFORE anything touches the GPU, passes
 rank 0's JSON line through and exits with the launcher's status; under an external torch.distributed.run it is a rank.
 """
@@ -95,6 +101,10 @@ def main() -> None:
     ap.add_argument("--samples", type=int, default=1000)
     ap.add_argument("--family", default="t0", choices=["t0", "t1"])
     ap.add_argument("--n-iter", type=int, default=128)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other block (converged, cycle_watch, tie_rich, float64, config4, from_host, cpu_baseline); "
+                         "the --no-* options below pick among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-tie-rich", action="store_true")
     ap.add_argument("--no-float64", action="store_true", help="skip the Float64-input block")
@@ -105,6 +115,8 @@ def main() -> None:
     ap.add_argument("--debug-gloo-one-gpu", action="store_true",
                     help="debug only: every rank uses cuda:0 and the table exchange goes through gloo via the host")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher.  Nothing here has imported torch or made a HIP call, and
@@ -298,9 +310,15 @@ def run(args, pkg, torch, dist, rank, world, local, dev, force_comm, _StdoutToSt
         ctx.close()
         return X, out, info
 
-    X, (forced, conv), info = run_family(args.family, args.steps, args.warmup, [0, 5])
-    dt, iters, trace, tm, res = forced
-    dtc, iters_c, trace_c, tmc, _ = conv
+    X, legs, info = run_family(args.family, args.steps, args.warmup, [0, 5] if args.full else [0])
+    dt, iters, trace, tm, res = legs[0]
+
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller (reo_identify_degs: result, passes run, trace), for output-for-output comparisons
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in (("result", res), ("trace", np.asarray(trace, dtype=np.float64).reshape(-1, 2)),
+                        ("iterations", np.array([iters], dtype=np.float64))):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
     P = G * (G - 1) // 2
     units = P * S                                          # comparisons per step (whole job, all ranks together)
@@ -352,13 +370,16 @@ def run(args, pkg, torch, dist, rank, world, local, dev, force_comm, _StdoutToSt
                                f"2 groups, ref_gene_max=3000, n_iter={args.n_iter}, n_conv=0 (exactly {iters} iterations)",
                    "genes": G, "samples": S, "iterations": iters, "sharding": f"pair tiles over {world} GPU(s)",
                    "cycle_watch": "off for this line (REO_CYCLE=0): all %d passes are executed; the library's default is in the block cycle_watch" % iters},
-        "converged": {"value": units * args.steps / dtc, "ms_per_step": dtc / args.steps * 1e3,
-                      "n_conv": 5, "iterations": iters_c, "final_trace": list(trace_c[-1]) if trace_c else None},
         "stages_ms_per_step": {k: tm[k] / args.steps for k in ("transform_ms", "k1_ms", "k2_full_ms", "iter_ms", "exchange_ms")},
         "roofline": k1, "roofline_k1": k1, "roofline_k2": k2,
         "final_trace": list(trace[-1]) if trace else None,
         "has_ties": info["has_ties"],
+        "full": args.full,
     }
+    if args.full:
+        dtc, iters_c, trace_c, _, _ = legs[1]
+        out["converged"] = {"value": units * args.steps / dtc, "ms_per_step": dtc / args.steps * 1e3,
+                            "n_conv": 5, "iterations": iters_c, "final_trace": list(trace_c[-1]) if trace_c else None}
     out["step_walls_ms"] = {"%s n_conv=%d cycle=%s G=%d" % k: [round(w, 3) for w in v] for k, v in step_walls.items()}
     out["stages_ms_per_step"]["iteration_passes_us_each"] = tm["iter_ms"] / args.steps / max(iters, 1) * 1e3
 
@@ -376,7 +397,7 @@ def run(args, pkg, torch, dist, rank, world, local, dev, force_comm, _StdoutToSt
                              "tiles (about %d MB over all ranks; the whole table is %d MB), mirror words are derived on arrival; "
                              "exchange_ms_per_build = pack + collective + unpack") % (G * info["Gp"] // 4 // 1000000, G * info["Gp"] // 2 // 1000000)
 
-    if not args.no_cycle_watch:
+    if args.full and not args.no_cycle_watch:
         # the library as it ships: the forced loop ends in a cycle of reference sets (period 4 here), the light passes find it and the
         # call skips whole periods -- the same iters_run, trace and result (compared below), fewer executed passes
         stc = max(3, args.steps // 2)
@@ -388,7 +409,7 @@ def run(args, pkg, torch, dist, rank, world, local, dev, force_comm, _StdoutToSt
                               "same_trace_as_all_passes_executed": bool(trw == trace and itw == iters),
                               "same_result_as_all_passes_executed": bool(np.array_equal(resw, res, equal_nan=True))}
 
-    if not args.no_tie_rich and args.family == "t0":
+    if args.full and not args.no_tie_rich and args.family == "t0":
         st = max(3, args.steps // 4)
         _, (f1,), info1 = run_family("t1", st, 1, [0])
         dt1, it1, tr1, tm1, _ = f1
@@ -408,7 +429,7 @@ def run(args, pkg, torch, dist, rank, world, local, dev, force_comm, _StdoutToSt
         dist.all_gather_object(allr, mine)
         return allr
 
-    if not args.no_float64 and args.family == "t0":
+    if args.full and not args.no_float64 and args.family == "t0":
         # the reference's other input type (Matrix(df_expr) of Float64, :652): the same shape with log-like expression values,
         # ranked through the 0.1 band of is_greater (:72) -- every pair needs both band edges (the tie-rich pair kernel)
         st = max(3, args.steps // 4)
@@ -421,7 +442,7 @@ def run(args, pkg, torch, dist, rank, world, local, dev, force_comm, _StdoutToSt
                           "frac": rf["frac"], "kernel": rf["kernel"], "steps": st, "transform_in_lds": infof["transform_in_lds"],
                           "final_trace": list(trf[-1]) if trf else None}
 
-    if not args.no_config4 and args.family == "t0" and (G, S) == (20000, 1000):
+    if args.full and not args.no_config4 and args.family == "t0" and (G, S) == (20000, 1000):
         # BASELINE config 4 (30 000 x 4 000, the shape BASELINE.json names for the 1/2/4/8-GPU scaling): the same step on
         # it -- forced 128 passes and the converging run -- for every N; its pair stage is 19-20 ms on one GPU, so the
         # replicated pass stage weighs a sixth of the step instead of half
@@ -455,7 +476,7 @@ def run(args, pkg, torch, dist, rank, world, local, dev, force_comm, _StdoutToSt
             if "cycle_watch" in out["config4"]:
                 out["config4"]["cycle_watch"]["replicated_stage_share"] = (tmw4["transform_ms"] + tmw4["iter_ms"]) / st4 / (dtw4 / st4 * 1e3)
 
-    if not args.no_from_host and world == 1 and args.family == "t0" and (G, S) == (20000, 1000):
+    if args.full and not args.no_from_host and world == 1 and args.family == "t0" and (G, S) == (20000, 1000):
         # The DROP-IN call: what julia/RankCompV3HIP.jl (and tests/abi/abi_client.c) does at :652 -- the matrix is a pageable
         # column-major HOST array handed to reo_set_matrix_i64 / _f64.  `value` above never includes this (inputs resident in HBM);
         # this block says what it costs and how much of it the library hides behind the transform and the pair kernel (groups and
@@ -534,7 +555,7 @@ def run(args, pkg, torch, dist, rank, world, local, dev, force_comm, _StdoutToSt
             out["from_host"]["config4_int64"] = from_host("t0", 30000, 4000, 0x5EED0004, 3, out["config4"]["ms_per_step"])
 
     out["step_walls_ms"] = {"%s n_conv=%d cycle=%s G=%d" % k: [round(w, 3) for w in v] for k, v in step_walls.items()}   # (every timed leg, per step)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         oracle = ge.load_oracle()
         ncores = oracle.num_threads()
         if ncores >= 32:

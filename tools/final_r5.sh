@@ -8,12 +8,12 @@ O=gpurun_out/r5z
 mkdir -p $O
 if [ "$1" != "profiles-only" ]; then
   python -m pytest tests -m gpu -x -q > $O/gpu_tests.log 2>&1
-  python bench.py > $O/bench.json 2> $O/bench.err
+  python bench.py --full > $O/bench.json 2> $O/bench.err
 fi
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_h -o s -- python3 bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-config4 --no-float64 --no-tie-rich --no-cycle-watch --no-from-host > $O/bench_headline_under_rocprof.json 2> $O/stats_h.log
 cp $(find $O/stats_h -name "s_kernel_stats.csv" | head -1) $O/kernel_stats_headline.csv
 rm -rf $O/stats_h
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o s -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/stats.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o s -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/stats.log
 cp $(find $O/stats -name "s_kernel_stats.csv" | head -1) $O/kernel_stats.csv
 rm -rf $O/stats
 for fam in t0 t1; do

@@ -17,15 +17,15 @@ if [ "$1" = "tests" ]; then
   python tools/fuzz_upload.py 150 60609 > $O/fuzz_upload_150.txt 2>&1
   python tools/fuzz_light.py 600 > $O/fuzz_light_600.txt 2>&1
   python tools/fuzz_shards.py 30 > $O/fuzz_shards_30.txt 2>&1
-  python bench.py --gpus 2 --debug-gloo-one-gpu --steps 4 --warmup 1 --no-cpu-baseline --no-tie-rich --no-float64 > $O/bench_2ranks_rehearsal_one_gpu_gloo.json 2> $O/bench_2ranks.err
+  python bench.py --full --gpus 2 --debug-gloo-one-gpu --steps 4 --warmup 1 --no-cpu-baseline --no-tie-rich --no-float64 > $O/bench_2ranks_rehearsal_one_gpu_gloo.json 2> $O/bench_2ranks.err
   REO_BENCH_FAIL_RANK=1 python bench.py --gpus 2 --debug-gloo-one-gpu --steps 2 --warmup 1 --no-cpu-baseline --no-tie-rich --no-float64 --no-config4 > $O/bench_2ranks_rank1_fails.json 2> $O/bench_2ranks_fail.err || echo "exit code $?" >> $O/bench_2ranks_rank1_fails.json
   exit 0
 fi
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_h -o s -- python3 bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-config4 --no-float64 --no-tie-rich --no-cycle-watch --no-from-host > $O/bench_headline_under_rocprof.json 2> $O/stats_h.log
 cp $(find $O/stats_h -name "s_kernel_stats.csv" | head -1) $O/kernel_stats_headline.csv
 rm -rf $O/stats_h
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o s -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/stats.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o s -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/stats.log
 cp $(find $O/stats -name "s_kernel_stats.csv" | head -1) $O/kernel_stats.csv
 rm -rf $O/stats
 for job in "t0:tools/k1_only.py t0" "t1:tools/k1_only.py t1" "c4:tools/k1_shape.py 30000 4000 t0"; do

@@ -4,6 +4,6 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/r5a
 mkdir -p $O
 python -m pytest tests -m gpu -x -q > $O/gpu_tests.log 2>&1
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 python tools/host_breakdown.py > $O/host_breakdown.txt 2>&1
 lscpu > $O/lscpu.txt
