@@ -45,6 +45,7 @@
 #include <type_traits>
 
 #include "reo_internal.h"
+#include "k1_items.h"
 
 namespace reo {
 
@@ -3634,107 +3635,27 @@ __global__ __launch_bounds__(256) void x_expand_mirror(XArgs a, const uint32_t *
 
 // ------------------------------------------------------------------ launchers
 
+static_assert(kItemTileI == kTileI && kItemUnitH == kUnitH, "k1_items.h carries its own copy of the tile geometry");
+
 // bits needed for every number the pair kernel compares: positions 0..G-1 and band ends up to G
 static int plane_bits(int64_t G) { return G <= 4095 ? 12 : (G <= 32767 ? 15 : (G <= 65535 ? 16 : (G <= 131071 ? 17 : 18))); }
 
-// the wave form with more than 16 planes (more than 65 535 genes; at most 65 535 samples): only the wave kernels have a loop for them
-template <int NB>
-static void launch_big_pairs(reo_ctx *c, const K1Args &a, bool shared, bool multi, size_t plane_elems, bool wide)
-{
-    const unsigned gridw = static_cast<unsigned>(c->k1_items_n);
-    if (wide) {  // (two groups: launch_k1 refuses the rest)
-        if (gridw == 0) return;
-        if (c->has_ties) k1w_pairs_wide<NB, true><<<gridw, 64, 0, c->stream>>>(a);
-        else k1w_pairs_wide<NB, false><<<gridw, 64, 0, c->stream>>>(a);
-        return;
-    }
-    if (shared) {
-        if (!c->gc_valid) {
-            if (gridw > 0) {
-                if (c->has_ties) k1w_group_counts<NB, true><<<gridw, 64, 0, c->stream>>>(a, c->gcounts.p, plane_elems);
-                else k1w_group_counts<NB, false><<<gridw, 64, 0, c->stream>>>(a, c->gcounts.p, plane_elems);
-            }
-            c->gc_valid = true;
-        }
-        const unsigned grid = static_cast<unsigned>((a.n_units + 7) / 8 * 8 * kUnitH * a.Q);
-        k1_classify<kRJ><<<grid, 256, 0, c->stream>>>(a, c->gcounts.p, plane_elems);
-        return;
-    }
-    if (gridw == 0) return;
-    if (multi) {
-        if (c->has_ties) k1w_pairs_multi<NB, true><<<gridw, 64, 0, c->stream>>>(a);
-        else k1w_pairs_multi<NB, false><<<gridw, 64, 0, c->stream>>>(a);
-    } else if (c->has_ties) k1w_pairs<NB, true><<<gridw, 64, 0, c->stream>>>(a);
-    else k1w_pairs<NB, false><<<gridw, 64, 0, c->stream>>>(a);
-}
+// What launch_k1 decides before it launches anything: which form of the pair kernel runs, the geometry of its work units
+// and which units this shard owns.
+struct K1Plan {
+    bool multi, wide, big, wave, shared, wcounts, wmulti;   // the form (k1_plan says what each means)
+    int RJ, CJ, Q, NP;      // genes j per lane, per j-chunk; j-chunks per panel; panels
+    unsigned grid;          // workgroups of the workgroup forms
+    size_t plane_elems;     // elements of one group's count plane (shared counts)
+    std::vector<uint32_t> units, units_all;   // panel << 16 | i-range: this shard's, and every unit of the build (owner = index % world)
+    int64_t tiles_owned, tiles_total;
+};
 
-template <int NB>
-static void launch_pair_kernels(reo_ctx *c, const K1Args &a, unsigned grid, bool shared, bool multi, size_t plane_elems, bool wide)
+// The plan of a launch.  Refuses what no kernel can do; decides -- by the free device
+// memory, when the planes are not there yet -- whether the groups' counts are shared, and allocates them.
+static int32_t k1_plan(reo_ctx *c, int sides, K1Plan &pl)
 {
-    if (wide) {  // more than 65 535 samples: 32-bit counts (never the shared per-group planes, which are 16-bit)
-        if (multi) {
-            if (c->has_ties) k1_pairs_wide<NB, true, true><<<grid, 256, 0, c->stream>>>(a);
-            else k1_pairs_wide<NB, false, true><<<grid, 256, 0, c->stream>>>(a);
-        } else if (c->k1_wave) {  // wave form: the count loop in runs of 2 047 blocks, 32-bit totals
-            const unsigned gridw = static_cast<unsigned>(c->k1_items_n);
-            if (gridw == 0) return;
-            if (c->has_ties) k1w_pairs_wide<NB, true><<<gridw, 64, 0, c->stream>>>(a);
-            else k1w_pairs_wide<NB, false><<<gridw, 64, 0, c->stream>>>(a);
-        } else {
-            if (c->has_ties) k1_pairs_wide<NB, true, false><<<grid, 256, 0, c->stream>>>(a);
-            else k1_pairs_wide<NB, false, false><<<grid, 256, 0, c->stream>>>(a);
-        }
-    } else if (shared) {
-        if (!c->gc_valid) {
-            if (c->k1_wave) {  // one wave per workgroup, the generated count loop, one item per (tile, chunk)
-                const unsigned gridw = static_cast<unsigned>(c->k1_items_n);
-                if (gridw > 0) {
-                    if (c->has_ties) k1w_group_counts<NB, true><<<gridw, 64, 0, c->stream>>>(a, c->gcounts.p, plane_elems);
-                    else k1w_group_counts<NB, false><<<gridw, 64, 0, c->stream>>>(a, c->gcounts.p, plane_elems);
-                }
-            } else if (c->has_ties) k1_group_counts<NB, true><<<grid, 256, 0, c->stream>>>(a, c->gcounts.p, plane_elems);
-            else k1_group_counts<NB, false><<<grid, 256, 0, c->stream>>>(a, c->gcounts.p, plane_elems);
-            c->gc_valid = true;
-        }
-        if (c->has_ties && !c->k1_wave) k1_classify<kRJTies><<<grid, 256, 0, c->stream>>>(a, c->gcounts.p, plane_elems);
-        else k1_classify<kRJ><<<grid, 256, 0, c->stream>>>(a, c->gcounts.p, plane_elems);
-    } else if (multi) {
-        if (c->has_ties) k1_pairs<NB, true, true><<<grid, 256, 0, c->stream>>>(a);
-        else k1_pairs<NB, false, true><<<grid, 256, 0, c->stream>>>(a);
-    } else if (c->k1_wave) {  // one wave per workgroup, generated count loop (two groups)
-        const unsigned gridw = static_cast<unsigned>(c->k1_items_n);
-        if (gridw == 0) return;
-        if (a.gate) k1w_pairs_gated<NB><<<gridw, 64, 0, c->stream>>>(a);   // the tie form is chosen on the device (K1Args::gate)
-        else if (c->has_ties) k1w_pairs<NB, true><<<gridw, 64, 0, c->stream>>>(a);
-        else k1w_pairs<NB, false><<<gridw, 64, 0, c->stream>>>(a);
-    } else {
-        if (c->has_ties) k1_pairs<NB, true, false><<<grid, 256, 0, c->stream>>>(a);
-        else k1_pairs<NB, false, false><<<grid, 256, 0, c->stream>>>(a);
-    }
-}
-
-static int32_t exchange_args(reo_ctx *c, XArgs &a, int m0, int mcnt);
-
-// sides (wave form, two groups): which sides' items are launched -- bit 0 the comparison's own group, bit 1 the rest; 3 = the whole
-// table.  keep_table: the class table has been cleared by the caller and holds other sides' planes already (the pipelined upload,
-// transform.hip eager_upload, launches a side as soon as its group's samples are ranked).
-int32_t launch_k1(reo_ctx *c, int k, int sides, bool keep_table, const int32_t *gate, const K1Range *range, bool prepare)
-{
-    K1Args a;
-    a.P = c->pos.p; a.AL = c->lo.p; a.AH = c->hi.p; a.table = c->table.p;
-    a.G = static_cast<int>(c->G); a.Gp = c->Gp; a.Wp = c->Wp;
     const bool multi = c->ngroups > 2;
-    const int other = multi ? k : 1 - k;  // two groups: the treat side is the other group
-    a.cb = c->goff32[k] / 32; a.ce = c->goff32[k + 1] / 32;
-    a.tb = c->goff32[other] / 32; a.te = c->goff32[other + 1] / 32;
-    a.gc = k; a.gt = other;
-    a.nc = c->goff[k + 1] - c->goff[k]; a.nt = static_cast<int>(c->S) - a.nc;  // gsi1, gsi2 (:358-359)
-    a.goff = c->goff_dev.p; a.ngroups = c->ngroups;
-    a.m1 = c->thr[2 * k]; a.m2 = c->thr[2 * k + 1];
-    a.seed = c->seed;
-
-    // work units: panel p = Q consecutive j-chunks, cut into i-ranges of kUnitH tiles.  Q keeps the
-    // panel's pos planes (Q x 256 RJ genes x nblk blocks x 64 B) within about 2 MiB of the 4 MiB L2 of an XCD.
     const bool wide = c->S > 65535;  // a count may not fit 16 bits: the unpacked form of the pair loop
     const bool big = c->G > 65535;    // more than 16 position planes: only the wave form has a loop for them
     if (big && wide && multi) {
@@ -3758,21 +3679,24 @@ int32_t launch_k1(reo_ctx *c, int k, int sides, bool keep_table, const int32_t *
     const bool wcounts = shared && (c->k1_wave || big);  // the per-group counts by the wave form's loop (k1w_group_counts): kRJ genes per lane too
     const bool wmulti = multi && !shared && !wide && big;  // a comparison recounted by the wave form (k1w_pairs_multi): above 65 535 genes only --
                                                            // below, the workgroup form recounts 10 % faster (ten groups: 3.7 - 4.3 against 4.1 - 4.8 ms)
+    // work units: panel p = Q consecutive j-chunks, cut into i-ranges of kUnitH tiles.  Q keeps the
+    // panel's pos planes (Q x 256 RJ genes x nblk blocks x 64 B) within about 2 MiB of the 4 MiB L2 of an XCD.
     const int RJ = (wave || wcounts || wmulti) ? kRJ : (wide ? (c->has_ties ? kRJWideTies : kRJWide) : (c->has_ties ? kRJTies : kRJ));  // genes j per lane
     const int CJ = kTileJ * RJ;
     const int NJ = (c->Gp + CJ - 1) / CJ, NIT = c->Gp / kTileI;
     const size_t chunk_bytes = static_cast<size_t>(CJ) * (c->goff32[c->ngroups] / 32) * 64;
     const int Q = chunk_bytes * 4 <= (2u << 20) ? 4 : (chunk_bytes * 2 <= (2u << 20) ? 2 : 1);
     const int NP = (NJ + Q - 1) / Q;
-    std::vector<uint32_t> units;
-    c->units_all_host.clear();
+    std::vector<uint32_t> &units = pl.units;
+    units.clear();
+    pl.units_all.clear();
     int64_t owned = 0, total = 0;
     uint32_t gu = 0;
     for (int p = 0; p < NP; ++p) {
         const int ni = std::min(NIT, (CJ / kTileI) * Q * (p + 1));  // i-tiles that reach this panel's columns
         for (int r = 0; r * kUnitH < ni; ++r, ++gu) {
             const bool mine = c->world == 1 || static_cast<int>(gu % c->world) == c->rank;
-            c->units_all_host.push_back(static_cast<uint32_t>(p) << 16 | static_cast<uint32_t>(r));
+            pl.units_all.push_back(static_cast<uint32_t>(p) << 16 | static_cast<uint32_t>(r));
             if (mine) units.push_back(static_cast<uint32_t>(p) << 16 | static_cast<uint32_t>(r));
             for (int t = r * kUnitH; t < std::min(ni, (r + 1) * kUnitH); ++t)
                 for (int jc = p * Q; jc < std::min(NJ, (p + 1) * Q); ++jc) {
@@ -3782,266 +3706,345 @@ int32_t launch_k1(reo_ctx *c, int k, int sides, bool keep_table, const int32_t *
                 }
         }
     }
-    c->tiles_owned = owned; c->tiles_total = total;
-    c->k1_cj = CJ; c->k1_q = Q;
-    a.n_units = static_cast<int>(units.size()); a.Q = Q;
+    pl.multi = multi; pl.wide = wide; pl.big = big; pl.wave = wave; pl.shared = shared; pl.wcounts = wcounts; pl.wmulti = wmulti;
+    pl.RJ = RJ; pl.CJ = CJ; pl.Q = Q; pl.NP = NP; pl.plane_elems = plane_elems;
+    pl.tiles_owned = owned; pl.tiles_total = total;
+    pl.grid = static_cast<unsigned>((units.size() + 7) / 8 * 8 * kUnitH * Q);   // (workgroup forms)
+    return REO_OK;
+}
+
+// The pair kernel(s) of the plan's form for NB planes, over a.items / c->k1_items_n (wave forms) or pl.grid (workgroup forms), on
+// c->stream.  More than 16 planes (more than 65 535 genes; at most 65 535 samples): only the wave kernels have a loop for them.
+template <int NB>
+static void launch_pairs(reo_ctx *c, const K1Args &a, const K1Plan &pl)
+{
+    constexpr bool kWg = NB <= 16;              // the workgroup forms (and the gated wave form) exist for this plane count
+    const bool wv = c->k1_wave || !kWg;
+    const unsigned grid = pl.grid, gridw = static_cast<unsigned>(c->k1_items_n);
+    const size_t plane_elems = pl.plane_elems;
+    // launch(std::true_type) or launch(std::false_type): the kernel's TIES parameter
+    auto by_ties = [&](auto launch) { if (c->has_ties) launch(std::true_type{}); else launch(std::false_type{}); };
+    if (pl.wide) {  // more than 65 535 samples: 32-bit counts (never the shared per-group planes, which are 16-bit)
+        if constexpr (kWg) {
+            if (pl.multi || !wv) {
+                by_ties([&](auto t) {
+                    constexpr bool T = decltype(t)::value;
+                    if (pl.multi) k1_pairs_wide<NB, T, true><<<grid, 256, 0, c->stream>>>(a);
+                    else k1_pairs_wide<NB, T, false><<<grid, 256, 0, c->stream>>>(a);
+                });
+                return;
+            }
+        }
+        if (gridw == 0) return;   // wave form: the count loop in runs of 2 047 blocks, 32-bit totals (two groups: launch_k1 refuses the rest above 16 planes)
+        by_ties([&](auto t) { k1w_pairs_wide<NB, decltype(t)::value><<<gridw, 64, 0, c->stream>>>(a); });
+    } else if (pl.shared) {
+        if (!c->gc_valid) {
+            if (wv) {  // one wave per workgroup, the generated count loop, one item per (tile, chunk)
+                if (gridw > 0) by_ties([&](auto t) { k1w_group_counts<NB, decltype(t)::value><<<gridw, 64, 0, c->stream>>>(a, c->gcounts.p, plane_elems); });
+            } else if constexpr (kWg)
+                by_ties([&](auto t) { k1_group_counts<NB, decltype(t)::value><<<grid, 256, 0, c->stream>>>(a, c->gcounts.p, plane_elems); });
+            c->gc_valid = true;
+        }
+        if (c->has_ties && !wv) k1_classify<kRJTies><<<grid, 256, 0, c->stream>>>(a, c->gcounts.p, plane_elems);
+        else k1_classify<kRJ><<<grid, 256, 0, c->stream>>>(a, c->gcounts.p, plane_elems);
+    } else if (pl.multi) {
+        if constexpr (kWg) by_ties([&](auto t) { k1_pairs<NB, decltype(t)::value, true><<<grid, 256, 0, c->stream>>>(a); });
+        else if (gridw > 0) by_ties([&](auto t) { k1w_pairs_multi<NB, decltype(t)::value><<<gridw, 64, 0, c->stream>>>(a); });
+    } else if (wv) {  // one wave per workgroup, generated count loop (two groups)
+        if (gridw == 0) return;
+        if constexpr (kWg)
+            if (a.gate) { k1w_pairs_gated<NB><<<gridw, 64, 0, c->stream>>>(a); return; }   // the tie form is chosen on the device (K1Args::gate)
+        by_ties([&](auto t) { k1w_pairs<NB, decltype(t)::value><<<gridw, 64, 0, c->stream>>>(a); });
+    } else if constexpr (kWg)
+        by_ties([&](auto t) { k1_pairs<NB, decltype(t)::value, false><<<grid, 256, 0, c->stream>>>(a); });
+}
+
+static void dispatch_pairs(reo_ctx *c, const K1Args &a, const K1Plan &pl)
+{
+    switch (plane_bits(c->G)) {
+    case 12: launch_pairs<12>(c, a, pl); break;
+    case 15: launch_pairs<15>(c, a, pl); break;
+    case 16: launch_pairs<16>(c, a, pl); break;
+    case 17: launch_pairs<17>(c, a, pl); break;
+    default: launch_pairs<18>(c, a, pl); break;
+    }
+}
+
+static int32_t upload_units_all(reo_ctx *c);
+
+// The item lists are a function of the geometry alone: this process-wide store keeps the last 16 as host vectors, so that a NEW
+// context on the same problem shape (the drop-in call makes one per identify_degs) does not build and sort its list again (0.9 ms
+// per side at config 3, on the critical path of the pipelined upload).  Never destroyed: a context may outlive the statics' destructors.
+struct StoredItems { uint64_t key[7]; std::vector<uint32_t> units, items; };
+static std::mutex g_item_store_mu;
+static std::vector<StoredItems> *const g_item_store = new std::vector<StoredItems>();
+
+// item list of the wave form for a set of units: the units in order, side-major, i-tile-major, wave chunks fastest; kept
+// until the geometry changes.  (Group counts: one item per tile and chunk, all groups' blocks.)  part: which wave of how
+// many the units are (pipelined exchange; 0 of 1: all owned units).  The order itself: k1_items.h.
+static int32_t item_list(reo_ctx *c, const K1Args &a, const K1Plan &pl, int sides, const std::vector<uint32_t> &units, reo_ctx::ItemList &cache, int part, int nparts)
+{
+    K1ItemGeom g;
+    g.G = static_cast<int>(c->G); g.RJ = pl.RJ; g.CJ = pl.CJ; g.Q = pl.Q;
+    g.nsides = pl.wave ? 2u : 1u; g.sides = sides;
+    g.wave = pl.wave; g.wide = pl.wide; g.big = pl.big;
+    g.halves = pl.wave && !pl.wide && c->k1_half;  // k1w_pairs only: its last round's items are dealt as two halves each
+    g.side_blocks = pl.wave ? std::max(a.ce - a.cb, a.te - a.tb) : c->goff32[c->ngroups] / 32;
+    g.order = c->k1_order; g.n_cus = c->n_cus;
+    const uint64_t key[5] = {static_cast<uint64_t>(c->G) << 32 | static_cast<uint32_t>(c->Gp), static_cast<uint64_t>(g.halves ? 1 : 0) << 48 | static_cast<uint64_t>(g.RJ) << 32 | static_cast<uint32_t>(g.Q),
+                             static_cast<uint64_t>(c->world) << 32 | static_cast<uint32_t>(c->rank),
+                             static_cast<uint64_t>(g.nsides) << 56 | static_cast<uint64_t>(units.size()) << 24 | static_cast<uint64_t>(g.side_blocks),
+                             static_cast<uint64_t>(sides) << 48 | static_cast<uint64_t>(part) << 32 | static_cast<uint32_t>(nparts)};
+    if (cache.buf.p && std::memcmp(key, cache.key, sizeof key) == 0) return REO_OK;
+    const uint64_t skey[7] = {key[0], key[1], key[2], key[3], key[4], static_cast<uint64_t>(c->n_cus),
+                              static_cast<uint64_t>(c->k1_order) << 2 | static_cast<uint64_t>(g.big ? 1 : 0) << 1 | static_cast<uint64_t>(g.wide ? 1 : 0)};
+    std::vector<uint32_t> items;
+    bool have = false;
+    {
+        std::lock_guard<std::mutex> lk(g_item_store_mu);
+        for (const StoredItems &st : *g_item_store)
+            if (std::memcmp(st.key, skey, sizeof skey) == 0 && st.units == units) { items = st.items; have = true; break; }
+    }
+    if (!have) {
+        items = k1_item_list(g, units);
+        std::lock_guard<std::mutex> lk(g_item_store_mu);
+        if (g_item_store->size() >= 16) g_item_store->erase(g_item_store->begin());
+        StoredItems st;
+        std::memcpy(st.key, skey, sizeof skey);
+        st.units = units; st.items = items;
+        g_item_store->push_back(std::move(st));
+    }
+    int32_t rc;
+    if ((rc = cache.buf.ensure(std::max<size_t>(items.size(), 1)))) return rc;
+    if (!items.empty()) {
+        REO_HIP_CHECK(hipMemcpyAsync(cache.buf.p, items.data(), items.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        REO_HIP_CHECK(hipStreamSynchronize(c->stream));  // `items` is a local
+    }
+    cache.n = items.size();
+    std::memcpy(cache.key, key, sizeof key);
+    return REO_OK;
+}
+
+// Several shards and a gather exchange: this shard's units are counted in WAVES on two alternating streams (the tail of
+// one wave's launch overlaps the head of the next), and as soon as wave w is done a third stream packs its forward
+// words, all-gathers the shards' packs of that wave and unpacks them, while wave w + 1 is being counted.  Every word of
+// the table belongs to one unit, the unpack kernels touch only words that carry another shard's bits, and the pair
+// kernel only writes words of its own units: the three streams never meet in a word.  (Wave form for two groups only;
+// everything else exchanges behind the pair kernel, as in round 3.)
+// maxu_x: slots (units per shard) of the build; dispatch_wave(w, stream): the pair kernel over the item list of wave w on that stream.
+template <class F>
+static int32_t pipelined_exchange(reo_ctx *c, const K1Args &a, const K1Plan &pl, int nwaves, int maxu_x, F dispatch_wave)
+{
+    int32_t rc;
+    const std::vector<uint32_t> &units = pl.units;
+    const int mw = (maxu_x + nwaves - 1) / nwaves;   // slots per wave: the same on every shard
+    const size_t uw = static_cast<size_t>(exchange_unit_words(c));   // (of c->k1_cj, c->k1_q: this build's)
+    if ((rc = c->xsend.ensure(uw * mw * nwaves)) || (rc = c->xrecv.ensure(uw * mw * nwaves * c->world))) return rc;
+    if (!c->xs) {
+        for (int q = 0; q < 2; ++q) REO_HIP_CHECK(handle_stream(&c->k1s[q], 0));
+        REO_HIP_CHECK(handle_stream(&c->xs, 0));
+        REO_HIP_CHECK(handle_event(&c->ev_fork, 0));
+        REO_HIP_CHECK(handle_event(&c->ev_x, 0));
+        for (int q = 0; q < 2; ++q) REO_HIP_CHECK(handle_event(&c->ev_k1_join[q], 0));
+        for (int q = 0; q < 8; ++q) REO_HIP_CHECK(handle_event(&c->ev_k1[q], 0));
+    }
+    // the waves' item lists (uploads synchronise c->stream: before anything is forked)
+    std::vector<std::vector<uint32_t>> wunits(nwaves);
+    for (size_t m = 0; m < units.size(); ++m) wunits[std::min<size_t>(m / mw, nwaves - 1)].push_back(units[m]);
+    for (int w = 0; w < nwaves; ++w)
+        if ((rc = item_list(c, a, pl, 3, wunits[w], c->k1_wave_items[w], w, nwaves))) return rc;
+    // the exchange kernels read the unit list and the geometry of THIS build
+    if ((rc = upload_units_all(c))) return rc;
+    if (!c->table_prezeroed) REO_HIP_CHECK(hipMemsetAsync(c->table.p, 0, static_cast<size_t>(c->G) * kPlanes * c->Wp * sizeof(uint32_t), c->stream));
+    c->table_prezeroed = false;
+    c->last_k1_shared = 0;
+    tic(c, 1);
+    // From the fork to the join nothing returns: whatever fails in between, the two pair-kernel streams and the exchange stream
+    // are joined into c->stream afterwards, so that everything queued on them is ordered before whatever the caller does next
+    // on the context's stream -- its waits, and reo_destroy's frees (an early return here used to leave pair and exchange
+    // kernels, or an RCCL all-gather, queued on streams that nothing waited for).  The first failure is kept in xrc.
+    int32_t xrc = REO_OK;
+    auto hip_ok = [&](hipError_t e, const char *what) {
+        if (e == hipSuccess || xrc) return e == hipSuccess;
+        set_error("%s failed: %s (pipelined exchange)", what, hipGetErrorString(e));
+        xrc = e == hipErrorOutOfMemory ? REO_ENOMEM : REO_EHIP;
+        return false;
+    };
+    bool forked = hip_ok(hipEventRecord(c->ev_fork, c->stream), "hipEventRecord(fork)");
+    for (int q = 0; q < 2 && forked; ++q) forked = hip_ok(hipStreamWaitEvent(c->k1s[q], c->ev_fork, 0), "hipStreamWaitEvent(fork)");
+    if (forked) forked = hip_ok(hipStreamWaitEvent(c->xs, c->ev_fork, 0), "hipStreamWaitEvent(fork)");
+    for (int w = 0; w < nwaves && !xrc; ++w) {
+        hipStream_t ks = c->k1s[w & 1];
+        dispatch_wave(w, ks);
+        if (!hip_ok(hipGetLastError(), "pair kernel launch")) break;
+        if (!hip_ok(hipEventRecord(c->ev_k1[w], ks), "hipEventRecord(wave)") || !hip_ok(hipStreamWaitEvent(c->xs, c->ev_k1[w], 0), "hipStreamWaitEvent(wave)")) break;
+        const int m0 = w * mw, mc = std::max(0, std::min(mw, maxu_x - m0));
+        if (mc == 0) continue;
+        uint32_t *send = c->xsend.p + uw * mw * w, *recv = c->xrecv.p + uw * mw * w * c->world;
+        const int64_t bytes = static_cast<int64_t>(uw) * mc * sizeof(uint32_t);
+        if ((xrc = launch_pack_units(c, m0, mc, send, c->xs))) break;
+        if (c->comm) { if ((xrc = comm_allgather(c, send, recv, bytes, c->xs)) < 0) break; xrc = REO_OK; }
+        else {
+            const int hrc = c->ag(send, recv, bytes, c->xs, c->ag_user);  // stream-ordered on the exchange stream
+            if (hrc) { set_error("all-gather hook failed with %d", hrc); xrc = REO_ECOMM; break; }
+        }
+        if ((xrc = launch_expand_units(c, m0, mc, recv, c->xs))) break;
+    }
+    // join: the pair kernels first (their makespan is the K1 stage time), then the exchange stream (what is left of it: the
+    // exposed part of the exchange).  A join that cannot even be queued falls back to host waits for the side streams.
+    bool joined = true;
+    for (int q = 0; q < 2; ++q)
+        if (hipEventRecord(c->ev_k1_join[q], c->k1s[q]) != hipSuccess || hipStreamWaitEvent(c->stream, c->ev_k1_join[q], 0) != hipSuccess) joined = false;
+    toc(c);
+    tic(c, 6);
+    if (hipEventRecord(c->ev_x, c->xs) != hipSuccess || hipStreamWaitEvent(c->stream, c->ev_x, 0) != hipSuccess) joined = false;
+    toc(c);
+    if (!joined) {
+        for (int q = 0; q < 2; ++q) (void)hipStreamSynchronize(c->k1s[q]);
+        (void)hipStreamSynchronize(c->xs);
+        if (!xrc) { set_error("joining the streams of the pipelined exchange failed"); xrc = REO_EHIP; }
+    }
+    if (xrc) return xrc;
+    c->x_pipelined = true;
+    return REO_OK;
+}
+
+// diagnostic (REO_K1_STAMPS): where an item's time goes (100 MHz marks); stamps = four marks per item of the launch just made on
+// c->stream, then the marks of the two k_time_mark launches around it.  Frees them.
+static int32_t report_k1_stamps(reo_ctx *c, unsigned long long *stamps)
+{
+    std::vector<unsigned long long> h(c->k1_items_n * 4 + 2);
+    REO_HIP_CHECK(hipMemcpyAsync(h.data(), stamps, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    REO_HIP_CHECK(hipStreamSynchronize(c->stream));
+    double pro = 0, loop = 0, emit = 0;
+    unsigned long long t0 = ~0ull, t1 = 0;
+    for (size_t i = 0; i < c->k1_items_n; ++i) {
+        pro += static_cast<double>(h[4 * i + 1] - h[4 * i]); loop += static_cast<double>(h[4 * i + 2] - h[4 * i + 1]);
+        emit += static_cast<double>(h[4 * i + 3] - h[4 * i + 2]);
+        t0 = std::min(t0, h[4 * i]); t1 = std::max(t1, h[4 * i + 3]);
+    }
+    const double n = static_cast<double>(c->k1_items_n) * 100.0;  // marks per microsecond
+    fprintf(stderr, "[reo] K1 wave items %zu: prologue %.2f us, count loop %.2f us, classification %.2f us per item; first start to last end %.3f ms\n",
+            c->k1_items_n, pro / n, loop / n, emit / n, static_cast<double>(t1 - t0) / 1e5);
+    fprintf(stderr, "[reo]   a launch before it ended %.1f us before the first item began; one after it began %.1f us after the last item ended\n",
+            static_cast<double>(static_cast<long long>(t0 - h[c->k1_items_n * 4])) / 100.0, static_cast<double>(static_cast<long long>(h[c->k1_items_n * 4 + 1] - t1)) / 100.0);
+    // the launch in 24 slices of time: items in flight (average) and the count loop's duration of the items that started in the slice
+    constexpr int kSl = 24;
+    const double span = static_cast<double>(t1 - t0) + 1.0;
+    double busy[kSl] = {}, dur[kSl] = {};
+    size_t started[kSl] = {};
+    for (size_t i = 0; i < c->k1_items_n; ++i) {
+        const double b = static_cast<double>(h[4 * i] - t0), e = static_cast<double>(h[4 * i + 3] - t0);
+        const int s0 = static_cast<int>(b / span * kSl);
+        started[s0]++; dur[s0] += static_cast<double>(h[4 * i + 2] - h[4 * i + 1]);
+        for (int s = s0; s < kSl; ++s) {
+            const double lo = span * s / kSl, hi = span * (s + 1) / kSl;
+            if (e <= lo) break;
+            busy[s] += (std::min(e, hi) - std::max(b, lo)) / (hi - lo);
+        }
+    }
+    fprintf(stderr, "[reo]   items in flight by slice:");
+    for (int s = 0; s < kSl; ++s) fprintf(stderr, " %.0f", busy[s]);
+    fprintf(stderr, "\n[reo]   loop us of items started in slice:");
+    for (int s = 0; s < kSl; ++s) fprintf(stderr, " %.0f", started[s] ? dur[s] / static_cast<double>(started[s]) / 100.0 : 0.0);
+    fprintf(stderr, "\n");
+    (void)hipFree(stamps);
+    return REO_OK;
+}
+
+// The arguments of comparison k that do not depend on the plan: the operands, the two sides' blocks, sizes and thresholds.
+static K1Args k1_args(const reo_ctx *c, int k)
+{
+    K1Args a;
+    a.P = c->pos.p; a.AL = c->lo.p; a.AH = c->hi.p; a.table = c->table.p;
+    a.G = static_cast<int>(c->G); a.Gp = c->Gp; a.Wp = c->Wp;
+    const bool multi = c->ngroups > 2;
+    const int other = multi ? k : 1 - k;  // two groups: the treat side is the other group
+    a.cb = c->goff32[k] / 32; a.ce = c->goff32[k + 1] / 32;
+    a.tb = c->goff32[other] / 32; a.te = c->goff32[other + 1] / 32;
+    a.gc = k; a.gt = other;
+    a.nc = c->goff[k + 1] - c->goff[k]; a.nt = static_cast<int>(c->S) - a.nc;  // gsi1, gsi2 (:358-359)
+    a.goff = c->goff_dev.p; a.ngroups = c->ngroups;
+    a.m1 = c->thr[2 * k]; a.m2 = c->thr[2 * k + 1];
+    a.seed = c->seed;
+    a.items = nullptr; a.stamps = nullptr; a.gate = nullptr;
+    a.park = nullptr; a.park_ge = nullptr; a.park_mode = 0;
+    return a;
+}
+
+// This shard's units on the device (uploaded when the list, or the buffer, is a different one from last time's).
+static int32_t upload_unit_map(reo_ctx *c, const std::vector<uint32_t> &units)
+{
+    int32_t rc;
     if ((rc = c->unit_map.ensure(std::max<size_t>(units.size(), 1)))) return rc;
     if (!units.empty() && (c->unit_map.p != c->unit_map_uploaded || units != c->unit_map_host)) {  // (the same geometry as last time: already there)
         REO_HIP_CHECK(hipMemcpyAsync(c->unit_map.p, units.data(), units.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        REO_HIP_CHECK(hipStreamSynchronize(c->stream));  // `units` is a local: the copy must have read it before any return below
+        REO_HIP_CHECK(hipStreamSynchronize(c->stream));  // the copy must have read `units` before any return of the caller
         c->unit_map_host = units;
         c->unit_map_uploaded = c->unit_map.p;
     }
-    a.unit_map = c->unit_map.p;
-    a.items = nullptr; a.stamps = nullptr; a.gate = gate;
-    a.park = nullptr; a.park_ge = nullptr; a.park_mode = 0;
-    if ((range || prepare) && (sides != 1 && sides != 2)) { set_error("a range of sample blocks / a prepared launch: one side of the pair kernel"); return REO_EINVAL; }
-    if (gate && (!wave || wide || big)) { set_error("a gated launch of the pair kernel: wave form, at most 65535 genes and samples"); return REO_EINVAL; }
-    const unsigned grid = static_cast<unsigned>((units.size() + 7) / 8 * 8 * kUnitH * Q);   // (workgroup forms)
-    // item list of the wave form for a set of units: the units in order, side-major, i-tile-major, wave chunks fastest; kept
-    // until the geometry changes.  (Group counts: one item per tile and chunk, all groups' blocks.)  part: which wave of how
-    // many the units are (pipelined exchange; 0 of 1: all owned units)
-    auto item_list = [&](const std::vector<uint32_t> &units, reo_ctx::ItemList &cache, int part, int nparts) -> int32_t {
-        const int CW = 64 * RJ, QW = Q * (CJ / CW);
-        const uint32_t nsides = wave ? 2u : 1u;
-        const bool halves = wave && !wide && c->k1_half;  // k1w_pairs only: its last round's items are dealt as two halves each
-        const uint64_t key[5] = {static_cast<uint64_t>(c->G) << 32 | static_cast<uint32_t>(c->Gp), static_cast<uint64_t>(halves ? 1 : 0) << 48 | static_cast<uint64_t>(RJ) << 32 | static_cast<uint32_t>(Q),
-                                 static_cast<uint64_t>(c->world) << 32 | static_cast<uint32_t>(c->rank),
-                                 static_cast<uint64_t>(nsides) << 56 | static_cast<uint64_t>(units.size()) << 24 |
-                                     static_cast<uint64_t>(wave ? std::max(a.ce - a.cb, a.te - a.tb) : c->goff32[c->ngroups] / 32),
-                                 static_cast<uint64_t>(sides) << 48 | static_cast<uint64_t>(part) << 32 | static_cast<uint32_t>(nparts)};
-        if (!cache.buf.p || std::memcmp(key, cache.key, sizeof key) != 0) {
-            // The list is a function of the geometry alone: a process-wide store keeps the last few as host vectors, so that a NEW context
-            // on the same problem shape (the drop-in call makes one per identify_degs) does not build and sort it again (0.9 ms per
-            // side at config 3, on the critical path of the pipelined upload).
-            struct Stored { uint64_t key[7]; std::vector<uint32_t> units, items; };
-            static std::mutex store_mu;
-            static std::vector<Stored> *store = new std::vector<Stored>();
-            const uint64_t skey[7] = {key[0], key[1], key[2], key[3], key[4], static_cast<uint64_t>(c->n_cus),
-                                      static_cast<uint64_t>(c->k1_order) << 2 | static_cast<uint64_t>(big ? 1 : 0) << 1 | static_cast<uint64_t>(wide ? 1 : 0)};
-            std::vector<uint32_t> items;
-            bool have = false;
-            {
-                std::lock_guard<std::mutex> lk(store_mu);
-                for (const Stored &st : *store)
-                    if (std::memcmp(st.key, skey, sizeof skey) == 0 && st.units == units) { items = st.items; have = true; break; }
-            }
-            if (!have) {
-            // Workgroup b runs on XCD b & 7.  An item goes to the list of XCD (wave chunk & 7), and an XCD walks its list
-            // group by group of its chunks (as many pos chunks of one side as fit about 2.5 MB of its 4 MiB L2), inside a
-            // group side-major, then i-tile-major, chunks fastest: the group's pos planes stay in that L2 while each tile
-            // operand (32 rows x the side's blocks) streams through it once per group.  (Dealing the items of the
-            // unit-by-unit order one at a time made every XCD touch every chunk and re-read every tile operand per unit:
-            // 2.0 GB of L2 fills per launch at config 3, against 0.24 GB algorithmic.)  The lists are then levelled by
-            // moving the surplus of the long ones -- their last items -- to the short ones, and interleaved.
-            std::vector<uint32_t> lists[8];
-            const int G = static_cast<int>(c->G);
-            size_t total_items = 0;
-            const int side_blocks = wave ? std::max(a.ce - a.cb, a.te - a.tb) : c->goff32[c->ngroups] / 32;
-            const size_t chunk_side_bytes = static_cast<size_t>(CW) * std::max(side_blocks, 1) * 64;
-            const int per_group = static_cast<int>(std::max<size_t>(1, (size_t(5) << 19) / chunk_side_bytes));  // chunks of one XCD per group
-            uint32_t tile_block = 32;   // (order 2) i-tiles per block: their tile operands together about 1 MB, a power of two from 4 to 32
-            while (tile_block > 4 && static_cast<size_t>(tile_block) * kTileI * std::max(side_blocks, 1) * (big ? 128 : 64) > (size_t(1) << 20)) tile_block >>= 1;
-            for (uint32_t um : units)
-                for (uint32_t side = 0; side < nsides; ++side) {
-                    if (wave && !((sides >> side) & 1)) continue;
-                    for (int t = 0; t < kUnitH; ++t)
-                        for (int w = 0; w < QW; ++w) {
-                            const int it = static_cast<int>(um & 0xFFFFu) * kUnitH + t, cw = static_cast<int>(um >> 16) * QW + w;
-                            const int i0 = it * kTileI, jw = cw * CW;
-                            if (i0 >= G || jw >= G || ((jw + CW - 1) >> 6) < (i0 >> 6)) continue;  // no pair i < j < G in it
-                            lists[cw & 7].push_back(side << 31 | static_cast<uint32_t>(cw) << 16 | static_cast<uint32_t>(it));
-                            ++total_items;
-                        }
-                }
-            // order inside an XCD's list: chunk group, side, i-tile, chunk -- sorted as one 64-bit key per item (the comparator form,
-            // with its two divisions per comparison, took 0.9 ms per side at config 3)
-            std::vector<uint64_t> keys;
-            for (auto &l : lists) {
-                keys.resize(l.size());
-                for (size_t q = 0; q < l.size(); ++q) {
-                    const uint32_t x = l[q], cx = (x >> 16) & 0x7FFFu;
-                    if (c->k1_order == 0)
-                        keys[q] = static_cast<uint64_t>((cx >> 3) / static_cast<uint32_t>(per_group)) << 32 | static_cast<uint64_t>(x >> 31) << 31 |
-                                  static_cast<uint64_t>(x & 0xFFFFu) << 15 | cx;
-                    else if (c->k1_order == 1)   // i-tiles fastest inside a chunk: the mirror words of a chunk's genes (one 32-bit word per i-tile,
-                                                 // neighbours in their table rows) reach L2 one after the other -- but every chunk re-reads every tile operand
-                        keys[q] = static_cast<uint64_t>((cx >> 3) / static_cast<uint32_t>(per_group)) << 48 | static_cast<uint64_t>(x >> 31) << 47 |
-                                  static_cast<uint64_t>(cx) << 16 | (x & 0xFFFFu);
-                    else   // 2: blocks of TB consecutive i-tiles; inside a block chunk by chunk, the block's tiles fastest: TB mirror words in a row
-                           // (TB x 4 bytes of a table line) while the block's tile operands (TB x 32 rows x the side's blocks x 64 B: about 1 MB) stay in L2
-                        keys[q] = static_cast<uint64_t>((cx >> 3) / static_cast<uint32_t>(per_group)) << 48 | static_cast<uint64_t>(x >> 31) << 47 |
-                                  static_cast<uint64_t>((x & 0xFFFFu) / tile_block) << 31 | static_cast<uint64_t>(cx) << 16 | (x & 0xFFFFu);
-                }
-                std::sort(keys.begin(), keys.end());
-                for (size_t q = 0; q < l.size(); ++q) {
-                    const uint64_t k = keys[q];
-                    if (c->k1_order == 0) l[q] = static_cast<uint32_t>((k >> 31) & 1u) << 31 | static_cast<uint32_t>(k & 0x7FFFu) << 16 | static_cast<uint32_t>((k >> 15) & 0xFFFFu);
-                    else l[q] = static_cast<uint32_t>((k >> 47) & 1u) << 31 | static_cast<uint32_t>((k >> 16) & 0x7FFFu) << 16 | static_cast<uint32_t>(k & 0xFFFFu);
-                }
-            }
-            const size_t per = (total_items + 7) / 8;
-            std::vector<uint32_t> surplus;
-            for (auto &l : lists)
-                while (l.size() > per) { surplus.push_back(l.back()); l.pop_back(); }
-            for (auto &l : lists)
-                while (l.size() < per && !surplus.empty()) { l.push_back(surplus.back()); surplus.pop_back(); }
-            items.reserve(total_items);
-            for (size_t k = 0; k < per; ++k)
-                for (auto &l : lists)
-                    if (k < l.size()) items.push_back(l[k]);
-            // All items take the same time, so the resident waves (slots) work through the list in rounds; when the last
-            // round fills at most half of the slots, its items are dealt as two half-height items each (rows 0-15 and 16-31
-            // of the tile: bit 15 set, bit 14 = which half) and the launch ends half an item's time earlier -- 0.45 of a round
-            // out of 16.45 at config 3; a shard of one eighth of the tiles has 2.06 rounds.  Both halves of an item stay
-            // on the item's XCD (the tail is a multiple of 8 items).
-            if (halves && !items.empty()) {
-                const size_t slots = static_cast<size_t>(c->n_cus) * 4 * (big ? 2 : 3);
-                const size_t left = items.size() % slots;
-                if (left > 0 && left <= slots / 2) {
-                    const size_t n = std::min(items.size(), (left + 7) / 8 * 8);
-                    const std::vector<uint32_t> tail(items.end() - static_cast<ptrdiff_t>(n), items.end());
-                    items.resize(items.size() - n);
-                    for (uint32_t half = 0; half < 2; ++half)
-                        for (uint32_t x : tail) items.push_back(x | 0x8000u | (half ? 0x4000u : 0u));
-                }
-            }
-                std::lock_guard<std::mutex> lk(store_mu);
-                if (store->size() >= 16) store->erase(store->begin());
-                Stored st;
-                std::memcpy(st.key, skey, sizeof skey);
-                st.units = units; st.items = items;
-                store->push_back(std::move(st));
-            }   // (!have)
-            int32_t rc2;
-            if ((rc2 = cache.buf.ensure(std::max<size_t>(items.size(), 1)))) return rc2;
-            if (!items.empty()) {
-                REO_HIP_CHECK(hipMemcpyAsync(cache.buf.p, items.data(), items.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-                REO_HIP_CHECK(hipStreamSynchronize(c->stream));  // `items` is a local
-            }
-            cache.n = items.size();
-            std::memcpy(cache.key, key, sizeof key);
-        }
-        return REO_OK;
-    };
-    auto dispatch = [&]() {   // the pair kernel(s) for a.items / c->k1_items_n on c->stream
-        switch (plane_bits(c->G)) {
-        case 12: launch_pair_kernels<12>(c, a, grid, shared, multi, plane_elems, wide); break;
-        case 15: launch_pair_kernels<15>(c, a, grid, shared, multi, plane_elems, wide); break;
-        case 16: launch_pair_kernels<16>(c, a, grid, shared, multi, plane_elems, wide); break;
-        case 17: launch_big_pairs<17>(c, a, shared, multi, plane_elems, wide); break;
-        default: launch_big_pairs<18>(c, a, shared, multi, plane_elems, wide); break;
-        }
-    };
-    c->x_pipelined = false;
-    // Several shards and a gather exchange: this shard's units are counted in WAVES on two alternating streams (the tail of
-    // one wave's launch overlaps the head of the next), and as soon as wave w is done a third stream packs its forward
-    // words, all-gathers the shards' packs of that wave and unpacks them, while wave w + 1 is being counted.  Every word of
-    // the table belongs to one unit, the unpack kernels touch only words that carry another shard's bits, and the pair
-    // kernel only writes words of its own units: the three streams never meet in a word.  (Wave form for two groups only;
-    // everything else exchanges behind the pair kernel, as in round 3.)
-    const int maxu_x = std::max(1, (static_cast<int>(c->units_all_host.size()) + std::max(c->world, 1) - 1) / std::max(c->world, 1));
-    const int nwaves = (wave && sides == 3 && c->world > 1 && (c->comm || c->ag) && !c->in_multi && !c->k1_stamps) ? std::min({c->x_waves, 8, maxu_x}) : 1;   // (a reo_create_multi context hands its packs to the leader itself: comm.hip)
-    if (nwaves > 1) {
-        const int mw = (maxu_x + nwaves - 1) / nwaves;   // slots per wave: the same on every shard
-        const size_t uw = static_cast<size_t>(kUnitRows) * kPlanes * (static_cast<size_t>(Q) * CJ / 32);
-        if ((rc = c->xsend.ensure(uw * mw * nwaves)) || (rc = c->xrecv.ensure(uw * mw * nwaves * c->world))) return rc;
-        if (!c->xs) {
-            for (int q = 0; q < 2; ++q) REO_HIP_CHECK(handle_stream(&c->k1s[q], 0));
-            REO_HIP_CHECK(handle_stream(&c->xs, 0));
-            REO_HIP_CHECK(handle_event(&c->ev_fork, 0));
-            REO_HIP_CHECK(handle_event(&c->ev_x, 0));
-            for (int q = 0; q < 2; ++q) REO_HIP_CHECK(handle_event(&c->ev_k1_join[q], 0));
-            for (int q = 0; q < 8; ++q) REO_HIP_CHECK(handle_event(&c->ev_k1[q], 0));
-        }
-        // the waves' item lists (uploads synchronise c->stream: before anything is forked)
-        std::vector<std::vector<uint32_t>> wunits(nwaves);
-        for (size_t m = 0; m < units.size(); ++m) wunits[std::min<size_t>(m / mw, nwaves - 1)].push_back(units[m]);
-        for (int w = 0; w < nwaves; ++w)
-            if ((rc = item_list(wunits[w], c->k1_wave_items[w], w, nwaves))) return rc;
-        // the exchange kernels read the unit list and the geometry of THIS build
-        c->k1_cj = CJ; c->k1_q = Q;
-        XArgs xa;
-        if ((rc = exchange_args(c, xa, 0, mw))) return rc;
-        if (!c->table_prezeroed) REO_HIP_CHECK(hipMemsetAsync(c->table.p, 0, static_cast<size_t>(c->G) * kPlanes * c->Wp * sizeof(uint32_t), c->stream));
-        c->table_prezeroed = false;
-        c->last_k1_shared = 0;
-        tic(c, 1);
-        // From the fork to the join nothing returns: whatever fails in between, the two pair-kernel streams and the exchange stream
-        // are joined into c->stream afterwards, so that everything queued on them is ordered before whatever the caller does next
-        // on the context's stream -- its waits, and reo_destroy's frees (an early return here used to leave pair and exchange
-        // kernels, or an RCCL all-gather, queued on streams that nothing waited for).  The first failure is kept in xrc.
-        int32_t xrc = REO_OK;
-        auto hip_ok = [&](hipError_t e, const char *what) {
-            if (e == hipSuccess || xrc) return e == hipSuccess;
-            set_error("%s failed: %s (pipelined exchange)", what, hipGetErrorString(e));
-            xrc = e == hipErrorOutOfMemory ? REO_ENOMEM : REO_EHIP;
-            return false;
-        };
-        hipStream_t main_stream = c->stream;
-        bool forked = hip_ok(hipEventRecord(c->ev_fork, c->stream), "hipEventRecord(fork)");
-        for (int q = 0; q < 2 && forked; ++q) forked = hip_ok(hipStreamWaitEvent(c->k1s[q], c->ev_fork, 0), "hipStreamWaitEvent(fork)");
-        if (forked) forked = hip_ok(hipStreamWaitEvent(c->xs, c->ev_fork, 0), "hipStreamWaitEvent(fork)");
-        for (int w = 0; w < nwaves && !xrc; ++w) {
-            hipStream_t ks = c->k1s[w & 1];
-            c->stream = ks;   // (the launchers below enqueue on the context's stream)
-            a.items = c->k1_wave_items[w].buf.p; c->k1_items_n = c->k1_wave_items[w].n;
-            if (c->k1_items_n) dispatch();
-            c->stream = main_stream;
-            if (!hip_ok(hipGetLastError(), "pair kernel launch")) break;
-            if (!hip_ok(hipEventRecord(c->ev_k1[w], ks), "hipEventRecord(wave)") || !hip_ok(hipStreamWaitEvent(c->xs, c->ev_k1[w], 0), "hipStreamWaitEvent(wave)")) break;
-            const int m0 = w * mw, mc = std::max(0, std::min(mw, maxu_x - m0));
-            if (mc == 0) continue;
-            uint32_t *send = c->xsend.p + uw * mw * w, *recv = c->xrecv.p + uw * mw * w * c->world;
-            const int64_t bytes = static_cast<int64_t>(uw) * mc * sizeof(uint32_t);
-            if ((xrc = launch_pack_units(c, m0, mc, send, c->xs))) break;
-            if (c->comm) { if ((xrc = comm_allgather(c, send, recv, bytes, c->xs)) < 0) break; xrc = REO_OK; }
-            else {
-                const int hrc = c->ag(send, recv, bytes, c->xs, c->ag_user);  // stream-ordered on the exchange stream
-                if (hrc) { set_error("all-gather hook failed with %d", hrc); xrc = REO_ECOMM; break; }
-            }
-            if ((xrc = launch_expand_units(c, m0, mc, recv, c->xs))) break;
-        }
-        // join: the pair kernels first (their makespan is the K1 stage time), then the exchange stream (what is left of it: the
-        // exposed part of the exchange).  A join that cannot even be queued falls back to host waits for the side streams.
-        bool joined = true;
-        for (int q = 0; q < 2; ++q)
-            if (hipEventRecord(c->ev_k1_join[q], c->k1s[q]) != hipSuccess || hipStreamWaitEvent(c->stream, c->ev_k1_join[q], 0) != hipSuccess) joined = false;
-        toc(c);
-        tic(c, 6);
-        if (hipEventRecord(c->ev_x, c->xs) != hipSuccess || hipStreamWaitEvent(c->stream, c->ev_x, 0) != hipSuccess) joined = false;
-        toc(c);
-        if (!joined) {
-            for (int q = 0; q < 2; ++q) (void)hipStreamSynchronize(c->k1s[q]);
-            (void)hipStreamSynchronize(c->xs);
-            if (!xrc) { set_error("joining the streams of the pipelined exchange failed"); xrc = REO_EHIP; }
-        }
-        if (xrc) return xrc;
-        c->x_pipelined = true;
-        return REO_OK;
+    return REO_OK;
+}
+
+// A range of the blocks of one side (pipelined upload): the launch counts blocks [b0, b1) of the side and parks, or picks up, the counts.
+// The item list is the side's (its key holds the side's WHOLE block count): every range of the side runs the same
+// items, so blockIdx.x names the same (tile, chunk) in each and the park slots line up
+static int32_t apply_range(reo_ctx *c, K1Args &a, int sides, const K1Range *range, size_t n_items)
+{
+    int32_t rc;
+    const int side = sides == 1 ? 0 : 1, sb = side ? a.tb : a.cb, se = side ? a.te : a.ce;
+    if (range->b0 < 0 || range->b1 <= range->b0 || sb + range->b1 > se || (range->first != (range->b0 == 0)) || (range->last != (sb + range->b1 == se))) {
+        set_error("a range of sample blocks outside its side"); return REO_EINVAL;
     }
-    if (wave || (wcounts && !c->gc_valid) || wmulti) {
+    if (!(range->first && range->last)) {
+        if ((rc = c->k1_park[side].ensure(std::max<size_t>(n_items, 1) * kParkSlot)) || (rc = c->k1_park_ge[side].ensure(std::max<size_t>(n_items, 1)))) return rc;
+        a.park = c->k1_park[side].p; a.park_ge = c->k1_park_ge[side].p;
+        a.park_mode = (range->first ? 0 : 1) | (range->last ? 0 : 2);
+    }
+    (side ? a.tb : a.cb) = sb + range->b0;
+    (side ? a.te : a.ce) = sb + range->b1;
+    return REO_OK;
+}
+
+// sides (wave form, two groups): which sides' items are launched -- bit 0 the comparison's own group, bit 1 the rest; 3 = the whole
+// table.  keep_table: the class table has been cleared by the caller and holds other sides' planes already (the pipelined upload,
+// transform.hip eager_upload, launches a side as soon as its group's samples are ranked).
+int32_t launch_k1(reo_ctx *c, int k, int sides, bool keep_table, const int32_t *gate, const K1Range *range, bool prepare)
+{
+    K1Args a = k1_args(c, k);
+    K1Plan pl;
+    int32_t rc;
+    if ((rc = k1_plan(c, sides, pl))) return rc;
+    const std::vector<uint32_t> &units = pl.units;
+    c->units_all_host = pl.units_all;
+    c->tiles_owned = pl.tiles_owned; c->tiles_total = pl.tiles_total;
+    c->k1_cj = pl.CJ; c->k1_q = pl.Q;
+    a.n_units = static_cast<int>(units.size()); a.Q = pl.Q;
+    if ((rc = upload_unit_map(c, units))) return rc;
+    a.unit_map = c->unit_map.p;
+    a.gate = gate;
+    if ((range || prepare) && (sides != 1 && sides != 2)) { set_error("a range of sample blocks / a prepared launch: one side of the pair kernel"); return REO_EINVAL; }
+    if (gate && (!pl.wave || pl.wide || pl.big)) { set_error("a gated launch of the pair kernel: wave form, at most 65535 genes and samples"); return REO_EINVAL; }
+    c->x_pipelined = false;
+    const int maxu_x = exchange_units_per_rank(c);
+    const int nwaves = (pl.wave && sides == 3 && c->world > 1 && (c->comm || c->ag) && !c->in_multi && !c->k1_stamps) ? std::min({c->x_waves, 8, maxu_x}) : 1;   // (a reo_create_multi context hands its packs to the leader itself: comm.hip)
+    if (nwaves > 1) {
+        hipStream_t main_stream = c->stream;
+        return pipelined_exchange(c, a, pl, nwaves, maxu_x, [&](int w, hipStream_t ks) {
+            c->stream = ks;   // (the launchers enqueue on the context's stream)
+            a.items = c->k1_wave_items[w].buf.p; c->k1_items_n = c->k1_wave_items[w].n;
+            if (c->k1_items_n) dispatch_pairs(c, a, pl);
+            c->stream = main_stream;
+        });
+    }
+    if (pl.wave || (pl.wcounts && !c->gc_valid) || pl.wmulti) {
         reo_ctx::ItemList &il = c->k1_wave_items[sides == 3 ? 0 : sides];   // (a side's list keeps its own slot: the two sides of a pipelined upload alternate)
         const auto w0 = std::chrono::steady_clock::now();
-        if ((rc = item_list(units, il, 0, 1))) return rc;
+        if ((rc = item_list(c, a, pl, sides, units, il, 0, 1))) return rc;
         if (c->debug_passes) fprintf(stderr, "  launch_k1 sides %d: item list (%zu items) ready after %.0f us\n", sides, il.n, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - w0).count());
         a.items = il.buf.p; c->k1_items_n = il.n;
         if (prepare) return REO_OK;   // (the unit map and this side's item list are on the device; nothing is launched)
-        if (range) {
-            // the item list above is the side's (its key holds the side's WHOLE block count): every range of the side runs the same
-            // items, so blockIdx.x names the same (tile, chunk) in each and the park slots line up
-            const int side = sides == 1 ? 0 : 1, sb = side ? a.tb : a.cb, se = side ? a.te : a.ce;
-            if (range->b0 < 0 || range->b1 <= range->b0 || sb + range->b1 > se || (range->first != (range->b0 == 0)) || (range->last != (sb + range->b1 == se))) {
-                set_error("a range of sample blocks outside its side"); return REO_EINVAL;
-            }
-            if (!(range->first && range->last)) {
-                if ((rc = c->k1_park[side].ensure(std::max<size_t>(il.n, 1) * kParkSlot)) || (rc = c->k1_park_ge[side].ensure(std::max<size_t>(il.n, 1)))) return rc;
-                a.park = c->k1_park[side].p; a.park_ge = c->k1_park_ge[side].p;
-                a.park_mode = (range->first ? 0 : 1) | (range->last ? 0 : 2);
-            }
-            (side ? a.tb : a.cb) = sb + range->b0;
-            (side ? a.te : a.ce) = sb + range->b1;
-        }
+        if (range && (rc = apply_range(c, a, sides, range, il.n))) return rc;
         if (c->k1_stamps) REO_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&a.stamps), (std::max<size_t>(c->k1_items_n, 1) * 4 + 2) * sizeof(unsigned long long)));
     }
     // (every reader of the table -- the passes, the pack, a sum hook's element count, the scan of a hook's table -- works on
@@ -4051,51 +4054,14 @@ int32_t launch_k1(reo_ctx *c, int k, int sides, bool keep_table, const int32_t *
         c->table_prezeroed = false;
     }
     if (units.empty()) return REO_OK;
-    c->last_k1_shared = shared ? 1 : 0;
+    c->last_k1_shared = pl.shared ? 1 : 0;
     if (a.stamps) k_time_mark<<<1, 64, 0, c->stream>>>(a.stamps + c->k1_items_n * 4);
     tic(c, 1);
-    dispatch();
+    dispatch_pairs(c, a, pl);
     toc(c);
     if (a.stamps) k_time_mark<<<1, 64, 0, c->stream>>>(a.stamps + c->k1_items_n * 4 + 1);
     REO_HIP_CHECK(hipGetLastError());
-    if (a.stamps) {  // diagnostic: where an item's time goes (100 MHz marks)
-        std::vector<unsigned long long> h(c->k1_items_n * 4 + 2);
-        REO_HIP_CHECK(hipMemcpyAsync(h.data(), a.stamps, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-        REO_HIP_CHECK(hipStreamSynchronize(c->stream));
-        double pro = 0, loop = 0, emit = 0;
-        unsigned long long t0 = ~0ull, t1 = 0;
-        for (size_t i = 0; i < c->k1_items_n; ++i) {
-            pro += static_cast<double>(h[4 * i + 1] - h[4 * i]); loop += static_cast<double>(h[4 * i + 2] - h[4 * i + 1]);
-            emit += static_cast<double>(h[4 * i + 3] - h[4 * i + 2]);
-            t0 = std::min(t0, h[4 * i]); t1 = std::max(t1, h[4 * i + 3]);
-        }
-        const double n = static_cast<double>(c->k1_items_n) * 100.0;  // marks per microsecond
-        fprintf(stderr, "[reo] K1 wave items %zu: prologue %.2f us, count loop %.2f us, classification %.2f us per item; first start to last end %.3f ms\n",
-                c->k1_items_n, pro / n, loop / n, emit / n, static_cast<double>(t1 - t0) / 1e5);
-        fprintf(stderr, "[reo]   a launch before it ended %.1f us before the first item began; one after it began %.1f us after the last item ended\n",
-                static_cast<double>(static_cast<long long>(t0 - h[c->k1_items_n * 4])) / 100.0, static_cast<double>(static_cast<long long>(h[c->k1_items_n * 4 + 1] - t1)) / 100.0);
-        // the launch in 24 slices of time: items in flight (average) and the count loop's duration of the items that started in the slice
-        constexpr int kSl = 24;
-        const double span = static_cast<double>(t1 - t0) + 1.0;
-        double busy[kSl] = {}, dur[kSl] = {};
-        size_t started[kSl] = {};
-        for (size_t i = 0; i < c->k1_items_n; ++i) {
-            const double b = static_cast<double>(h[4 * i] - t0), e = static_cast<double>(h[4 * i + 3] - t0);
-            const int s0 = static_cast<int>(b / span * kSl);
-            started[s0]++; dur[s0] += static_cast<double>(h[4 * i + 2] - h[4 * i + 1]);
-            for (int s = s0; s < kSl; ++s) {
-                const double lo = span * s / kSl, hi = span * (s + 1) / kSl;
-                if (e <= lo) break;
-                busy[s] += (std::min(e, hi) - std::max(b, lo)) / (hi - lo);
-            }
-        }
-        fprintf(stderr, "[reo]   items in flight by slice:");
-        for (int s = 0; s < kSl; ++s) fprintf(stderr, " %.0f", busy[s]);
-        fprintf(stderr, "\n[reo]   loop us of items started in slice:");
-        for (int s = 0; s < kSl; ++s) fprintf(stderr, " %.0f", started[s] ? dur[s] / static_cast<double>(started[s]) / 100.0 : 0.0);
-        fprintf(stderr, "\n");
-        (void)hipFree(a.stamps);
-    }
+    if (a.stamps) return report_k1_stamps(c, a.stamps);
     return REO_OK;
 }
 

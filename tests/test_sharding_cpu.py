@@ -270,6 +270,25 @@ def test_generated_count_loops_are_current(pkg):
     assert out == open(os.path.join(csrc, "k1_loop_gen.inc")).read()
 
 
+def test_k1_item_lists_keep_their_order(pkg, tmp_path):
+    """The order of the wave form's item list decides which XCD's L2 sees which chunk (DESIGN: 2.0 GB against 0.24 GB of L2 fills per
+    launch when it is wrong), and no parity test sees it: the class table does not depend on it.  csrc/k1_items.h makes the list
+    without a context or a GPU; tests/k1_items_driver.cpp prints length and FNV-1a digest for a table of geometries (BASELINE configs 3
+    and 4 as the bench runs them, the three orders, halves taken and not, 17 planes, more than 65 535 samples, single sides, a shard
+    of eight, a wave of a pipelined exchange, group counts), and tests/golden/k1_item_lists.json holds what the code recorded there
+    made of them."""
+    import json, subprocess
+    exe = str(tmp_path / "k1_items_driver")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "rankcompv3.jl_amd", "csrc"),
+                           "-o", exe, os.path.join(ROOT, "tests", "k1_items_driver.cpp")])
+    out = subprocess.run([exe], capture_output=True, text=True, check=True).stdout
+    got = {f[0]: {"items": int(f[1]), "half_items": int(f[2]), "fnv1a64": f[3]} for f in (l.split() for l in out.splitlines())}
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "k1_item_lists.json")))["lists"]
+    assert len(want) >= 12 and {"config3", "config4"} <= set(want)
+    assert want["config3"]["half_items"] > 0 and want["config4"]["half_items"] == 0   # halves taken, and not (REO_K1_HALF on in both)
+    assert got == want
+
+
 def test_digest_of_table_and_trace_sees_every_difference(pkg):
     """bench.py --gpus N refuses to time a sharded run whose class table, trace or tallies differ from the unsharded build's: the
     64-bit digest it compares (dist.table_trace_digest) must change when ONE pair's class, one trace entry or one tally changes, must

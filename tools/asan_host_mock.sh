@@ -14,7 +14,7 @@ SRC=rankcompv3.jl_amd/csrc
 CLANG=/opt/rocm/lib/llvm/bin/clang++
 g++ -O1 -g -fPIC -shared -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -o $B/libmockhip.so tools/mockhip/mockhip.cpp
 for f in api kernels transform pseudobulk comm; do
-  if [ ! -f $B/$f.o ] || [ $SRC/$f.hip -nt $B/$f.o ] || [ $SRC/reo_internal.h -nt $B/$f.o ] || [ include/reo_hip.h -nt $B/$f.o ]; then
+  if [ ! -f $B/$f.o ] || [ $SRC/$f.hip -nt $B/$f.o ] || [ $SRC/reo_internal.h -nt $B/$f.o ] || [ $SRC/k1_items.h -nt $B/$f.o ] || [ include/reo_hip.h -nt $B/$f.o ]; then
     /opt/rocm/bin/hipcc -O1 -g -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fsanitize=address -fno-gpu-sanitize \
         -Iinclude -I$SRC -c -o $B/$f.o $SRC/$f.hip &
   fi
