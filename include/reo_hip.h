@@ -133,9 +133,9 @@ int32_t reo_set_allgather(reo_ctx *ctx, reo_allgather_fn fn, void *user);
 
 /* Expression matrix, G genes x S samples, column-major with leading dimension
  * ld >= G: the `data` argument of identify_degs (src/RankCompV3.jl:340) as
- * Matrix(df_expr) produces it (:652), eltype Float64 or Int64.  G must be in [2, 262143] and S in [2, 1048576];
- * with more than two groups G and S may not both exceed 65535; values must be finite.  reo_set_matrix_f64 / _i64
- * copy from host memory (pageable is fine) and have read all of it when they return; *_dev uses a buffer already resident in HBM (it
+ * Matrix(df_expr) produces it (:652), eltype Float64, Int64, Float32 or Int32.  G must be in [2, 262143] and S in [2, 1048576];
+ * with more than two groups G and S may not both exceed 65535; values must be finite.  reo_set_matrix_f64 / _i64 /
+ * _f32 / _i32 copy from host memory (pageable is fine) and have read all of it when they return; *_dev uses a buffer already resident in HBM (it
  * must stay valid until reo_build_pairs returns).
  * ORDER OF CALLS.  Any order of reo_set_matrix_*, reo_set_groups, reo_compute_thresholds works.  From HOST memory the cheap order is
  * groups and thresholds FIRST, the matrix last: the call then uploads the columns in chunks and pipelines them with the rest of
@@ -151,11 +151,25 @@ int32_t reo_set_allgather(reo_ctx *ctx, reo_allgather_fn fn, void *user);
  * is false, which makes a NaN gene below every later and above every earlier gene -- row order, not an ordering.
  * A context that is used for several matrices should keep to that order each time: a matrix handed over while the groups of the LAST
  * problem are still set is ranked and paired with those, and all of it is done again when the new groups arrive (correct, but wasted).
- * REO_EAGER_UPLOAD=0 in the environment switches the pipelining off, =1 keeps it to the ranking. */
+ * REO_EAGER_UPLOAD=0 in the environment switches the pipelining off, =1 keeps it to the ranking.
+ * ELEMENT TYPES.  A matrix is compared in the arithmetic of its own element type, as the reference's is_greater compares a
+ * Matrix of that type.  FLOAT32 RULE: x and y are tied iff (double)fabsf(x - y) < 0.1 -- the difference is formed and rounded (to
+ * nearest, subnormals kept) in Float32 and then compared with the Float64 literal 0.1; equivalently fabsf(x - y) <= 0x1.999998p-4f.
+ * Float32(0.1) = 0.100000001... is not below 0.1, so a pair whose exact difference lies in [0.09999999776, 0.1) and rounds up to
+ * Float32(0.1) is NOT tied, where the same values widened to Float64 would be; wherever x - y is exact in Float32 (every pair within a
+ * factor two of each other) the two agree.  A caller who wants the Float64 rule widens the matrix and calls _f64.  The Float32 matrix
+ * is ranked from a resident Float32 copy (4 bytes per value on the link and in HBM); no Float64 copy is made.  Int32 has Int64's rule
+ * (a tie is equality): _i32 sends the 4-byte values over the link and widens them on the device into the context's own Int64 matrix,
+ * _dev_i32 widens once on the context's stream (the caller's buffer has been read when it returns); results are bit-identical to
+ * _i64 on the same values.  REO_TRANSFORM=segmented (the A/B build) is refused for these two types. */
 int32_t reo_set_matrix_f64(reo_ctx *ctx, const double *X, int64_t G, int64_t S, int64_t ld);
 int32_t reo_set_matrix_i64(reo_ctx *ctx, const int64_t *X, int64_t G, int64_t S, int64_t ld);
 int32_t reo_set_matrix_dev_f64(reo_ctx *ctx, const void *dX, int64_t G, int64_t S, int64_t ld);
 int32_t reo_set_matrix_dev_i64(reo_ctx *ctx, const void *dX, int64_t G, int64_t S, int64_t ld);
+int32_t reo_set_matrix_f32(reo_ctx *ctx, const float *X, int64_t G, int64_t S, int64_t ld);
+int32_t reo_set_matrix_i32(reo_ctx *ctx, const int32_t *X, int64_t G, int64_t S, int64_t ld);
+int32_t reo_set_matrix_dev_f32(reo_ctx *ctx, const void *dX, int64_t G, int64_t S, int64_t ld);
+int32_t reo_set_matrix_dev_i32(reo_ctx *ctx, const void *dX, int64_t G, int64_t S, int64_t ld);
 
 /* Group of each sample: the `group` argument (src/RankCompV3.jl:341) recoded
  * to 0-based ids in order of first appearance (unique(), :353).  Length must
@@ -251,8 +265,8 @@ int32_t reo_pseudobulk_csc_i64(reo_ctx *ctx, int64_t G, int64_t C, const int64_t
  * statistics kernels K3, sum), 4 number of K2 launches (passes enqueued after
  * convergence return at once and are counted too), 5 number of K1 launches,
  * 6 exchange of the class table between shards (HIP events), 7 pseudo-bulk kernel, 8 K2 stage of the passes that scanned the whole table (sum), 9 their
- * number, 10 K2 stage of the passes that updated the tallies incrementally (sum), 11 host wall time inside reo_set_matrix_f64 / _i64
- * (the upload from host memory, with whatever was pipelined behind it). */
+ * number, 10 K2 stage of the passes that updated the tallies incrementally (sum), 11 host wall time inside reo_set_matrix_f64 / _i64 /
+ * _f32 / _i32 (the upload from host memory, with whatever was pipelined behind it). */
 enum { REO_NTIMINGS = 12 };
 int32_t reo_set_profiling(reo_ctx *ctx, int32_t on);
 int32_t reo_reset_timings(reo_ctx *ctx);
@@ -273,7 +287,8 @@ int32_t reo_get_timings(reo_ctx *ctx, double *ms, int32_t n);
  * were then skipped instead of executed (see reo_identify_degs; REO_CYCLE=0 switches the watch off), 19 the bytes that the last
  * reo_set_matrix_i64 / _f64 put on the PCIe link (chunks whose values all fit travel as int16 / int32 -- Float64 chunks of
  * integer-valued or single-precision numbers too, as int16 / int32 / float32 -- converted by REO_UPLOAD_THREADS host threads,
- * default 12, and widened on the device: bit-exact; 0 threads = the caller's array as it is), 20 the launches of the pair kernel that
+ * default 12, and widened on the device: bit-exact; 0 threads = the caller's array as it is; reo_set_matrix_f32 / _i32: the caller's
+ * array as it is, 4 bytes per value, no host threads), 20 the launches of the pair kernel that
  * the last pipelined reo_set_matrix_* made over a RANGE of a group's sample blocks (the pair kernel then starts before the whole group
  * has arrived; the counts of a range wait in HBM for the group's last range, which classifies -- REO_EAGER_RANGES=1 in the environment
  * launches whole sides only, as in round 5; 2..6 asks for that many ranges per side; default: by the number of blocks). */

@@ -40,7 +40,13 @@ function identify_degs(data::AbstractMatrix, group::AbstractVector, gene_names::
         # pair kernel's group-1 side while group 2 is still on its way over PCIe (include/reo_hip.h)
         check(ccall((:reo_set_groups, LIB), Int32, (Ptr{Cvoid}, Ptr{Int32}, Int64, Int32), ctx[], gid, c, length(glev)))
         check(ccall((:reo_compute_thresholds, LIB), Int32, (Ptr{Cvoid}, Float64), ctx[], pval_reo))           # :362
-        if eltype(data) <: Integer
+        if eltype(data) === Float32                     # compared in Float32 arithmetic, as is_greater(::Float32, ::Float32) does (:71-77)
+            X = convert(Matrix{Float32}, data)
+            check(ccall((:reo_set_matrix_f32, LIB), Int32, (Ptr{Cvoid}, Ptr{Float32}, Int64, Int64, Int64), ctx[], X, r, c, r))
+        elseif eltype(data) === Int32
+            X = convert(Matrix{Int32}, data)
+            check(ccall((:reo_set_matrix_i32, LIB), Int32, (Ptr{Cvoid}, Ptr{Int32}, Int64, Int64, Int64), ctx[], X, r, c, r))
+        elseif eltype(data) <: Integer
             X = convert(Matrix{Int64}, data)            # (no copy when `data` is a Matrix{Int64} already: Matrix(df_expr) of counts)
             check(ccall((:reo_set_matrix_i64, LIB), Int32, (Ptr{Cvoid}, Ptr{Int64}, Int64, Int64, Int64), ctx[], X, r, c, r))
         else

@@ -23,6 +23,7 @@ SYMBOLS = [
     "reo_version", "reo_last_error", "reo_create", "reo_destroy", "reo_trim_memory", "reo_set_shard", "reo_set_allreduce", "reo_set_allgather",
     "reo_create_multi", "reo_comm_unique_id", "reo_comm_init_rank",
     "reo_set_matrix_f64", "reo_set_matrix_i64", "reo_set_matrix_dev_f64", "reo_set_matrix_dev_i64",
+    "reo_set_matrix_f32", "reo_set_matrix_i32", "reo_set_matrix_dev_f32", "reo_set_matrix_dev_i32",
     "reo_set_groups", "reo_compute_thresholds", "reo_set_thresholds", "reo_get_thresholds", "reo_threshold",
     "reo_build_pairs", "reo_pair_counts", "reo_get_codes", "reo_tally", "reo_identify_degs", "reo_mccullagh",
     "reo_set_profiling", "reo_reset_timings", "reo_get_timings", "reo_get_info",
@@ -92,6 +93,10 @@ def lib() -> ctypes.CDLL:
         "reo_set_matrix_i64": (i32, [vp, vp, i64, i64, i64]),
         "reo_set_matrix_dev_f64": (i32, [vp, vp, i64, i64, i64]),
         "reo_set_matrix_dev_i64": (i32, [vp, vp, i64, i64, i64]),
+        "reo_set_matrix_f32": (i32, [vp, vp, i64, i64, i64]),
+        "reo_set_matrix_i32": (i32, [vp, vp, i64, i64, i64]),
+        "reo_set_matrix_dev_f32": (i32, [vp, vp, i64, i64, i64]),
+        "reo_set_matrix_dev_i32": (i32, [vp, vp, i64, i64, i64]),
         "reo_set_groups": (i32, [vp, vp, i64, i32]),
         "reo_compute_thresholds": (i32, [vp, f64]),
         "reo_set_thresholds": (i32, [vp, vp]),
@@ -146,6 +151,33 @@ def _ptr(a: np.ndarray) -> int:
     return a.ctypes.data
 
 
+# element types with an entry point of their own; every other integer type (and bool) goes to Int64, every other float type to Float64
+_NATIVE = {np.dtype(np.float64): "f64", np.dtype(np.int64): "i64", np.dtype(np.float32): "f32", np.dtype(np.int32): "i32"}
+
+
+def matrix_entry(X):
+    """(symbol name, array, ld) for a host expression matrix (genes x samples): which reo_set_matrix_* takes it, the column-major array
+    that is handed over and its leading dimension in elements.  Pure: no library, no GPU.  A column-major array (or view with
+    ld >= G, like a Julia view of rows of a taller matrix) of Float64 / Int64 / Float32 / Int32 is passed as it is, WITHOUT a copy; a
+    Float32 matrix is then compared in Float32 arithmetic, as the reference compares a Matrix{Float32} (X.astype(np.float64) asks for
+    the Float64 rule).  Narrower integers and bool are converted to Int64, every other float type to Float64, on the host."""
+    X = np.asarray(X)
+    if X.ndim != 2:
+        raise DimensionMismatch(REO_EINVAL, "expression matrix must be 2-D (genes x samples)")
+    if X.dtype in _NATIVE:
+        want = X.dtype
+    else:
+        want = np.dtype(np.int64) if (np.issubdtype(X.dtype, np.integer) or X.dtype == np.bool_) else np.dtype(np.float64)
+    G, S = X.shape
+    sz = want.itemsize
+    if X.dtype == want and G > 0 and S > 1 and X.strides[0] == sz and X.strides[1] % sz == 0 and X.strides[1] >= sz * G:
+        Xf, ld = X, X.strides[1] // sz
+    else:
+        Xf = np.asfortranarray(X, dtype=want)
+        ld = max(G, 1)
+    return "reo_set_matrix_" + _NATIVE[want], Xf, ld
+
+
 UNIQUE_ID_BYTES = 128
 
 
@@ -154,6 +186,31 @@ def comm_unique_id() -> bytes:
     buf = ctypes.create_string_buffer(UNIQUE_ID_BYTES)
     check(lib().reo_comm_unique_id(buf))
     return buf.raw
+
+
+def is_device_tensor(data) -> bool:
+    """A torch tensor that lives on a GPU (without importing torch for anything that is not one)."""
+    return type(data).__module__.split(".")[0] == "torch" and hasattr(data, "data_ptr") and bool(getattr(data, "is_cuda", False))
+
+
+def device_matrix(t):
+    """(device pointer, G, S, ld, dtype name, tensor to keep alive) for a 2-D torch tensor on a ROCm device.  Plumbing only: a tensor
+    of float64 / int64 / float32 / int32 whose strides are (1, ld), ld >= G -- column-major -- is used in place; any other layout is
+    made column-major ON THE DEVICE (t.t().contiguous().t()), other dtypes are cast on the device first (integers and bool to int64,
+    floats to float64).  The stream that produced the tensor is synchronised before the pointer is handed over; the caller keeps the
+    returned tensor alive until build_pairs has returned."""
+    import torch
+    if t.dim() != 2:
+        raise DimensionMismatch(REO_EINVAL, "expression matrix must be 2-D (genes x samples)")
+    names = {torch.float64: "f64", torch.int64: "i64", torch.float32: "f32", torch.int32: "i32"}
+    t = t.detach()
+    if t.dtype not in names:
+        t = t.to(torch.float64 if t.dtype.is_floating_point else torch.int64)
+    G, S = t.shape
+    if not (G > 0 and S > 1 and t.stride(0) == 1 and t.stride(1) >= G):
+        t = t.t().contiguous().t()   # column-major, ld = G
+    torch.cuda.current_stream(t.device).synchronize()
+    return int(t.data_ptr()), int(G), int(S), int(t.stride(1)) if S > 1 else int(max(G, 1)), names[t.dtype], t
 
 
 class Context:
@@ -189,28 +246,26 @@ class Context:
 
     # -- problem definition -------------------------------------------------
     def set_matrix(self, X: np.ndarray) -> None:
-        """X is genes x samples (host); Float64 or any integer dtype (-> Int64), like Matrix(df_expr)."""
-        X = np.asarray(X)
-        if X.ndim != 2:
-            raise DimensionMismatch(REO_EINVAL, "expression matrix must be 2-D (genes x samples)")
-        integer = np.issubdtype(X.dtype, np.integer) or X.dtype == np.bool_
-        fn = self._L.reo_set_matrix_i64 if integer else self._L.reo_set_matrix_f64
-        want = np.int64 if integer else np.float64
-        G, S = X.shape
-        if X.dtype == want and G > 0 and S > 1 and X.strides[0] == 8 and X.strides[1] % 8 == 0 and X.strides[1] >= 8 * G:
-            Xf, ld = X, X.strides[1] // 8  # a column-major view (rows of a taller matrix): passed as is, like a Julia view
-        else:
-            Xf = np.asfortranarray(X, dtype=want)
-            ld = max(G, 1)
-        check(fn(self._h, _ptr(Xf), G, S, ld))
+        """X is genes x samples (host); Float64, Float32, Int64 or Int32 as it is, any other integer dtype -> Int64, any other float
+        dtype -> Float64 (matrix_entry), like Matrix(df_expr)."""
+        name, Xf, ld = matrix_entry(X)
+        G, S = Xf.shape
+        check(getattr(self._L, name)(self._h, _ptr(Xf), G, S, ld))
         self.G, self.S = G, S
 
     def set_matrix_device(self, dev_ptr: int, G: int, S: int, ld: int, dtype: str, keepalive=None) -> None:
-        """Column-major matrix already resident in HBM (dtype 'f64' or 'i64')."""
-        fn = self._L.reo_set_matrix_dev_f64 if dtype == "f64" else self._L.reo_set_matrix_dev_i64
+        """Column-major matrix already resident in HBM (dtype 'f64', 'i64', 'f32' or 'i32')."""
+        if dtype not in ("f64", "i64", "f32", "i32"):
+            raise DimensionMismatch(REO_EINVAL, f"dtype {dtype!r}: a device matrix is 'f64', 'i64', 'f32' or 'i32'")
+        fn = getattr(self._L, "reo_set_matrix_dev_" + dtype)
         check(fn(self._h, ctypes.c_void_p(dev_ptr), G, S, ld))
         self._keep.append(keepalive)
         self.G, self.S = G, S
+
+    def set_matrix_tensor(self, t) -> None:
+        """A torch tensor on the context's device (genes x samples) as the expression matrix: see device_matrix."""
+        ptr, G, S, ld, dtype, keep = device_matrix(t)
+        self.set_matrix_device(ptr, G, S, ld, dtype, keepalive=keep)
 
     def set_groups(self, group_id, ngroups: int) -> None:
         gid = np.ascontiguousarray(group_id, dtype=np.int32)

@@ -351,10 +351,17 @@ static void invalidate(reo_ctx *c)
     c->eager_k1 = false;
 }
 
+// dtype: what the caller hands over -- 1 Float64, 2 Int64, 3 Float32, 4 Int32 (which becomes a resident Int64 matrix: its tie is equality)
+static size_t elem_bytes(int dtype) { return dtype >= 3 ? 4 : 8; }
+
 static int32_t set_matrix(reo_ctx *c, const void *X, int64_t G, int64_t S, int64_t ld, int dtype, bool on_device)
 {
     int32_t rc = use(c);
     if (rc) return rc;
+    if (dtype >= 3 && getenv("REO_TRANSFORM") && getenv("REO_TRANSFORM")[0] == 's') {
+        set_error("REO_TRANSFORM=segmented: the segmented sort of the A/B build takes Float64 and Int64 matrices only, not Float32 / Int32");
+        return REO_EINVAL;
+    }
     if (!X) { set_error("matrix pointer is null"); return REO_EINVAL; }
     if (G < 2 || G > kMaxGenes || S < 2 || S > (1 << 20)) {
         set_error("matrix is %lld x %lld; G must be in [2, %d] and S in [2, 1048576]", (long long)G, (long long)S, kMaxGenes);
@@ -362,12 +369,20 @@ static int32_t set_matrix(reo_ctx *c, const void *X, int64_t G, int64_t S, int64
     }
     if (ld < G) { set_error("leading dimension %lld < G = %lld", (long long)ld, (long long)G); return REO_EINVAL; }
     invalidate(c);
-    c->G = G; c->S = S; c->dtype = dtype;
-    if (on_device) {
+    const bool host_i32 = dtype == 4 && !on_device;
+    const size_t resident = static_cast<size_t>(G) * S * (dtype == 3 ? 4 : 8);   // bytes of the matrix the kernels read
+    c->G = G; c->S = S; c->dtype = dtype == 4 ? 2 : dtype;
+    if (on_device && dtype == 4) {
+        // widened once into the context's own Int64 matrix; the caller's buffer has been read when the call returns
+        if ((rc = c->dX_owned.ensure(resident))) return rc;
+        c->dX = c->dX_owned.p; c->ld = G;
+        if ((rc = widen_device_i32(c, X, ld, G, S, c->dX_owned.p))) { invalidate(c); c->dtype = 0; return rc; }
+        if (hipStreamSynchronize(c->stream) != hipSuccess) { set_error("widening the Int32 matrix failed"); invalidate(c); c->dtype = 0; return REO_EHIP; }
+    } else if (on_device) {
         c->dX = X; c->ld = ld;
         c->dX_owned.release();
     } else {
-        if ((rc = c->dX_owned.ensure(static_cast<size_t>(G) * S * 8))) return rc;
+        if ((rc = c->dX_owned.ensure(resident))) return rc;
         c->dX = c->dX_owned.p; c->ld = G;
         // Groups already set (the order the Julia shim and hotpath.py use): the upload is pipelined with the per-sample transform
         // and -- two groups, thresholds set, one GPU -- with the pair kernel's group-0 side (transform.hip, eager_upload).
@@ -384,7 +399,7 @@ static int32_t set_matrix(reo_ctx *c, const void *X, int64_t G, int64_t S, int64
                 ~DrainUp() { if (c->up) (void)hipStreamSynchronize(c->up); if (c->rk) (void)hipStreamSynchronize(c->rk); }
             } drain_up{c};
             DrainOnExit drain(c);
-            rc = eager_upload(c, X, ld, k1);
+            rc = eager_upload(c, X, ld, k1, host_i32);
             if (rc) { invalidate(c); return rc; }
             drain.dismiss();   // (the pair kernel may still be running, as after reo_build_pairs on one GPU: it reads device memory only)
             c->t_ms[11] += (wall_us() - w0) * 1e-3;
@@ -546,7 +561,7 @@ using namespace reo;
 
 extern "C" {
 
-int32_t reo_version(void) { return 100; }
+int32_t reo_version(void) { return 200; }
 
 int32_t reo_trim_memory(void)
 {
@@ -736,14 +751,18 @@ static int32_t set_matrix_all(reo_ctx *c, const void *X, int64_t G, int64_t S, i
     for (size_t d = 0; d < (c ? c->peers.size() : 0) && !rc; ++d) {
         reo_ctx *p = c->peers[d];
         if (!on_device) { rc = set_matrix(p, X, G, S, ld, dtype, false); continue; }
-        if ((rc = use(p)) || (rc = p->dX_owned.ensure(static_cast<size_t>(G) * S * 8))) break;
+        // (an Int32 device matrix: the leader has widened it into its own Int64 matrix, which is what the peers copy)
+        const void *src = dtype == 4 ? c->dX : X;
+        const int64_t sld = dtype == 4 ? G : ld;
+        const size_t eb = dtype == 4 ? 8 : elem_bytes(dtype);
+        if ((rc = use(p)) || (rc = p->dX_owned.ensure(static_cast<size_t>(G) * S * eb))) break;
         // one 2-D copy (the source may have a leading dimension); unified addressing finds the source device
-        if (hipMemcpy2DAsync(p->dX_owned.p, static_cast<size_t>(G) * 8, X, static_cast<size_t>(ld) * 8, static_cast<size_t>(G) * 8, static_cast<size_t>(S),
+        if (hipMemcpy2DAsync(p->dX_owned.p, static_cast<size_t>(G) * eb, src, static_cast<size_t>(sld) * eb, static_cast<size_t>(G) * eb, static_cast<size_t>(S),
                              hipMemcpyDefault, p->stream) != hipSuccess) {
             set_error("peer copy of the matrix to device %d failed", p->device); rc = REO_EHIP;
         }
         if (!rc && hipStreamSynchronize(p->stream) != hipSuccess) { set_error("peer copy failed"); rc = REO_EHIP; }
-        if (!rc) { invalidate(p); p->G = G; p->S = S; p->dtype = dtype; p->dX = p->dX_owned.p; p->ld = G; }
+        if (!rc) { invalidate(p); p->G = G; p->S = S; p->dtype = dtype == 4 ? 2 : dtype; p->dX = p->dX_owned.p; p->ld = G; }
     }
     if (c && !c->peers.empty()) (void)hipSetDevice(c->device);
     return rc;
@@ -753,6 +772,10 @@ int32_t reo_set_matrix_f64(reo_ctx *c, const double *X, int64_t G, int64_t S, in
 int32_t reo_set_matrix_i64(reo_ctx *c, const int64_t *X, int64_t G, int64_t S, int64_t ld) { return set_matrix_all(c, X, G, S, ld, 2, false); }
 int32_t reo_set_matrix_dev_f64(reo_ctx *c, const void *dX, int64_t G, int64_t S, int64_t ld) { return set_matrix_all(c, dX, G, S, ld, 1, true); }
 int32_t reo_set_matrix_dev_i64(reo_ctx *c, const void *dX, int64_t G, int64_t S, int64_t ld) { return set_matrix_all(c, dX, G, S, ld, 2, true); }
+int32_t reo_set_matrix_f32(reo_ctx *c, const float *X, int64_t G, int64_t S, int64_t ld) { return set_matrix_all(c, X, G, S, ld, 3, false); }
+int32_t reo_set_matrix_i32(reo_ctx *c, const int32_t *X, int64_t G, int64_t S, int64_t ld) { return set_matrix_all(c, X, G, S, ld, 4, false); }
+int32_t reo_set_matrix_dev_f32(reo_ctx *c, const void *dX, int64_t G, int64_t S, int64_t ld) { return set_matrix_all(c, dX, G, S, ld, 3, true); }
+int32_t reo_set_matrix_dev_i32(reo_ctx *c, const void *dX, int64_t G, int64_t S, int64_t ld) { return set_matrix_all(c, dX, G, S, ld, 4, true); }
 
 int32_t reo_set_groups(reo_ctx *c, const int32_t *group_id, int64_t len, int32_t ngroups)
 {

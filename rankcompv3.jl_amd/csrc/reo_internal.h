@@ -182,7 +182,7 @@ struct reo_ctx {
 
     // problem
     int64_t G = 0, S = 0, ld = 0;
-    int dtype = 0;  // 0 none, 1 f64, 2 i64
+    int dtype = 0;  // of the resident matrix: 0 none, 1 f64, 2 i64, 3 f32 (Int32 input is widened to Int64: 2)
     const void *dX = nullptr;
     reo::DevBuf<unsigned char> dX_owned;
     std::vector<int32_t> group_id;
@@ -337,8 +337,10 @@ namespace reo {
 
 // transform.hip
 int32_t run_transform(reo_ctx *c);
-int32_t eager_upload(reo_ctx *c, const void *hX, int64_t hld, bool with_k1);  // host matrix -> HBM in chunks, ranked (and paired) as they arrive
+// host matrix -> HBM in chunks, ranked (and paired) as they arrive (host_i32: the host array is Int32, the resident matrix Int64)
+int32_t eager_upload(reo_ctx *c, const void *hX, int64_t hld, bool with_k1, bool host_i32 = false);
 int32_t upload_columns(reo_ctx *c, const void *hX, int64_t hld, int64_t G, int64_t ncols, void *dX, int dtype);  // a host matrix into a device matrix (ld = G), chunked, Int64 narrowed
+int32_t widen_device_i32(reo_ctx *c, const void *dX32, int64_t ld, int64_t G, int64_t S, void *dX64);  // a device Int32 matrix into a dense Int64 one, on c->stream
 int32_t ensure_upload_streams(reo_ctx *c);                                      // c->up, c->rk and their events (created on first use)
 int32_t ensure_staging(reo_ctx *c, size_t slot_bytes);                          // three pinned + device staging slots of at least that size, their events
 void host_parallel(int nthreads, int ntasks, const std::function<void(int)> &fn);   // fn(0 .. ntasks - 1) on the process-wide pool of host threads (and the caller)

@@ -66,6 +66,7 @@ struct Codec<double> {
         uint64_t u = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFULL) : ~k;
         return __longlong_as_double(u);
     }
+    static constexpr int kLowZero = 0;   // low bits of a code that are zero for every value
     __device__ static bool tie(double x, double y) { return fabs(x - y) < 0.1; }
     // is_greater (/root/reference/src/RankCompV3.jl:71-77) on infinities: abs(Inf - Inf) = NaN is not < 0.1 and Inf > Inf is false, so
     // EQUAL infinities are neither tied nor greater -- the pair (i, j), i < j, counts as "i not greater" in that sample, every time, no
@@ -88,12 +89,47 @@ struct Codec<double> {
 template <>
 struct Codec<int64_t> {
     __device__ static uint64_t enc(int64_t x) { return static_cast<uint64_t>(x) ^ 0x8000000000000000ULL; }
+    static constexpr int kLowZero = 0;
     __device__ static int64_t dec(uint64_t k) { return static_cast<int64_t>(k ^ 0x8000000000000000ULL); }
     // abs(x - y) < 0.1 on Int64 <=> x == y
     __device__ static bool tie(int64_t x, int64_t y) { return x == y; }
     __device__ static uint64_t enc(int64_t x, uint32_t) { return enc(x); }
     __device__ static bool ordered(int64_t) { return true; }
 };
+
+// Float32 input (Matrix{Float32}): is_greater(x::Float32, y::Float32) evaluates abs(x - y) in Float32 (rounded to nearest, subnormals
+// kept: this unit is compiled without a flush flag) and compares that with the Float64 literal 0.1 -- Float32(0.1) = 0.100000001... is
+// NOT below it, so a difference that rounds up to Float32(0.1) is "not tied" where the widened values would be.
+// The order-preserving code of the 32 value bits sits in the HIGH half of the 64-bit code space of the bucket machinery (the low half is
+// zero: kLowZero), so "16 equal pieces of a code interval" stay 16 pieces however narrow the interval is in Float32 codes.
+template <>
+struct Codec<float> {
+    static constexpr int kLowZero = 32;
+    __device__ static uint64_t enc(float x)
+    {
+        const uint32_t u = __float_as_uint(x);
+        return static_cast<uint64_t>((u >> 31) ? ~u : (u | 0x80000000u)) << 32;
+    }
+    __device__ static float dec(uint64_t k)
+    {
+        const uint32_t c = static_cast<uint32_t>(k >> 32);
+        return __uint_as_float((c >> 31) ? (c & 0x7FFFFFFFu) : ~c);
+    }
+    __device__ static bool tie(float x, float y) { return static_cast<double>(fabsf(x - y)) < 0.1; }
+    // infinities as in Codec<double>: gene g's +-Inf gets a code of its own among the NaN codes (2^23 payloads per sign, g <= 262 142),
+    // which dec() turns into a NaN -- tied with nothing, and equal infinities in gene order
+    static constexpr uint64_t kPosInf = 0xFF800000ULL << 32, kNegInf = 0x007FFFFFULL << 32;   // enc(+Inf), enc(-Inf)
+    __device__ static uint64_t enc(float x, uint32_t g)
+    {
+        const uint64_t k = enc(x);
+        return k == kPosInf ? k + (static_cast<uint64_t>(g) << 32)
+                            : (k == kNegInf ? k - (static_cast<uint64_t>(static_cast<uint32_t>(kMaxGenes) - g) << 32) : k);
+    }
+    __device__ static bool ordered(float x) { return x == x; }
+};
+
+// input types whose tie band is wider than the equal values (the 0.1 band of is_greater): band edges are searched in code space
+template <class T> constexpr bool kBanded = std::is_floating_point<T>::value;
 
 #ifdef REO_WITH_ROCPRIM   // the segmented-sort form of the transform (rounds 1-4): built for A/B runs only (make ROCPRIM=1)
 template <class T, class IdxT>
@@ -528,22 +564,28 @@ __host__ __device__ constexpr size_t wide_lds_head(size_t nb, bool h16 = false)
 template <class T>
 __device__ __forceinline__ bool code_tied(uint64_t c, T x) { return Codec<T>::tie(Codec<T>::dec(c), x); }
 
-// smallest code <= cx that is tied with x (DOWN) / largest code >= cx that is (UP): the band of x in code space
-template <bool UP>
-__device__ __forceinline__ uint64_t band_edge_code(double x, uint64_t cx)
+// smallest code <= cx that is tied with x (DOWN) / largest code >= cx that is (UP): the band of x in code space.  The search runs over
+// the codes of the input's own format (Float32: the high half of the 64-bit code, in units of one Float32 code) with the predicate of
+// that format; fl(x - y) is monotone in y in any round-to-nearest format.
+template <bool UP, class T>
+__device__ __forceinline__ uint64_t band_edge_code(T x, uint64_t cx64)
 {
-    uint64_t g = Codec<double>::enc(UP ? x + 0.1 : x - 0.1);
+    constexpr int Z = Codec<T>::kLowZero;
+    constexpr uint64_t kLast = ~0ULL >> Z;   // the last code, in units
+    auto tied = [&](uint64_t u) { return code_tied<T>(u << Z, x); };
+    const uint64_t cx = cx64 >> Z;
+    uint64_t g = Codec<T>::enc(UP ? x + static_cast<T>(0.1) : x - static_cast<T>(0.1)) >> Z;
     if (UP ? g < cx : g > cx) g = cx;
     // invariant of both branches: `in` is tied, `out` is not (or is the end of the code space), in between unknown
     uint64_t in, out;
-    if (code_tied<double>(g, x)) {  // walk away from cx while the codes stay tied
+    if (tied(g)) {  // walk away from cx while the codes stay tied
         in = g;
         uint64_t step = 1;
         while (true) {
-            const bool room = UP ? (in <= ~0ULL - step) : (in >= step);
-            if (!room) { out = UP ? ~0ULL : 0ULL; if (code_tied<double>(out, x)) return out; break; }
+            const bool room = UP ? (in <= kLast - step) : (in >= step);
+            if (!room) { out = UP ? kLast : 0ULL; if (tied(out)) return out << Z; break; }
             const uint64_t n = UP ? in + step : in - step;
-            if (!code_tied<double>(n, x)) { out = n; break; }
+            if (!tied(n)) { out = n; break; }
             in = n; step <<= 1;
         }
     } else {  // walk towards cx (which is tied with itself) until a code is tied
@@ -553,15 +595,15 @@ __device__ __forceinline__ uint64_t band_edge_code(double x, uint64_t cx)
             const uint64_t dist = UP ? out - cx : cx - out;
             if (step >= dist) { in = cx; break; }
             const uint64_t n = UP ? out - step : out + step;
-            if (code_tied<double>(n, x)) { in = n; break; }
+            if (tied(n)) { in = n; break; }
             out = n; step <<= 1;
         }
     }
     while ((UP ? out - in : in - out) > 1) {
         const uint64_t mid = UP ? in + (out - in) / 2 : out + (in - out) / 2;
-        if (code_tied<double>(mid, x)) in = mid; else out = mid;
+        if (tied(mid)) in = mid; else out = mid;
     }
-    return in;
+    return in << Z;
 }
 
 // GENL: the by-slot gene row lives in LDS beside the offset row (4 bytes per gene: up to 32 768 genes); else in a scratch row (L2) --
@@ -666,7 +708,7 @@ __global__ __launch_bounds__(1024) void t_sample_wide(const T *__restrict__ X, i
         bucket = lb * PER + static_cast<uint32_t>(o >> sh);
         const int rs = sh > 16 ? sh - 16 : 0;
         r16 = static_cast<uint32_t>((o & ((1ULL << sh) - 1ULL)) >> rs);
-        exact = sh <= 16;
+        exact = sh <= 16 + Codec<T>::kLowZero;   // (the bits below the 16 kept ones are zero in every code)
     };
     TSTAMP(2);
     // ---- 2. histogram; arrival slot (+ `exact` in bit 15), bucket and r16 parked in the pos / lo / hi rows
@@ -785,7 +827,7 @@ __global__ __launch_bounds__(1024) void t_sample_wide(const T *__restrict__ X, i
             }
             l = s0 + smaller; h = l + equal; p = l + before;
         }
-        if constexpr (std::is_same<T, double>::value) {  // the band is wider than the equal values: two more rank queries
+        if constexpr (kBanded<T>) {  // the band is wider than the equal values: two more rank queries
             if (!isinf(x)) {   // (an infinity's code is its own: l = p, h = p + 1 from the scan above -- tied with nothing, :72)
                 l = rank_of(band_edge_code<false>(x, k), false);
                 h = rank_of(band_edge_code<true>(x, k), true);
@@ -907,7 +949,7 @@ __global__ __launch_bounds__(1024) void t_sample_big(const T *__restrict__ X, in
         bucket = lb * PER + static_cast<uint32_t>(o >> sh);
         const int rs = sh > 16 ? sh - 16 : 0;
         r16 = static_cast<uint32_t>((o & ((1ULL << sh) - 1ULL)) >> rs);
-        exact = sh <= 16;
+        exact = sh <= 16 + Codec<T>::kLowZero;   // (the bits below the 16 kept ones are zero in every code)
     };
     // ---- 2. histogram; the arrival slot is parked in the pos row, bucket word and offset bits in the lo row (32-bit rows)
 #pragma unroll 2
@@ -976,7 +1018,7 @@ __global__ __launch_bounds__(1024) void t_sample_big(const T *__restrict__ X, in
         const bool exact = (bw & 0x8000u) != 0;
         // The gene's own value is a scattered 8-byte read of a column that no cache holds at this size (256 workgroups x 0.5-2 MB): only
         // Float64 (band edges) and a bucket wider than 2^16 codes need it -- an Int64 key in an exact bucket IS (bucket, offset bits).
-        const bool need_x = std::is_same<T, double>::value || !exact;
+        const bool need_x = kBanded<T> || !exact;
         T x = T(0);
         uint64_t k = 0;
         if (need_x) { x = col[gene]; k = Codec<T>::enc(x, gene); }
@@ -1004,7 +1046,7 @@ __global__ __launch_bounds__(1024) void t_sample_big(const T *__restrict__ X, in
             }
             l = s0 + smaller; h = l + equal; p = l + before;
         }
-        if constexpr (std::is_same<T, double>::value) {  // the band is wider than the equal values: two more rank queries
+        if constexpr (kBanded<T>) {  // the band is wider than the equal values: two more rank queries
             if (!isinf(x)) {   // (an infinity's code is its own: l = p, h = p + 1 from the scan above -- tied with nothing, :72)
                 l = rank_of(band_edge_code<false>(x, k), false);
                 h = rank_of(band_edge_code<true>(x, k), true);
@@ -1711,10 +1753,78 @@ struct ChunkUploader {
         hipEvent_t ev = c->ev_up[nraw++ % 8];
         REO_HIP_CHECK(hipEventRecord(ev, c->up));
         *ready = ev;
-        c->narrowed_bytes += static_cast<int64_t>(nc) * G * 8;
+        c->narrowed_bytes += static_cast<int64_t>(nc) * G * sizeof(T);
         return REO_OK;
     }
 };
+
+// a column-major matrix with a leading dimension (a device-resident Int32 matrix) into a dense wider one
+template <class N, class W>
+__global__ __launch_bounds__(256) void t_widen_cols(const N *__restrict__ src, int64_t ld, int64_t G, W *__restrict__ dst, size_t n)
+{
+    const size_t base = static_cast<size_t>(blockIdx.x) * 2048 + threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const size_t i = base + static_cast<size_t>(k) * 256;
+        if (i < n) { const size_t col = i / static_cast<size_t>(G), row = i - col * static_cast<size_t>(G); dst[i] = static_cast<W>(src[col * static_cast<size_t>(ld) + row]); }
+    }
+}
+
+// Host matrices of 32-bit elements (reo_set_matrix_f32 / _i32) are already what a narrowed chunk is on the link: they cross it as they
+// are, straight from the caller's (pageable) array -- no host threads, no pinned copy.  Float32 chunks land in their place in the resident
+// Float32 matrix; Int32 chunks land in the device half of a staging slot and t_widen writes them into the Int64 matrix (the form a
+// narrowed Int64 chunk takes).  Same interface as ChunkUploader.
+template <class H, class T>
+struct Uploader32 {
+    static constexpr bool kWiden = !std::is_same<H, T>::value;
+    reo_ctx *c;
+    const H *hX;
+    int64_t hld, G;
+    T *dX;
+    int nslot = 0, nraw = 0;
+
+    int32_t init(reo_ctx *ctx, const H *host, int64_t ld, int64_t genes, T *dev, int max_cols)
+    {
+        c = ctx; hX = host; hld = ld; G = genes; dX = dev;
+        int32_t rc;
+        if ((rc = ensure_upload_streams(c))) return rc;
+        c->narrowed_bytes = 0;
+        if (kWiden) {
+            for (int q = 0; q < 3; ++q) {
+                if ((rc = c->stage_d[q].ensure(static_cast<size_t>(max_cols) * G * sizeof(H)))) return rc;
+                if (!c->ev_widen[q]) REO_HIP_CHECK(handle_event(&c->ev_widen[q], 0));
+            }
+        }
+        return REO_OK;
+    }
+
+    int32_t send(int c0, int nc, hipEvent_t *ready)
+    {
+        const size_t nel = static_cast<size_t>(nc) * G;
+        const int sl = nslot % 3;
+        // (a slot's device half is free when its widening is done: the next copy into it follows on the same stream)
+        H *land = kWiden ? reinterpret_cast<H *>(c->stage_d[sl].p) : reinterpret_cast<H *>(dX + static_cast<size_t>(c0) * G);
+        const H *src = hX + static_cast<size_t>(c0) * hld;
+        if (hld == G) REO_HIP_CHECK(hipMemcpyAsync(land, src, nel * sizeof(H), hipMemcpyHostToDevice, c->up));
+        else REO_HIP_CHECK(hipMemcpy2DAsync(land, G * sizeof(H), src, hld * sizeof(H), G * sizeof(H), nc, hipMemcpyHostToDevice, c->up));
+        hipEvent_t ev;
+        if constexpr (kWiden) {
+            t_widen<H, T><<<static_cast<unsigned>((nel + 2047) / 2048), 256, 0, c->up>>>(land, dX + static_cast<size_t>(c0) * G, nel);
+            REO_HIP_CHECK(hipGetLastError());
+            ev = c->ev_widen[sl];
+            ++nslot;
+        } else {
+            ev = c->ev_up[nraw++ % 8];
+        }
+        REO_HIP_CHECK(hipEventRecord(ev, c->up));
+        *ready = ev;
+        c->narrowed_bytes += static_cast<int64_t>(nel * sizeof(H));
+        return REO_OK;
+    }
+};
+
+template <class H, class T>
+using UploaderFor = std::conditional_t<sizeof(H) == 4, Uploader32<H, T>, ChunkUploader<T>>;
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Pipelined upload (round 5): reo_set_matrix_i64 / _f64 from HOST memory when groups (and thresholds) are already known.
@@ -1729,8 +1839,8 @@ struct ChunkUploader {
 //     second side's pair kernel possibly still running (like reo_build_pairs on one GPU); reo_build_pairs then has nothing to do.
 // Anything the in-LDS ranking cannot take (a flagged sample: another form is needed) falls back to run_transform on the
 // resident copy at reo_build_pairs -- same results, no overlap.
-template <class T>
-int32_t eager_upload_impl(reo_ctx *c, const T *hX, int64_t hld, bool with_k1)
+template <class T, class H = T>   // T: the resident matrix's element type; H: the host array's (Int32 host data is resident as Int64)
+int32_t eager_upload_impl(reo_ctx *c, const H *hX, int64_t hld, bool with_k1)
 {
     const auto w_begin = std::chrono::steady_clock::now();
     auto stamp = [&](const char *what) {   // REO_DEBUG_PASSES: where the host is, microseconds since the call began
@@ -1852,7 +1962,7 @@ int32_t eager_upload_impl(reo_ctx *c, const T *hX, int64_t hld, bool with_k1)
         if (fl[4] || fl[5]) fallback = true;
         return REO_OK;
     };
-    ChunkUploader<T> upl;
+    UploaderFor<H, T> upl;
     if ((rc = upl.init(c, hX, hld, G, dX, std::min(CH, S)))) return rc;
     stamp("buffers, streams, lists ready");
     for (int c0 = 0; c0 < S;) {
@@ -1985,13 +2095,14 @@ int32_t ensure_staging(reo_ctx *c, size_t slot_bytes)
 
 // A whole host matrix (G x ncols, leading dimension hld) into a device matrix of leading dimension G, in chunks on the upload stream
 // (Int64 narrowed: ChunkUploader); the context's stream is ordered behind the last chunk, and the call returns when the host array has
-// been read.  dtype: 1 Float64, 2 Int64.
+// been read.  dtype: 1 Float64, 2 Int64, 3 Float32, 4 Int32 on the host into an Int64 device matrix.
 int32_t upload_columns(reo_ctx *c, const void *hX, int64_t hld, int64_t G, int64_t ncols, void *dX, int dtype)
 {
     auto go = [&](auto *host, auto *dev) -> int32_t {
         using T = std::remove_pointer_t<decltype(dev)>;
+        using H = std::remove_const_t<std::remove_pointer_t<decltype(host)>>;
         const int CH = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(ncols, std::max<int64_t>(16, (int64_t(32) << 20) / (G * 8)))));   // about 32 MB of source per chunk
-        ChunkUploader<T> upl;
+        UploaderFor<H, T> upl;
         int32_t rc = upl.init(c, host, hld, G, dev, CH);
         if (rc) return rc;
         hipEvent_t last = nullptr;
@@ -2001,19 +2112,40 @@ int32_t upload_columns(reo_ctx *c, const void *hX, int64_t hld, int64_t G, int64
         REO_HIP_CHECK(hipStreamSynchronize(c->up));
         return REO_OK;
     };
-    return dtype == 1 ? go(static_cast<const double *>(hX), static_cast<double *>(dX)) : go(static_cast<const int64_t *>(hX), static_cast<int64_t *>(dX));
+    switch (dtype) {
+    case 1: return go(static_cast<const double *>(hX), static_cast<double *>(dX));
+    case 3: return go(static_cast<const float *>(hX), static_cast<float *>(dX));
+    case 4: return go(static_cast<const int32_t *>(hX), static_cast<int64_t *>(dX));
+    default: return go(static_cast<const int64_t *>(hX), static_cast<int64_t *>(dX));
+    }
 }
 
-int32_t eager_upload(reo_ctx *c, const void *hX, int64_t hld, bool with_k1)
+// a device-resident Int32 matrix into the context's own Int64 matrix (ld = G), on the context's stream
+int32_t widen_device_i32(reo_ctx *c, const void *dX32, int64_t ld, int64_t G, int64_t S, void *dX64)
 {
-    return c->dtype == 1 ? eager_upload_impl<double>(c, static_cast<const double *>(hX), hld, with_k1)
-                         : eager_upload_impl<int64_t>(c, static_cast<const int64_t *>(hX), hld, with_k1);
+    const size_t n = static_cast<size_t>(G) * static_cast<size_t>(S);
+    t_widen_cols<int32_t, int64_t><<<static_cast<unsigned>((n + 2047) / 2048), 256, 0, c->stream>>>(static_cast<const int32_t *>(dX32), ld, G, static_cast<int64_t *>(dX64), n);
+    REO_HIP_CHECK(hipGetLastError());
+    return REO_OK;
+}
+
+int32_t eager_upload(reo_ctx *c, const void *hX, int64_t hld, bool with_k1, bool host_i32)
+{
+    if (c->dtype == 1) return eager_upload_impl<double>(c, static_cast<const double *>(hX), hld, with_k1);
+    if (c->dtype == 3) return eager_upload_impl<float>(c, static_cast<const float *>(hX), hld, with_k1);
+    if (host_i32) return eager_upload_impl<int64_t, int32_t>(c, static_cast<const int32_t *>(hX), hld, with_k1);
+    return eager_upload_impl<int64_t>(c, static_cast<const int64_t *>(hX), hld, with_k1);
 }
 
 int32_t run_transform(reo_ctx *c)
 {
     tic(c, 0);
-    int32_t rc = c->dtype == 1 ? transform_impl<double>(c) : transform_impl<int64_t>(c);
+    const char *env = getenv("REO_TRANSFORM");
+    if (c->dtype == 3 && env && env[0] == 's') {
+        set_error("REO_TRANSFORM=segmented: the segmented sort of the A/B build takes Float64 and Int64 matrices only, not Float32");
+        return REO_EINVAL;
+    }
+    int32_t rc = c->dtype == 1 ? transform_impl<double>(c) : c->dtype == 3 ? transform_impl<float>(c) : transform_impl<int64_t>(c);
     toc(c);
     return rc;
 }

@@ -74,10 +74,15 @@ class DegRun:
 
 def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref_gene, n_iter, n_conv, *,
                       seed: int = 0, device: int = -1, shard=(0, 1), allreduce=None, allgather=None, profile: bool = False) -> DegRun:
-    """identify_degs with the extras (trace, timings) kept.  Two groups: one comparison, group 1 vs
+    """identify_degs with the extras (trace, timings) kept.  `data` is a host matrix (numpy, anything np.asarray takes) or a torch
+    tensor on a ROCm device, which is used in place (_ffi.device_matrix).  Two groups: one comparison, group 1 vs
     group 2 (the reference's `gnum == 2` path, :387-389,431-434).  More groups: one comparison per
     group, that group vs every other sample (:375-390,396-436), 16 more columns each."""
-    data = np.asarray(data)
+    on_device = _ffi.is_device_tensor(data)   # a torch tensor on a ROCm device: used where it is (its device is the context's)
+    if on_device:
+        device = data.device.index if data.device.index is not None else -1
+    else:
+        data = np.asarray(data)
     if data.ndim != 2:
         raise _ffi.DimensionMismatch(_ffi.REO_EINVAL, "'data' must be a genes x samples matrix")
     r, c = data.shape
@@ -102,7 +107,10 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
                 ctx.set_allgather(allgather)   # all-gather of the shards' own table words (what the in-library RCCL path does)
             else:
                 ctx.set_allreduce(allreduce)   # in-place sum of the whole table
-        ctx.set_matrix(data)
+        if on_device:
+            ctx.set_matrix_tensor(data)   # (the context keeps the tensor alive until it is closed, behind the last build_pairs)
+        else:
+            ctx.set_matrix(data)
         for k in range(ncomp):  # `for k=1:gnum ... if gnum==2 break` (:396,431-434)
             ctx.build_pairs(k)
             result, iters, trace = ctx.identify_degs(np.asarray(ref_gene, dtype=bool), pval_deg, padj_deg, n_iter, n_conv)
