@@ -161,7 +161,17 @@ int32_t reo_set_allgather(reo_ctx *ctx, reo_allgather_fn fn, void *user);
  * is ranked from a resident Float32 copy (4 bytes per value on the link and in HBM); no Float64 copy is made.  Int32 has Int64's rule
  * (a tie is equality): _i32 sends the 4-byte values over the link and widens them on the device into the context's own Int64 matrix,
  * _dev_i32 widens once on the context's stream (the caller's buffer has been read when it returns); results are bit-identical to
- * _i64 on the same values.  REO_TRANSFORM=segmented (the A/B build) is refused for these two types. */
+ * _i64 on the same values.  REO_TRANSFORM=segmented (the A/B build) is refused for these two types.
+ * LAYOUT.  reo_set_matrix_rm_f64 / _i64 / _f32 / _i32 take the same matrix ROW-MAJOR from host memory (pageable is fine): the value of
+ * gene g in sample s is X[g * ld + s], ld >= S (REO_EINVAL otherwise) -- a C-ordered numpy array, a genes x cells HDF5 dataset, a
+ * column slice of a wider one.  The array is read IN PLACE, no transposed host copy is made: a chunk of sample columns is G row
+ * segments, which the host threads narrow (or pack) into a staging slot as they are, and the transposition into the context's own
+ * column-major matrix is fused with the widening kernel on the device.  Limits, ownership (all of it has been read on return, no host
+ * pointer is kept), the NaN refusal, the +-Inf rule, the element-type rules and both upload paths (pipelined with the groups set first,
+ * plain otherwise) are those of the column-major entries, and every result is BIT-IDENTICAL to reo_set_matrix_* on the transposed copy,
+ * in every order of calls; chunk by chunk the link carries the same bytes (reo_get_info 19).  REO_ROWMAJOR_COPY=2d in the environment
+ * sends chunks that are not narrowed as one 2-D copy from the caller's array instead of packing them through pinned memory (A/B;
+ * REO_UPLOAD_THREADS=0 always does).  reo_get_info 21 says which layout the last host matrix had. */
 int32_t reo_set_matrix_f64(reo_ctx *ctx, const double *X, int64_t G, int64_t S, int64_t ld);
 int32_t reo_set_matrix_i64(reo_ctx *ctx, const int64_t *X, int64_t G, int64_t S, int64_t ld);
 int32_t reo_set_matrix_dev_f64(reo_ctx *ctx, const void *dX, int64_t G, int64_t S, int64_t ld);
@@ -170,6 +180,10 @@ int32_t reo_set_matrix_f32(reo_ctx *ctx, const float *X, int64_t G, int64_t S, i
 int32_t reo_set_matrix_i32(reo_ctx *ctx, const int32_t *X, int64_t G, int64_t S, int64_t ld);
 int32_t reo_set_matrix_dev_f32(reo_ctx *ctx, const void *dX, int64_t G, int64_t S, int64_t ld);
 int32_t reo_set_matrix_dev_i32(reo_ctx *ctx, const void *dX, int64_t G, int64_t S, int64_t ld);
+int32_t reo_set_matrix_rm_f64(reo_ctx *ctx, const double *X, int64_t G, int64_t S, int64_t ld);
+int32_t reo_set_matrix_rm_i64(reo_ctx *ctx, const int64_t *X, int64_t G, int64_t S, int64_t ld);
+int32_t reo_set_matrix_rm_f32(reo_ctx *ctx, const float *X, int64_t G, int64_t S, int64_t ld);
+int32_t reo_set_matrix_rm_i32(reo_ctx *ctx, const int32_t *X, int64_t G, int64_t S, int64_t ld);
 
 /* Group of each sample: the `group` argument (src/RankCompV3.jl:341) recoded
  * to 0-based ids in order of first appearance (unique(), :353).  Length must
@@ -291,7 +305,8 @@ int32_t reo_get_timings(reo_ctx *ctx, double *ms, int32_t n);
  * array as it is, 4 bytes per value, no host threads), 20 the launches of the pair kernel that
  * the last pipelined reo_set_matrix_* made over a RANGE of a group's sample blocks (the pair kernel then starts before the whole group
  * has arrived; the counts of a range wait in HBM for the group's last range, which classifies -- REO_EAGER_RANGES=1 in the environment
- * launches whole sides only, as in round 5; 2..6 asks for that many ranges per side; default: by the number of blocks). */
+ * launches whole sides only, as in round 5; 2..6 asks for that many ranges per side; default: by the number of blocks), 21 the last
+ * host matrix was read row-major in place (reo_set_matrix_rm_*: 1; every other reo_set_matrix_*: 0). */
 int32_t reo_get_info(reo_ctx *ctx, int64_t *info, int32_t n);
 
 #ifdef __cplusplus

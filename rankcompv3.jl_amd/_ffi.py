@@ -24,6 +24,7 @@ SYMBOLS = [
     "reo_create_multi", "reo_comm_unique_id", "reo_comm_init_rank",
     "reo_set_matrix_f64", "reo_set_matrix_i64", "reo_set_matrix_dev_f64", "reo_set_matrix_dev_i64",
     "reo_set_matrix_f32", "reo_set_matrix_i32", "reo_set_matrix_dev_f32", "reo_set_matrix_dev_i32",
+    "reo_set_matrix_rm_f64", "reo_set_matrix_rm_i64", "reo_set_matrix_rm_f32", "reo_set_matrix_rm_i32",
     "reo_set_groups", "reo_compute_thresholds", "reo_set_thresholds", "reo_get_thresholds", "reo_threshold",
     "reo_build_pairs", "reo_pair_counts", "reo_get_codes", "reo_tally", "reo_identify_degs", "reo_mccullagh",
     "reo_set_profiling", "reo_reset_timings", "reo_get_timings", "reo_get_info",
@@ -97,6 +98,10 @@ def lib() -> ctypes.CDLL:
         "reo_set_matrix_i32": (i32, [vp, vp, i64, i64, i64]),
         "reo_set_matrix_dev_f32": (i32, [vp, vp, i64, i64, i64]),
         "reo_set_matrix_dev_i32": (i32, [vp, vp, i64, i64, i64]),
+        "reo_set_matrix_rm_f64": (i32, [vp, vp, i64, i64, i64]),
+        "reo_set_matrix_rm_i64": (i32, [vp, vp, i64, i64, i64]),
+        "reo_set_matrix_rm_f32": (i32, [vp, vp, i64, i64, i64]),
+        "reo_set_matrix_rm_i32": (i32, [vp, vp, i64, i64, i64]),
         "reo_set_groups": (i32, [vp, vp, i64, i32]),
         "reo_compute_thresholds": (i32, [vp, f64]),
         "reo_set_thresholds": (i32, [vp, vp]),
@@ -178,6 +183,36 @@ def matrix_entry(X):
     return "reo_set_matrix_" + _NATIVE[want], Xf, ld
 
 
+def host_matrix_entry(X):
+    """(symbol name, array, ld) for a host expression matrix in EITHER layout: matrix_entry's answer for a column-major array, and for a
+    row-major one -- numpy's default -- a reo_set_matrix_rm_* symbol, the array ITSELF and its row pitch in elements: a 2-D array of
+    Float64 / Int64 / Float32 / Int32 with strides (ld * itemsize, itemsize), ld >= S (C-contiguous, or a column slice of a wider
+    C-ordered array) is read in place, without the transposing host copy of np.asfortranarray; the library transposes on the device.
+    Column-major wins where both descriptions hold.  A C-contiguous array of another dtype is cast in C order (the casts of matrix_entry)
+    and routed row-major; every other stride pattern goes through matrix_entry.  The route is OPT-IN until tools/rowmajor_ab.py has been
+    run on the GPU host: REO_ROWMAJOR=1 in the environment (read per call) takes it; unset or 0, everything goes
+    through matrix_entry as before.  Pure: no library, no GPU."""
+    if os.environ.get("REO_ROWMAJOR", "0") != "1":
+        return matrix_entry(X)
+    X = np.asarray(X)
+    if X.ndim != 2:
+        raise DimensionMismatch(REO_EINVAL, "expression matrix must be 2-D (genes x samples)")
+    G, S = X.shape
+    if G < 1 or S < 2:
+        return matrix_entry(X)
+    if X.dtype in _NATIVE:
+        sz = X.dtype.itemsize
+        if X.strides[0] == sz and X.strides[1] % sz == 0 and X.strides[1] >= sz * G:
+            return matrix_entry(X)   # column-major as it is
+        if X.strides[1] == sz and X.strides[0] % sz == 0 and X.strides[0] >= sz * S:
+            return "reo_set_matrix_rm_" + _NATIVE[X.dtype], X, X.strides[0] // sz
+        return matrix_entry(X)
+    if X.flags.c_contiguous and not X.flags.f_contiguous:
+        want = np.dtype(np.int64) if (np.issubdtype(X.dtype, np.integer) or X.dtype == np.bool_) else np.dtype(np.float64)
+        return "reo_set_matrix_rm_" + _NATIVE[want], np.ascontiguousarray(X, dtype=want), S
+    return matrix_entry(X)
+
+
 UNIQUE_ID_BYTES = 128
 
 
@@ -247,8 +282,9 @@ class Context:
     # -- problem definition -------------------------------------------------
     def set_matrix(self, X: np.ndarray) -> None:
         """X is genes x samples (host); Float64, Float32, Int64 or Int32 as it is, any other integer dtype -> Int64, any other float
-        dtype -> Float64 (matrix_entry), like Matrix(df_expr)."""
-        name, Xf, ld = matrix_entry(X)
+        dtype -> Float64, like Matrix(df_expr).  A column-major array is read in place; a row-major (C-ordered) one is copied
+        column-major on the host first, or with REO_ROWMAJOR=1 read in place too (host_matrix_entry)."""
+        name, Xf, ld = host_matrix_entry(X)
         G, S = Xf.shape
         check(getattr(self._L, name)(self._h, _ptr(Xf), G, S, ld))
         self.G, self.S = G, S
@@ -420,11 +456,11 @@ class Context:
                 "k2_full_launches": int(ms[9]), "k2_delta_ms": ms[10], "set_matrix_host_wall_ms": ms[11]}
 
     def info(self) -> dict:
-        v = np.zeros(21, dtype=np.int64)
-        check(self._L.reo_get_info(self._h, _ptr(v), 21))
+        v = np.zeros(22, dtype=np.int64)
+        check(self._L.reo_get_info(self._h, _ptr(v), 22))
         return {"G": int(v[0]), "S": int(v[1]), "Gp": int(v[2]), "table_bytes": int(v[3]), "has_ties": int(v[4]),
                 "tiles_owned": int(v[5]), "tiles_total": int(v[6]), "tile_i": int(v[7]), "chunk_j": int(v[8]),
                 "chunks_per_panel": int(v[9]), "unit_h": int(v[10]), "sample_slots": int(v[11]),
                 "shared_group_counts": int(v[12]), "group_count_bytes": int(v[13]), "transform_in_lds": int(v[14]), "xcc_local_histograms": int(v[15]),
                 "cycle_period": int(v[16]), "cycle_found_at_pass": int(v[17]), "cycle_passes_skipped": int(v[18]), "upload_link_bytes": int(v[19]),
-                "eager_range_launches": int(v[20])}
+                "eager_range_launches": int(v[20]), "rowmajor_upload": int(v[21])}

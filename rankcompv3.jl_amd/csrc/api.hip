@@ -354,7 +354,8 @@ static void invalidate(reo_ctx *c)
 // dtype: what the caller hands over -- 1 Float64, 2 Int64, 3 Float32, 4 Int32 (which becomes a resident Int64 matrix: its tie is equality)
 static size_t elem_bytes(int dtype) { return dtype >= 3 ? 4 : 8; }
 
-static int32_t set_matrix(reo_ctx *c, const void *X, int64_t G, int64_t S, int64_t ld, int dtype, bool on_device)
+// rowmajor (host matrices only): X[g * ld + s], ld >= S; the resident matrix is the same column-major one either way
+static int32_t set_matrix(reo_ctx *c, const void *X, int64_t G, int64_t S, int64_t ld, int dtype, bool on_device, bool rowmajor = false)
 {
     int32_t rc = use(c);
     if (rc) return rc;
@@ -367,8 +368,10 @@ static int32_t set_matrix(reo_ctx *c, const void *X, int64_t G, int64_t S, int64
         set_error("matrix is %lld x %lld; G must be in [2, %d] and S in [2, 1048576]", (long long)G, (long long)S, kMaxGenes);
         return REO_EINVAL;
     }
-    if (ld < G) { set_error("leading dimension %lld < G = %lld", (long long)ld, (long long)G); return REO_EINVAL; }
+    if (rowmajor && ld < S) { set_error("row pitch %lld < S = %lld (row-major: ld counts the elements from one gene's row to the next)", (long long)ld, (long long)S); return REO_EINVAL; }
+    if (!rowmajor && ld < G) { set_error("leading dimension %lld < G = %lld", (long long)ld, (long long)G); return REO_EINVAL; }
     invalidate(c);
+    c->rowmajor_upload = 0;
     const bool host_i32 = dtype == 4 && !on_device;
     const size_t resident = static_cast<size_t>(G) * S * (dtype == 3 ? 4 : 8);   // bytes of the matrix the kernels read
     c->G = G; c->S = S; c->dtype = dtype == 4 ? 2 : dtype;
@@ -399,8 +402,9 @@ static int32_t set_matrix(reo_ctx *c, const void *X, int64_t G, int64_t S, int64
                 ~DrainUp() { if (c->up) (void)hipStreamSynchronize(c->up); if (c->rk) (void)hipStreamSynchronize(c->rk); }
             } drain_up{c};
             DrainOnExit drain(c);
-            rc = eager_upload(c, X, ld, k1, host_i32);
+            rc = eager_upload(c, X, ld, k1, host_i32, rowmajor);
             if (rc) { invalidate(c); return rc; }
+            c->rowmajor_upload = rowmajor ? 1 : 0;
             drain.dismiss();   // (the pair kernel may still be running, as after reo_build_pairs on one GPU: it reads device memory only)
             c->t_ms[11] += (wall_us() - w0) * 1e-3;
             if (c->eager_k1) { c->built_k = 0; c->table_complete = true; }
@@ -413,7 +417,8 @@ static int32_t set_matrix(reo_ctx *c, const void *X, int64_t G, int64_t S, int64
         } drain_up{c};
         DrainOnExit drain(c);
         const double w0 = wall_us();
-        if ((rc = upload_columns(c, X, ld, G, S, c->dX_owned.p, dtype))) { invalidate(c); return rc; }
+        if ((rc = upload_columns(c, X, ld, G, S, c->dX_owned.p, dtype, rowmajor))) { invalidate(c); return rc; }
+        c->rowmajor_upload = rowmajor ? 1 : 0;
         drain.dismiss();   // (upload_columns has waited for the upload stream: the caller's array has been read)
         c->t_ms[11] += (wall_us() - w0) * 1e-3;
     }
@@ -561,7 +566,7 @@ using namespace reo;
 
 extern "C" {
 
-int32_t reo_version(void) { return 200; }
+int32_t reo_version(void) { return 300; }
 
 int32_t reo_trim_memory(void)
 {
@@ -745,12 +750,12 @@ int32_t reo_set_allgather(reo_ctx *c, reo_allgather_fn fn, void *user)
 
 // multi-GPU context: every device gets its own copy of the matrix (host source: one upload each; device source:
 // a peer copy from the leader's buffer)
-static int32_t set_matrix_all(reo_ctx *c, const void *X, int64_t G, int64_t S, int64_t ld, int dtype, bool on_device)
+static int32_t set_matrix_all(reo_ctx *c, const void *X, int64_t G, int64_t S, int64_t ld, int dtype, bool on_device, bool rowmajor = false)
 {
-    int32_t rc = set_matrix(c, X, G, S, ld, dtype, on_device);
+    int32_t rc = set_matrix(c, X, G, S, ld, dtype, on_device, rowmajor);
     for (size_t d = 0; d < (c ? c->peers.size() : 0) && !rc; ++d) {
         reo_ctx *p = c->peers[d];
-        if (!on_device) { rc = set_matrix(p, X, G, S, ld, dtype, false); continue; }
+        if (!on_device) { rc = set_matrix(p, X, G, S, ld, dtype, false, rowmajor); continue; }
         // (an Int32 device matrix: the leader has widened it into its own Int64 matrix, which is what the peers copy)
         const void *src = dtype == 4 ? c->dX : X;
         const int64_t sld = dtype == 4 ? G : ld;
@@ -776,6 +781,10 @@ int32_t reo_set_matrix_f32(reo_ctx *c, const float *X, int64_t G, int64_t S, int
 int32_t reo_set_matrix_i32(reo_ctx *c, const int32_t *X, int64_t G, int64_t S, int64_t ld) { return set_matrix_all(c, X, G, S, ld, 4, false); }
 int32_t reo_set_matrix_dev_f32(reo_ctx *c, const void *dX, int64_t G, int64_t S, int64_t ld) { return set_matrix_all(c, dX, G, S, ld, 3, true); }
 int32_t reo_set_matrix_dev_i32(reo_ctx *c, const void *dX, int64_t G, int64_t S, int64_t ld) { return set_matrix_all(c, dX, G, S, ld, 4, true); }
+int32_t reo_set_matrix_rm_f64(reo_ctx *c, const double *X, int64_t G, int64_t S, int64_t ld) { return set_matrix_all(c, X, G, S, ld, 1, false, true); }
+int32_t reo_set_matrix_rm_i64(reo_ctx *c, const int64_t *X, int64_t G, int64_t S, int64_t ld) { return set_matrix_all(c, X, G, S, ld, 2, false, true); }
+int32_t reo_set_matrix_rm_f32(reo_ctx *c, const float *X, int64_t G, int64_t S, int64_t ld) { return set_matrix_all(c, X, G, S, ld, 3, false, true); }
+int32_t reo_set_matrix_rm_i32(reo_ctx *c, const int32_t *X, int64_t G, int64_t S, int64_t ld) { return set_matrix_all(c, X, G, S, ld, 4, false, true); }
 
 int32_t reo_set_groups(reo_ctx *c, const int32_t *group_id, int64_t len, int32_t ngroups)
 {
@@ -1230,12 +1239,12 @@ int32_t reo_get_timings(reo_ctx *c, double *ms, int32_t n)
 int32_t reo_get_info(reo_ctx *c, int64_t *info, int32_t n)
 {
     if (!c || !info) { set_error("null argument"); return REO_EINVAL; }
-    const int64_t v[21] = {c->G, c->S, c->Gp, static_cast<int64_t>(c->table.n * sizeof(uint32_t)), c->has_ties,
+    const int64_t v[22] = {c->G, c->S, c->Gp, static_cast<int64_t>(c->table.n * sizeof(uint32_t)), c->has_ties,
                            c->tiles_owned, c->tiles_total, kTileI, c->k1_cj, c->k1_q, kUnitH,
                            c->goff32.empty() ? 0 : c->goff32.back(), c->last_k1_shared,
                            static_cast<int64_t>(c->gcounts.n * sizeof(uint16_t)), c->transform_in_lds, c->xcc_local,
-                           c->it_cycle_period, c->it_cycle_at, c->it_cycle_skipped, c->narrowed_bytes, c->eager_range_launches};
-    for (int i = 0; i < n && i < 21; ++i) info[i] = v[i];
+                           c->it_cycle_period, c->it_cycle_at, c->it_cycle_skipped, c->narrowed_bytes, c->eager_range_launches, c->rowmajor_upload};
+    for (int i = 0; i < n && i < 22; ++i) info[i] = v[i];
     return REO_OK;
 }
 

@@ -40,6 +40,7 @@
 #include <type_traits>
 
 #include "reo_internal.h"
+#include "upload_rows.h"
 
 namespace reo {
 
@@ -1627,6 +1628,138 @@ __global__ __launch_bounds__(256) void t_widen(const N *__restrict__ src, W *__r
     }
 }
 
+// The same widening for a chunk that arrived ROW-MAJOR (reo_set_matrix_rm_*): src is the chunk's staging image [G][nc] of N, packed, and
+// dst the chunk's place in the resident column-major matrix (ld = G): dst[col * G + row] = (W)src[row * nc + col].  A 32 x 32 tile goes
+// through LDS, read along the sample axis (32 consecutive elements of a staging row per half wave) and written along the gene axis
+// (32 consecutive genes of a column, 128 or 256 contiguous bytes).  The tile holds 4- or 8-byte words, rows padded by one word: a half
+// wave that reads a tile column then meets banks (row + col) % 32 (ds_read_b32) or the even banks 2 (row + col) % 64 (ds_read_b64), all
+// distinct.  8.3 KB of LDS at most, so a workgroup of it fits on a CU beside nothing or anything and never keeps a ranking workgroup
+// (135 KB) waiting.  Element accesses only: a staging row of nc int16 numbers starts on a 2-byte boundary, nc and G are arbitrary.
+constexpr int kTrTile = 32;
+template <class N, class W>
+__global__ __launch_bounds__(256) void t_widen_transpose(const N *__restrict__ src, W *__restrict__ dst, int64_t G, int nc)
+{
+    using L = std::conditional_t<(sizeof(N) < 4), int32_t, N>;
+    __shared__ L tile[kTrTile][kTrTile + 1];
+    const int lane = threadIdx.x & 31, part = threadIdx.x >> 5;   // 8 parts of 32 lanes
+    const int64_t g0 = static_cast<int64_t>(blockIdx.y) * kTrTile;
+    const int s0 = static_cast<int>(blockIdx.x) * kTrTile;
+#pragma unroll
+    for (int k = 0; k < kTrTile / 8; ++k) {
+        const int row = part + 8 * k;
+        const int64_t g = g0 + row;
+        if (g < G && s0 + lane < nc) tile[row][lane] = static_cast<L>(src[g * static_cast<int64_t>(nc) + s0 + lane]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kTrTile / 8; ++k) {
+        const int col = part + 8 * k;
+        const int64_t g = g0 + lane;
+        if (g < G && s0 + col < nc) dst[static_cast<int64_t>(s0 + col) * G + g] = static_cast<W>(static_cast<N>(tile[lane][col]));   // (exact, as in t_widen)
+    }
+}
+
+template <class N, class W>
+static hipError_t launch_widen_transpose(const void *src, W *dst, int64_t G, int nc, hipStream_t st)
+{
+    const dim3 grid(static_cast<unsigned>((nc + kTrTile - 1) / kTrTile), static_cast<unsigned>((G + kTrTile - 1) / kTrTile));   // (G <= 262 143: 8 192 rows of tiles)
+    t_widen_transpose<N, W><<<grid, 256, 0, st>>>(static_cast<const N *>(src), dst, G, nc);
+    return hipGetLastError();
+}
+
+// how a row-major chunk that is not narrowed leaves the host (REO_ROWMAJOR_COPY, read per upload): "pack" -- the host threads copy
+// the row segments into the pinned slot, one 1-D copy follows -- or "2d" -- one hipMemcpy2DAsync of G rows from the caller's pageable
+// array.  REO_UPLOAD_THREADS=0 always takes the 2-D copy (no host thread touches the data).  Default: tools/rowmajor_ab.py, DESIGN.md 4.1.
+static bool rowmajor_pack_default()
+{
+    const char *e = getenv("REO_ROWMAJOR_COPY");
+    return !(e && e[0] == '2');
+}
+
+// REO_UPLOAD_TIMES=1 (tools/rowmajor_ab.py): HIP events in front of the copy, behind it and behind the transposition of every row-major
+// chunk; the uploader prints one line per chunk to stderr when it goes out of scope (the upload stream is idle by then).  Off: nothing.
+struct ChunkTimes {
+    struct Rec { int c0, nc, width; hipEvent_t e[3]; };
+    bool on = false;
+    std::vector<Rec> recs;
+    void init() { const char *e = getenv("REO_UPLOAD_TIMES"); on = e && e[0] == '1'; }
+    void mark(hipStream_t st, int k, int c0 = 0, int nc = 0, int width = 0)
+    {
+        if (!on) return;
+        if (k == 0) { recs.push_back(Rec{c0, nc, width, {nullptr, nullptr, nullptr}}); }
+        Rec &r = recs.back();
+        if (hipEventCreate(&r.e[k]) == hipSuccess) (void)hipEventRecord(r.e[k], st);
+    }
+    void report(hipStream_t st, int64_t G)
+    {
+        if (!on || recs.empty()) return;
+        (void)hipStreamSynchronize(st);
+        for (Rec &r : recs) {
+            if (!(r.e[0] && r.e[1] && r.e[2])) {   // send() returned with an error between the marks
+                fprintf(stderr, "  upload chunk: columns %d..%d: not timed, the chunk did not go out\n", r.c0, r.c0 + r.nc);
+                continue;
+            }
+            float copy_ms = 0.f, tr_ms = 0.f;
+            (void)hipEventElapsedTime(&copy_ms, r.e[0], r.e[1]); (void)hipEventElapsedTime(&tr_ms, r.e[1], r.e[2]);
+            fprintf(stderr, "  upload chunk: columns %d..%d, %d bytes per value, %.1f MB on the link: copy %.1f us, transposition %.1f us\n", r.c0, r.c0 + r.nc,
+                    r.width, static_cast<double>(G) * r.nc * r.width * 1e-6, copy_ms * 1e3, tr_ms * 1e3);
+        }
+        clear();
+    }
+    void clear()
+    {
+        for (Rec &r : recs) for (hipEvent_t e : r.e) if (e) (void)hipEventDestroy(e);
+        recs.clear();
+    }
+    ~ChunkTimes() { clear(); }
+};
+
+// the host threads an uploader uses, bound to the CPUs of the device's node
+static int upload_host_threads(reo_ctx *c)
+{
+    const int n = std::max(1, std::min<int>(c->upload_threads, static_cast<int>(std::thread::hardware_concurrency())));
+    cpu_set_t node;
+    if (device_node_cpus(c->device, &node)) HostPool::get(n).bind(node);
+    return n;
+}
+
+// One row-major chunk that crosses the link as it is (the RAW form, and every chunk of a 32-bit host matrix): the caller's rows into the
+// device half of staging slot nslot % 3 (free when the transposition that read it is done: the same stream), then t_widen_transpose
+// into place.  Off the host: packed by the host threads through the slot's pinned half (free behind ev_stage) and one 1-D copy, or one
+// 2-D copy of G row segments from the caller's pageable array; a chunk that is the whole of a dense matrix is one 1-D copy.
+template <class H, class W>
+static int32_t send_rows_as_they_are(reo_ctx *c, const H *hX, int64_t hld, int64_t G, int64_t ncols_all, W *dX, int c0, int nc, bool pack,
+                                     int nthreads, int *nslot, ChunkTimes &times, hipEvent_t *ready)
+{
+    const int sl = *nslot % 3;
+    const size_t nel = static_cast<size_t>(nc) * G;
+    H *land = reinterpret_cast<H *>(c->stage_d[sl].p);
+    times.mark(c->up, 0, c0, nc, static_cast<int>(sizeof(H)));
+    if (hld == nc && nc == ncols_all) {
+        REO_HIP_CHECK(hipMemcpyAsync(land, hX, nel * sizeof(H), hipMemcpyHostToDevice, c->up));
+    } else if (pack) {
+        if (*nslot >= 3) REO_HIP_CHECK(hipEventSynchronize(c->ev_stage[sl]));
+        H *hs = reinterpret_cast<H *>(c->stage_h[sl]);
+        const int64_t rper = (G + nthreads - 1) / nthreads;
+        HostPool::get(nthreads).run(nthreads, [&](int t) {
+            const int64_t a = std::min<int64_t>(G, t * rper), b = std::min<int64_t>(G, a + rper);
+            if (a < b) pack_rows(hX, hld, a, b, c0, nc, hs);
+        });
+        REO_HIP_CHECK(hipMemcpyAsync(land, hs, nel * sizeof(H), hipMemcpyHostToDevice, c->up));
+        REO_HIP_CHECK(hipEventRecord(c->ev_stage[sl], c->up));
+    } else {
+        REO_HIP_CHECK(hipMemcpy2DAsync(land, nc * sizeof(H), hX + c0, hld * sizeof(H), nc * sizeof(H), G, hipMemcpyHostToDevice, c->up));
+    }
+    times.mark(c->up, 1);
+    REO_HIP_CHECK((launch_widen_transpose<H, W>(land, dX + static_cast<size_t>(c0) * G, G, nc, c->up)));
+    times.mark(c->up, 2);
+    REO_HIP_CHECK(hipEventRecord(c->ev_widen[sl], c->up));
+    *ready = c->ev_widen[sl];
+    ++*nslot;
+    c->narrowed_bytes += static_cast<int64_t>(nel * sizeof(H));
+    return REO_OK;
+}
+
 // Float64 columns whose values are integers (counts read into a Float64 DataFrame) or float32 numbers (data that was stored in single
 // precision) cross the link as int16 / int32 / float32 too: the chunk is narrowed only if EVERY value converts back to the same
 // bits (so -0.0, NaN and anything with more mantissa than the narrow type keeps the chunk on the wider form).
@@ -1660,25 +1793,37 @@ static bool narrow_columns_f64(const double *src, int64_t ld, int64_t G, int col
 // in place.  Used by the pipelined reo_set_matrix (eager_upload), by the plain one and by the dense pseudo-bulk call (upload_columns).
 template <class T>
 struct ChunkUploader {
-    static constexpr int kStage = 3;
+    static constexpr int kStage = 3;   // (send_rows_as_they_are turns the same ring of 3)
     enum Form { I16 = 0, I32 = 1, F32 = 2, RAW = 3 };   // what a chunk is on the link; the form only moves up this ladder (F32: Float64 input only)
-    reo_ctx *c;
+    reo_ctx *c = nullptr;
     const T *hX;
     int64_t hld, G;
     T *dX;
     int form = RAW, nslot = 0, nthreads = 1, nraw = 0;
+    bool rm = false, pack = false;   // rm: the host matrix is row-major (hld = its pitch, >= the number of samples); pack: see rowmajor_pack_default
+    int64_t ncols_all = 0;           // rm: the samples of the whole matrix (a chunk that is all of a dense matrix is contiguous)
+    ChunkTimes times;
+    ~ChunkUploader() { if (times.on) times.report(c->up, G); }
 
-    int32_t init(reo_ctx *ctx, const T *host, int64_t ld, int64_t genes, T *dev, int max_cols)
+    int32_t init(reo_ctx *ctx, const T *host, int64_t ld, int64_t genes, T *dev, int max_cols, bool rowmajor = false, int64_t ncols = 0)
     {
-        c = ctx; hX = host; hld = ld; G = genes; dX = dev;
+        c = ctx; hX = host; hld = ld; G = genes; dX = dev; rm = rowmajor; ncols_all = ncols;
         int32_t rc;
         if ((rc = ensure_upload_streams(c))) return rc;
         c->narrowed_bytes = 0;
+        pack = rm && c->upload_threads > 0 && rowmajor_pack_default();
+        if (rm) times.init();
+        if (rm) {
+            // every chunk lands row-major in the device half of a slot, the RAW form too (8 bytes per element), and is put in place by
+            // t_widen_transpose; the pinned half is as large only if RAW chunks are packed through it
+            for (int q = 0; q < kStage; ++q) {
+                if ((rc = c->stage_d[q].ensure(static_cast<size_t>(max_cols) * G * sizeof(T)))) return rc;
+                if (!c->ev_widen[q]) REO_HIP_CHECK(handle_event(&c->ev_widen[q], 0));
+            }
+        }
         if (c->upload_threads > 0) {
-            if ((rc = ensure_staging(c, static_cast<size_t>(max_cols) * G * 4))) return rc;
-            nthreads = std::max(1, std::min<int>(c->upload_threads, static_cast<int>(std::thread::hardware_concurrency())));
-            cpu_set_t node;
-            if (device_node_cpus(c->device, &node)) HostPool::get(nthreads).bind(node);
+            if ((rc = ensure_staging(c, static_cast<size_t>(max_cols) * G * (pack ? sizeof(T) : 4)))) return rc;
+            nthreads = upload_host_threads(c);
             form = I16;
         }
         return REO_OK;
@@ -1695,12 +1840,14 @@ struct ChunkUploader {
                 unsigned char probe[256 * 4];
                 const int64_t np_ = std::min<int64_t>(G, 256);
                 bool ok;
+                T head[256];   // row-major: the same 256 values, gathered (the ladder does not depend on the layout)
+                if (rm) gather_column_head(hX, hld, c0, np_, head);
                 if constexpr (std::is_same<T, int64_t>::value) {
-                    const int64_t *src = hX + static_cast<int64_t>(c0) * hld;
+                    const int64_t *src = rm ? head : hX + static_cast<int64_t>(c0) * hld;
                     ok = form == I16 ? narrow_columns<int16_t>(src, hld, np_, 0, 1, reinterpret_cast<int16_t *>(probe))
                                      : narrow_columns<int32_t>(src, hld, np_, 0, 1, reinterpret_cast<int32_t *>(probe));
                 } else {
-                    const double *src = hX + static_cast<int64_t>(c0) * hld;
+                    const double *src = rm ? head : hX + static_cast<int64_t>(c0) * hld;
                     ok = form == I16 ? narrow_columns_f64<int16_t>(src, hld, np_, 0, 1, reinterpret_cast<int16_t *>(probe))
                        : form == I32 ? narrow_columns_f64<int32_t>(src, hld, np_, 0, 1, reinterpret_cast<int32_t *>(probe))
                                      : narrow_columns_f64<float>(src, hld, np_, 0, 1, reinterpret_cast<float *>(probe));
@@ -1713,6 +1860,23 @@ struct ChunkUploader {
             std::atomic<int> fits{1};
             const int per = (nc + nthreads - 1) / nthreads;
             const int f = form;
+            if (rm) {   // split by gene rows: every thread reads its rows' segments and writes one contiguous piece of the slot
+                const int64_t rper = (G + nthreads - 1) / nthreads;
+                HostPool::get(nthreads).run(nthreads, [&](int t) {
+                    const int64_t a = std::min<int64_t>(G, t * rper), b = std::min<int64_t>(G, a + rper);
+                    if (a >= b) return;
+                    bool ok;
+                    if constexpr (std::is_same<T, int64_t>::value) {
+                        ok = f == I16 ? narrow_rows<int16_t>(hX, hld, a, b, c0, nc, reinterpret_cast<int16_t *>(hs))
+                                      : narrow_rows<int32_t>(hX, hld, a, b, c0, nc, reinterpret_cast<int32_t *>(hs));
+                    } else {
+                        ok = f == I16 ? narrow_rows_f64<int16_t>(hX, hld, a, b, c0, nc, reinterpret_cast<int16_t *>(hs))
+                           : f == I32 ? narrow_rows_f64<int32_t>(hX, hld, a, b, c0, nc, reinterpret_cast<int32_t *>(hs))
+                                      : narrow_rows_f64<float>(hX, hld, a, b, c0, nc, reinterpret_cast<float *>(hs));
+                    }
+                    if (!ok) fits.store(0);
+                });
+            } else
             HostPool::get(nthreads).run(nthreads, [&](int t) {
                 const int a = std::min(nc, t * per), b = std::min(nc, a + per);
                 if (a >= b) return;
@@ -1732,21 +1896,30 @@ struct ChunkUploader {
             if (!fits.load()) { ++form; continue; }   // (this chunk again, one form up)
             const size_t nel = static_cast<size_t>(nc) * G, width = form == I16 ? 2 : 4;
             // copy and widening both on the upload stream: the staging ring turns whatever the other streams are waiting for
+            times.mark(c->up, 0, c0, nc, static_cast<int>(width));
             REO_HIP_CHECK(hipMemcpyAsync(c->stage_d[sl].p, hs, nel * width, hipMemcpyHostToDevice, c->up));
             REO_HIP_CHECK(hipEventRecord(c->ev_stage[sl], c->up));
+            times.mark(c->up, 1);
             T *dst = dX + static_cast<size_t>(c0) * G;
             const unsigned grid = static_cast<unsigned>((nel + 2047) / 2048);
             const unsigned char *ds = c->stage_d[sl].p;
+            if (rm) {   // the image is [G][nc]: widened and transposed into its columns
+                REO_HIP_CHECK((form == I16 ? launch_widen_transpose<int16_t, T>(ds, dst, G, nc, c->up)
+                             : form == I32 ? launch_widen_transpose<int32_t, T>(ds, dst, G, nc, c->up)
+                                           : launch_widen_transpose<float, T>(ds, dst, G, nc, c->up)));
+            } else
             if (form == I16) t_widen<int16_t, T><<<grid, 256, 0, c->up>>>(reinterpret_cast<const int16_t *>(ds), dst, nel);
             else if (form == I32) t_widen<int32_t, T><<<grid, 256, 0, c->up>>>(reinterpret_cast<const int32_t *>(ds), dst, nel);
             else t_widen<float, T><<<grid, 256, 0, c->up>>>(reinterpret_cast<const float *>(ds), dst, nel);
             REO_HIP_CHECK(hipGetLastError());
+            times.mark(c->up, 2);
             REO_HIP_CHECK(hipEventRecord(c->ev_widen[sl], c->up));
             *ready = c->ev_widen[sl];
             ++nslot;
             c->narrowed_bytes += static_cast<int64_t>(nel * width);
             return REO_OK;
         }
+        if (rm) return send_rows_as_they_are<T, T>(c, hX, hld, G, ncols_all, dX, c0, nc, pack, nthreads, &nslot, times, ready);
         // the caller's array as it is: pageable source, so the call returns when the runtime has staged the chunk
         if (hld == G) REO_HIP_CHECK(hipMemcpyAsync(dX + static_cast<size_t>(c0) * G, hX + static_cast<size_t>(c0) * hld, static_cast<size_t>(nc) * G * sizeof(T), hipMemcpyHostToDevice, c->up));
         else REO_HIP_CHECK(hipMemcpy2DAsync(dX + static_cast<size_t>(c0) * G, G * sizeof(T), hX + static_cast<size_t>(c0) * hld, hld * sizeof(T), G * sizeof(T), nc, hipMemcpyHostToDevice, c->up));
@@ -1777,19 +1950,29 @@ __global__ __launch_bounds__(256) void t_widen_cols(const N *__restrict__ src, i
 template <class H, class T>
 struct Uploader32 {
     static constexpr bool kWiden = !std::is_same<H, T>::value;
-    reo_ctx *c;
+    reo_ctx *c = nullptr;
     const H *hX;
     int64_t hld, G;
     T *dX;
-    int nslot = 0, nraw = 0;
+    int nslot = 0, nraw = 0, nthreads = 1;
+    bool rm = false, pack = false;   // as in ChunkUploader
+    int64_t ncols_all = 0;
+    ChunkTimes times;
+    ~Uploader32() { if (times.on) times.report(c->up, G); }
 
-    int32_t init(reo_ctx *ctx, const H *host, int64_t ld, int64_t genes, T *dev, int max_cols)
+    int32_t init(reo_ctx *ctx, const H *host, int64_t ld, int64_t genes, T *dev, int max_cols, bool rowmajor = false, int64_t ncols = 0)
     {
-        c = ctx; hX = host; hld = ld; G = genes; dX = dev;
+        c = ctx; hX = host; hld = ld; G = genes; dX = dev; rm = rowmajor; ncols_all = ncols;
         int32_t rc;
         if ((rc = ensure_upload_streams(c))) return rc;
         c->narrowed_bytes = 0;
-        if (kWiden) {
+        pack = rm && c->upload_threads > 0 && rowmajor_pack_default();
+        if (rm) times.init();
+        if (pack) {   // row segments packed by the host threads into a pinned slot (a column-major matrix needs none of this)
+            if ((rc = ensure_staging(c, static_cast<size_t>(max_cols) * G * sizeof(H)))) return rc;
+            nthreads = upload_host_threads(c);
+        }
+        if (kWiden || rm) {
             for (int q = 0; q < 3; ++q) {
                 if ((rc = c->stage_d[q].ensure(static_cast<size_t>(max_cols) * G * sizeof(H)))) return rc;
                 if (!c->ev_widen[q]) REO_HIP_CHECK(handle_event(&c->ev_widen[q], 0));
@@ -1802,6 +1985,9 @@ struct Uploader32 {
     {
         const size_t nel = static_cast<size_t>(nc) * G;
         const int sl = nslot % 3;
+        // row-major: the chunk cannot land in its place; it lands as [G][nc] in a staging slot and t_widen_transpose puts it into the
+        // resident matrix, Float32 as Float32, Int32 widened
+        if (rm) return send_rows_as_they_are<H, T>(c, hX, hld, G, ncols_all, dX, c0, nc, pack, nthreads, &nslot, times, ready);
         // (a slot's device half is free when its widening is done: the next copy into it follows on the same stream)
         H *land = kWiden ? reinterpret_cast<H *>(c->stage_d[sl].p) : reinterpret_cast<H *>(dX + static_cast<size_t>(c0) * G);
         const H *src = hX + static_cast<size_t>(c0) * hld;
@@ -1840,7 +2026,7 @@ using UploaderFor = std::conditional_t<sizeof(H) == 4, Uploader32<H, T>, ChunkUp
 // Anything the in-LDS ranking cannot take (a flagged sample: another form is needed) falls back to run_transform on the
 // resident copy at reo_build_pairs -- same results, no overlap.
 template <class T, class H = T>   // T: the resident matrix's element type; H: the host array's (Int32 host data is resident as Int64)
-int32_t eager_upload_impl(reo_ctx *c, const H *hX, int64_t hld, bool with_k1)
+int32_t eager_upload_impl(reo_ctx *c, const H *hX, int64_t hld, bool with_k1, bool rowmajor)
 {
     const auto w_begin = std::chrono::steady_clock::now();
     auto stamp = [&](const char *what) {   // REO_DEBUG_PASSES: where the host is, microseconds since the call began
@@ -1963,7 +2149,7 @@ int32_t eager_upload_impl(reo_ctx *c, const H *hX, int64_t hld, bool with_k1)
         return REO_OK;
     };
     UploaderFor<H, T> upl;
-    if ((rc = upl.init(c, hX, hld, G, dX, std::min(CH, S)))) return rc;
+    if ((rc = upl.init(c, hX, hld, G, dX, std::min(CH, S), rowmajor, S))) return rc;
     stamp("buffers, streams, lists ready");
     for (int c0 = 0; c0 < S;) {
         int nc = std::min(CH, S - c0);
@@ -2096,14 +2282,14 @@ int32_t ensure_staging(reo_ctx *c, size_t slot_bytes)
 // A whole host matrix (G x ncols, leading dimension hld) into a device matrix of leading dimension G, in chunks on the upload stream
 // (Int64 narrowed: ChunkUploader); the context's stream is ordered behind the last chunk, and the call returns when the host array has
 // been read.  dtype: 1 Float64, 2 Int64, 3 Float32, 4 Int32 on the host into an Int64 device matrix.
-int32_t upload_columns(reo_ctx *c, const void *hX, int64_t hld, int64_t G, int64_t ncols, void *dX, int dtype)
+int32_t upload_columns(reo_ctx *c, const void *hX, int64_t hld, int64_t G, int64_t ncols, void *dX, int dtype, bool rowmajor)
 {
     auto go = [&](auto *host, auto *dev) -> int32_t {
         using T = std::remove_pointer_t<decltype(dev)>;
         using H = std::remove_const_t<std::remove_pointer_t<decltype(host)>>;
         const int CH = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(ncols, std::max<int64_t>(16, (int64_t(32) << 20) / (G * 8)))));   // about 32 MB of source per chunk
         UploaderFor<H, T> upl;
-        int32_t rc = upl.init(c, host, hld, G, dev, CH);
+        int32_t rc = upl.init(c, host, hld, G, dev, CH, rowmajor, ncols);
         if (rc) return rc;
         hipEvent_t last = nullptr;
         for (int64_t c0 = 0; c0 < ncols; c0 += CH)
@@ -2129,12 +2315,12 @@ int32_t widen_device_i32(reo_ctx *c, const void *dX32, int64_t ld, int64_t G, in
     return REO_OK;
 }
 
-int32_t eager_upload(reo_ctx *c, const void *hX, int64_t hld, bool with_k1, bool host_i32)
+int32_t eager_upload(reo_ctx *c, const void *hX, int64_t hld, bool with_k1, bool host_i32, bool rowmajor)
 {
-    if (c->dtype == 1) return eager_upload_impl<double>(c, static_cast<const double *>(hX), hld, with_k1);
-    if (c->dtype == 3) return eager_upload_impl<float>(c, static_cast<const float *>(hX), hld, with_k1);
-    if (host_i32) return eager_upload_impl<int64_t, int32_t>(c, static_cast<const int32_t *>(hX), hld, with_k1);
-    return eager_upload_impl<int64_t>(c, static_cast<const int64_t *>(hX), hld, with_k1);
+    if (c->dtype == 1) return eager_upload_impl<double>(c, static_cast<const double *>(hX), hld, with_k1, rowmajor);
+    if (c->dtype == 3) return eager_upload_impl<float>(c, static_cast<const float *>(hX), hld, with_k1, rowmajor);
+    if (host_i32) return eager_upload_impl<int64_t, int32_t>(c, static_cast<const int32_t *>(hX), hld, with_k1, rowmajor);
+    return eager_upload_impl<int64_t>(c, static_cast<const int64_t *>(hX), hld, with_k1, rowmajor);
 }
 
 int32_t run_transform(reo_ctx *c)

@@ -75,7 +75,11 @@ class DegRun:
 def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref_gene, n_iter, n_conv, *,
                       seed: int = 0, device: int = -1, shard=(0, 1), allreduce=None, allgather=None, profile: bool = False) -> DegRun:
     """identify_degs with the extras (trace, timings) kept.  `data` is a host matrix (numpy, anything np.asarray takes) or a torch
-    tensor on a ROCm device, which is used in place (_ffi.device_matrix).  Two groups: one comparison, group 1 vs
+    tensor on a ROCm device, which is used in place (_ffi.device_matrix).  A column-major host matrix is read in place; a row-major one
+    (numpy's default C order, column slices of a wider C-ordered array) is copied column-major on the host first, or, with REO_ROWMAJOR=1
+    in the environment, read in place through reo_set_matrix_rm_* -- no transposing host copy, the library transposes on the device
+    (_ffi.host_matrix_entry; opt-in until its timing has been recorded).
+    Two groups: one comparison, group 1 vs
     group 2 (the reference's `gnum == 2` path, :387-389,431-434).  More groups: one comparison per
     group, that group vs every other sample (:375-390,396-436), 16 more columns each."""
     on_device = _ffi.is_device_tensor(data)   # a torch tensor on a ROCm device: used where it is (its device is the context's)
