@@ -171,7 +171,22 @@ int32_t reo_set_allgather(reo_ctx *ctx, reo_allgather_fn fn, void *user);
  * plain otherwise) are those of the column-major entries, and every result is BIT-IDENTICAL to reo_set_matrix_* on the transposed copy,
  * in every order of calls; chunk by chunk the link carries the same bytes (reo_get_info 19).  REO_ROWMAJOR_COPY=2d in the environment
  * sends chunks that are not narrowed as one 2-D copy from the caller's array instead of packing them through pinned memory (A/B;
- * REO_UPLOAD_THREADS=0 always does).  reo_get_info 21 says which layout the last host matrix had. */
+ * REO_UPLOAD_THREADS=0 always does).  reo_get_info 21 says which layout the last host matrix had.
+ *
+ * SPARSE.  reo_set_matrix_csc_f64 / _i64 / _f32 / _i32 take the same matrix from host memory in compressed sparse column form (single-cell
+ * counts are 90-95 % zeros; a scipy.sparse csc_matrix is this container as it is), arguments in the order of reo_pseudobulk_csc_*:
+ * colptr has S + 1 entries, colptr[0] = 0, non-decreasing, colptr[S] = nnz; rowidx and val have nnz entries, row indices 0-based and
+ * STRICTLY INCREASING inside a column (sorted, no duplicates).  A row index outside [0, G), an unsorted or repeated one and a colptr
+ * that is not such a pointer are REO_EINVAL (the context then holds no matrix until the next reo_set_matrix_*; it stays usable).
+ * Explicitly stored zeros are fine, a stored -0.0 stays -0.0, an absent entry is +0 of the element type; nnz = 0 is an all-zero matrix,
+ * and rowidx / val may then be null.  The zeros never exist on the host or on the link: a chunk of columns is the entry range
+ * colptr[c0] .. colptr[c0 + nc], which the host threads check and narrow -- row indices to 16 bits when G <= 65 536, Int64 and Float64
+ * values as the dense entries narrow theirs, Float32 / Int32 values as they are (REO_UPLOAD_THREADS=0: the calling thread checks, the
+ * arrays go as they are) -- and a kernel writes the chunk's columns of the context's own column-major matrix, each element once.
+ * Limits, ownership (everything has been read on return, no host pointer is kept), the NaN refusal, the +-Inf rule, the element-type
+ * rules and both upload paths are those of the dense entries, and every result is BIT-IDENTICAL to reo_set_matrix_<type> on the
+ * densified array, in every order of calls.  reo_get_info 19 counts what this upload sent (colptr included), 22 says that the last host
+ * matrix came as CSC, 23 its nnz. */
 int32_t reo_set_matrix_f64(reo_ctx *ctx, const double *X, int64_t G, int64_t S, int64_t ld);
 int32_t reo_set_matrix_i64(reo_ctx *ctx, const int64_t *X, int64_t G, int64_t S, int64_t ld);
 int32_t reo_set_matrix_dev_f64(reo_ctx *ctx, const void *dX, int64_t G, int64_t S, int64_t ld);
@@ -184,6 +199,10 @@ int32_t reo_set_matrix_rm_f64(reo_ctx *ctx, const double *X, int64_t G, int64_t 
 int32_t reo_set_matrix_rm_i64(reo_ctx *ctx, const int64_t *X, int64_t G, int64_t S, int64_t ld);
 int32_t reo_set_matrix_rm_f32(reo_ctx *ctx, const float *X, int64_t G, int64_t S, int64_t ld);
 int32_t reo_set_matrix_rm_i32(reo_ctx *ctx, const int32_t *X, int64_t G, int64_t S, int64_t ld);
+int32_t reo_set_matrix_csc_f64(reo_ctx *ctx, int64_t G, int64_t S, const int64_t *colptr, const int32_t *rowidx, const double *val);
+int32_t reo_set_matrix_csc_i64(reo_ctx *ctx, int64_t G, int64_t S, const int64_t *colptr, const int32_t *rowidx, const int64_t *val);
+int32_t reo_set_matrix_csc_f32(reo_ctx *ctx, int64_t G, int64_t S, const int64_t *colptr, const int32_t *rowidx, const float *val);
+int32_t reo_set_matrix_csc_i32(reo_ctx *ctx, int64_t G, int64_t S, const int64_t *colptr, const int32_t *rowidx, const int32_t *val);
 
 /* Group of each sample: the `group` argument (src/RankCompV3.jl:341) recoded
  * to 0-based ids in order of first appearance (unique(), :353).  Length must
@@ -306,7 +325,8 @@ int32_t reo_get_timings(reo_ctx *ctx, double *ms, int32_t n);
  * the last pipelined reo_set_matrix_* made over a RANGE of a group's sample blocks (the pair kernel then starts before the whole group
  * has arrived; the counts of a range wait in HBM for the group's last range, which classifies -- REO_EAGER_RANGES=1 in the environment
  * launches whole sides only, as in round 5; 2..6 asks for that many ranges per side; default: by the number of blocks), 21 the last
- * host matrix was read row-major in place (reo_set_matrix_rm_*: 1; every other reo_set_matrix_*: 0). */
+ * host matrix was read row-major in place (reo_set_matrix_rm_*: 1; every other reo_set_matrix_*: 0), 22 the last host matrix came as CSC
+ * (reo_set_matrix_csc_*: 1; every other reo_set_matrix_*: 0), 23 the stored entries (nnz) of that CSC matrix. */
 int32_t reo_get_info(reo_ctx *ctx, int64_t *info, int32_t n);
 
 #ifdef __cplusplus

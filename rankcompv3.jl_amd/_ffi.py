@@ -25,6 +25,7 @@ SYMBOLS = [
     "reo_set_matrix_f64", "reo_set_matrix_i64", "reo_set_matrix_dev_f64", "reo_set_matrix_dev_i64",
     "reo_set_matrix_f32", "reo_set_matrix_i32", "reo_set_matrix_dev_f32", "reo_set_matrix_dev_i32",
     "reo_set_matrix_rm_f64", "reo_set_matrix_rm_i64", "reo_set_matrix_rm_f32", "reo_set_matrix_rm_i32",
+    "reo_set_matrix_csc_f64", "reo_set_matrix_csc_i64", "reo_set_matrix_csc_f32", "reo_set_matrix_csc_i32",
     "reo_set_groups", "reo_compute_thresholds", "reo_set_thresholds", "reo_get_thresholds", "reo_threshold",
     "reo_build_pairs", "reo_pair_counts", "reo_get_codes", "reo_tally", "reo_identify_degs", "reo_mccullagh",
     "reo_set_profiling", "reo_reset_timings", "reo_get_timings", "reo_get_info",
@@ -102,6 +103,10 @@ def lib() -> ctypes.CDLL:
         "reo_set_matrix_rm_i64": (i32, [vp, vp, i64, i64, i64]),
         "reo_set_matrix_rm_f32": (i32, [vp, vp, i64, i64, i64]),
         "reo_set_matrix_rm_i32": (i32, [vp, vp, i64, i64, i64]),
+        "reo_set_matrix_csc_f64": (i32, [vp, i64, i64, vp, vp, vp]),
+        "reo_set_matrix_csc_i64": (i32, [vp, i64, i64, vp, vp, vp]),
+        "reo_set_matrix_csc_f32": (i32, [vp, i64, i64, vp, vp, vp]),
+        "reo_set_matrix_csc_i32": (i32, [vp, i64, i64, vp, vp, vp]),
         "reo_set_groups": (i32, [vp, vp, i64, i32]),
         "reo_compute_thresholds": (i32, [vp, f64]),
         "reo_set_thresholds": (i32, [vp, vp]),
@@ -213,6 +218,36 @@ def host_matrix_entry(X):
     return matrix_entry(X)
 
 
+def is_sparse(X) -> bool:
+    """A scipy.sparse matrix (or anything else that converts itself with .tocsc()): never handed to np.asarray."""
+    return hasattr(X, "tocsc") and not isinstance(X, np.ndarray)
+
+
+def csc_entry(M):
+    """(symbol name, colptr int64, rowidx int32, val, G, S) for a sparse expression matrix (genes x samples; anything with .tocsc():
+    CSR, COO and CSC alike): which reo_set_matrix_csc_* takes it and the three arrays that are handed over.  Pure: no library, no GPU.
+    The library wants the row indices of a column strictly increasing, so a matrix that is not in canonical format (unsorted indices or
+    duplicates) is COPIED and sum_duplicates()-ed; the caller's matrix is never modified.  A canonical CSC matrix is handed over without
+    copying `data`; `indices` is copied only if it is not int32, `indptr` is cast to int64.  Value dtypes follow matrix_entry's rule:
+    Float64 / Int64 / Float32 / Int32 as they are, narrower integers and bool to Int64, every other float type to Float64."""
+    if len(M.shape) != 2:
+        raise DimensionMismatch(REO_EINVAL, "expression matrix must be 2-D (genes x samples)")
+    m = M.tocsc()   # (a CSC matrix answers with itself)
+    if not m.has_canonical_format:
+        if m is M or np.shares_memory(m.data, getattr(M, "data", m.data)):
+            m = m.copy()
+        m.sum_duplicates()   # sorts the indices of every column and adds up repeated entries, in place (on the copy)
+    G, S = m.shape
+    if m.dtype in _NATIVE:
+        want = m.dtype
+    else:
+        want = np.dtype(np.int64) if (np.issubdtype(m.dtype, np.integer) or m.dtype == np.bool_) else np.dtype(np.float64)
+    val = np.ascontiguousarray(m.data, dtype=want)
+    rowidx = np.ascontiguousarray(m.indices, dtype=np.int32)
+    colptr = np.ascontiguousarray(m.indptr, dtype=np.int64)
+    return "reo_set_matrix_csc_" + _NATIVE[want], colptr, rowidx, val, int(G), int(S)
+
+
 UNIQUE_ID_BYTES = 128
 
 
@@ -283,7 +318,13 @@ class Context:
     def set_matrix(self, X: np.ndarray) -> None:
         """X is genes x samples (host); Float64, Float32, Int64 or Int32 as it is, any other integer dtype -> Int64, any other float
         dtype -> Float64, like Matrix(df_expr).  A column-major array is read in place; a row-major (C-ordered) one is copied
-        column-major on the host first, or with REO_ROWMAJOR=1 read in place too (host_matrix_entry)."""
+        column-major on the host first, or with REO_ROWMAJOR=1 read in place too (host_matrix_entry).  A scipy.sparse matrix goes up
+        as CSC and becomes dense on the device (csc_entry)."""
+        if is_sparse(X):   # a scipy.sparse matrix: CSC, densified on the device (csc_entry); there is no other route for one
+            name, colptr, rowidx, val, G, S = csc_entry(X)
+            check(getattr(self._L, name)(self._h, G, S, _ptr(colptr), _ptr(rowidx) if rowidx.size else None, _ptr(val) if val.size else None))
+            self.G, self.S = G, S
+            return
         name, Xf, ld = host_matrix_entry(X)
         G, S = Xf.shape
         check(getattr(self._L, name)(self._h, _ptr(Xf), G, S, ld))
@@ -456,11 +497,12 @@ class Context:
                 "k2_full_launches": int(ms[9]), "k2_delta_ms": ms[10], "set_matrix_host_wall_ms": ms[11]}
 
     def info(self) -> dict:
-        v = np.zeros(22, dtype=np.int64)
-        check(self._L.reo_get_info(self._h, _ptr(v), 22))
+        v = np.zeros(24, dtype=np.int64)
+        check(self._L.reo_get_info(self._h, _ptr(v), 24))
         return {"G": int(v[0]), "S": int(v[1]), "Gp": int(v[2]), "table_bytes": int(v[3]), "has_ties": int(v[4]),
                 "tiles_owned": int(v[5]), "tiles_total": int(v[6]), "tile_i": int(v[7]), "chunk_j": int(v[8]),
                 "chunks_per_panel": int(v[9]), "unit_h": int(v[10]), "sample_slots": int(v[11]),
                 "shared_group_counts": int(v[12]), "group_count_bytes": int(v[13]), "transform_in_lds": int(v[14]), "xcc_local_histograms": int(v[15]),
                 "cycle_period": int(v[16]), "cycle_found_at_pass": int(v[17]), "cycle_passes_skipped": int(v[18]), "upload_link_bytes": int(v[19]),
-                "eager_range_launches": int(v[20]), "rowmajor_upload": int(v[21])}
+                "eager_range_launches": int(v[20]), "rowmajor_upload": int(v[21]),
+                "csc_upload": int(v[22]), "csc_nnz": int(v[23])}

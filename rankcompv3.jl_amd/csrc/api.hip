@@ -14,6 +14,7 @@
 #include <cstring>
 
 #include "reo_internal.h"
+#include "upload_csc.h"
 
 #include <mutex>
 #include <unordered_map>
@@ -354,9 +355,20 @@ static void invalidate(reo_ctx *c)
 // dtype: what the caller hands over -- 1 Float64, 2 Int64, 3 Float32, 4 Int32 (which becomes a resident Int64 matrix: its tie is equality)
 static size_t elem_bytes(int dtype) { return dtype >= 3 ? 4 : 8; }
 
-// rowmajor (host matrices only): X[g * ld + s], ld >= S; the resident matrix is the same column-major one either way
-static int32_t set_matrix(reo_ctx *c, const void *X, int64_t G, int64_t S, int64_t ld, int dtype, bool on_device, bool rowmajor = false)
+static int32_t check_shape(int64_t G, int64_t S)
 {
+    if (G < 2 || G > kMaxGenes || S < 2 || S > (1 << 20)) {
+        set_error("matrix is %lld x %lld; G must be in [2, %d] and S in [2, 1048576]", (long long)G, (long long)S, kMaxGenes);
+        return REO_EINVAL;
+    }
+    return REO_OK;
+}
+
+// layout (host matrices only): row-major is X[g * ld + s], ld >= S; CSC hands over the reo::CscSrc of its element type as X (ld unused);
+// the resident matrix is the same column-major one every way
+static int32_t set_matrix(reo_ctx *c, const void *X, int64_t G, int64_t S, int64_t ld, int dtype, bool on_device, int layout = kLayoutColMajor)
+{
+    const bool rowmajor = layout == kLayoutRowMajor;
     int32_t rc = use(c);
     if (rc) return rc;
     if (dtype >= 3 && getenv("REO_TRANSFORM") && getenv("REO_TRANSFORM")[0] == 's') {
@@ -364,14 +376,12 @@ static int32_t set_matrix(reo_ctx *c, const void *X, int64_t G, int64_t S, int64
         return REO_EINVAL;
     }
     if (!X) { set_error("matrix pointer is null"); return REO_EINVAL; }
-    if (G < 2 || G > kMaxGenes || S < 2 || S > (1 << 20)) {
-        set_error("matrix is %lld x %lld; G must be in [2, %d] and S in [2, 1048576]", (long long)G, (long long)S, kMaxGenes);
-        return REO_EINVAL;
-    }
+    if ((rc = check_shape(G, S))) return rc;
     if (rowmajor && ld < S) { set_error("row pitch %lld < S = %lld (row-major: ld counts the elements from one gene's row to the next)", (long long)ld, (long long)S); return REO_EINVAL; }
-    if (!rowmajor && ld < G) { set_error("leading dimension %lld < G = %lld", (long long)ld, (long long)G); return REO_EINVAL; }
+    if (layout == kLayoutColMajor && ld < G) { set_error("leading dimension %lld < G = %lld", (long long)ld, (long long)G); return REO_EINVAL; }
     invalidate(c);
     c->rowmajor_upload = 0;
+    c->csc_upload = 0; c->csc_nnz = 0;
     const bool host_i32 = dtype == 4 && !on_device;
     const size_t resident = static_cast<size_t>(G) * S * (dtype == 3 ? 4 : 8);   // bytes of the matrix the kernels read
     c->G = G; c->S = S; c->dtype = dtype == 4 ? 2 : dtype;
@@ -402,9 +412,10 @@ static int32_t set_matrix(reo_ctx *c, const void *X, int64_t G, int64_t S, int64
                 ~DrainUp() { if (c->up) (void)hipStreamSynchronize(c->up); if (c->rk) (void)hipStreamSynchronize(c->rk); }
             } drain_up{c};
             DrainOnExit drain(c);
-            rc = eager_upload(c, X, ld, k1, host_i32, rowmajor);
+            rc = eager_upload(c, X, ld, k1, host_i32, layout);
             if (rc) { invalidate(c); return rc; }
             c->rowmajor_upload = rowmajor ? 1 : 0;
+            c->csc_upload = layout == kLayoutCsc ? 1 : 0;
             drain.dismiss();   // (the pair kernel may still be running, as after reo_build_pairs on one GPU: it reads device memory only)
             c->t_ms[11] += (wall_us() - w0) * 1e-3;
             if (c->eager_k1) { c->built_k = 0; c->table_complete = true; }
@@ -417,8 +428,9 @@ static int32_t set_matrix(reo_ctx *c, const void *X, int64_t G, int64_t S, int64
         } drain_up{c};
         DrainOnExit drain(c);
         const double w0 = wall_us();
-        if ((rc = upload_columns(c, X, ld, G, S, c->dX_owned.p, dtype, rowmajor))) { invalidate(c); return rc; }
+        if ((rc = upload_columns(c, X, ld, G, S, c->dX_owned.p, dtype, layout))) { invalidate(c); return rc; }
         c->rowmajor_upload = rowmajor ? 1 : 0;
+        c->csc_upload = layout == kLayoutCsc ? 1 : 0;
         drain.dismiss();   // (upload_columns has waited for the upload stream: the caller's array has been read)
         c->t_ms[11] += (wall_us() - w0) * 1e-3;
     }
@@ -566,7 +578,7 @@ using namespace reo;
 
 extern "C" {
 
-int32_t reo_version(void) { return 300; }
+int32_t reo_version(void) { return 400; }
 
 int32_t reo_trim_memory(void)
 {
@@ -750,12 +762,12 @@ int32_t reo_set_allgather(reo_ctx *c, reo_allgather_fn fn, void *user)
 
 // multi-GPU context: every device gets its own copy of the matrix (host source: one upload each; device source:
 // a peer copy from the leader's buffer)
-static int32_t set_matrix_all(reo_ctx *c, const void *X, int64_t G, int64_t S, int64_t ld, int dtype, bool on_device, bool rowmajor = false)
+static int32_t set_matrix_all(reo_ctx *c, const void *X, int64_t G, int64_t S, int64_t ld, int dtype, bool on_device, int layout = kLayoutColMajor)
 {
-    int32_t rc = set_matrix(c, X, G, S, ld, dtype, on_device, rowmajor);
+    int32_t rc = set_matrix(c, X, G, S, ld, dtype, on_device, layout);
     for (size_t d = 0; d < (c ? c->peers.size() : 0) && !rc; ++d) {
         reo_ctx *p = c->peers[d];
-        if (!on_device) { rc = set_matrix(p, X, G, S, ld, dtype, false, rowmajor); continue; }
+        if (!on_device) { rc = set_matrix(p, X, G, S, ld, dtype, false, layout); continue; }
         // (an Int32 device matrix: the leader has widened it into its own Int64 matrix, which is what the peers copy)
         const void *src = dtype == 4 ? c->dX : X;
         const int64_t sld = dtype == 4 ? G : ld;
@@ -781,10 +793,36 @@ int32_t reo_set_matrix_f32(reo_ctx *c, const float *X, int64_t G, int64_t S, int
 int32_t reo_set_matrix_i32(reo_ctx *c, const int32_t *X, int64_t G, int64_t S, int64_t ld) { return set_matrix_all(c, X, G, S, ld, 4, false); }
 int32_t reo_set_matrix_dev_f32(reo_ctx *c, const void *dX, int64_t G, int64_t S, int64_t ld) { return set_matrix_all(c, dX, G, S, ld, 3, true); }
 int32_t reo_set_matrix_dev_i32(reo_ctx *c, const void *dX, int64_t G, int64_t S, int64_t ld) { return set_matrix_all(c, dX, G, S, ld, 4, true); }
-int32_t reo_set_matrix_rm_f64(reo_ctx *c, const double *X, int64_t G, int64_t S, int64_t ld) { return set_matrix_all(c, X, G, S, ld, 1, false, true); }
-int32_t reo_set_matrix_rm_i64(reo_ctx *c, const int64_t *X, int64_t G, int64_t S, int64_t ld) { return set_matrix_all(c, X, G, S, ld, 2, false, true); }
-int32_t reo_set_matrix_rm_f32(reo_ctx *c, const float *X, int64_t G, int64_t S, int64_t ld) { return set_matrix_all(c, X, G, S, ld, 3, false, true); }
-int32_t reo_set_matrix_rm_i32(reo_ctx *c, const int32_t *X, int64_t G, int64_t S, int64_t ld) { return set_matrix_all(c, X, G, S, ld, 4, false, true); }
+int32_t reo_set_matrix_rm_f64(reo_ctx *c, const double *X, int64_t G, int64_t S, int64_t ld) { return set_matrix_all(c, X, G, S, ld, 1, false, kLayoutRowMajor); }
+int32_t reo_set_matrix_rm_i64(reo_ctx *c, const int64_t *X, int64_t G, int64_t S, int64_t ld) { return set_matrix_all(c, X, G, S, ld, 2, false, kLayoutRowMajor); }
+int32_t reo_set_matrix_rm_f32(reo_ctx *c, const float *X, int64_t G, int64_t S, int64_t ld) { return set_matrix_all(c, X, G, S, ld, 3, false, kLayoutRowMajor); }
+int32_t reo_set_matrix_rm_i32(reo_ctx *c, const int32_t *X, int64_t G, int64_t S, int64_t ld) { return set_matrix_all(c, X, G, S, ld, 4, false, kLayoutRowMajor); }
+
+// A sparse host matrix (include/reo_hip.h, SPARSE).  What can be said without reading the entries is said here; the colptr runs and
+// the row indices are checked chunk by chunk by the host threads that read them (transform.hip, CscUploader).
+extern "C++" template <class V>
+static int32_t set_matrix_csc(reo_ctx *c, int64_t G, int64_t S, const int64_t *colptr, const int32_t *rowidx, const V *val, int dtype)
+{
+    if (!c) { set_error("null context"); return REO_EINVAL; }
+    int32_t rc = check_shape(G, S);
+    if (rc) return rc;
+    if (!colptr) { set_error("colptr is null"); return REO_EINVAL; }
+    if (colptr[0] != 0) { set_error("colptr must start at 0 (colptr[0] = %lld)", (long long)colptr[0]); return REO_EINVAL; }
+    const int64_t nnz = colptr[S];
+    if (nnz < 0 || nnz > G * S) { set_error("colptr[S] = %lld is not a number of entries of a %lld x %lld matrix", (long long)nnz, (long long)G, (long long)S); return REO_EINVAL; }
+    if (nnz > 0 && (!rowidx || !val)) { set_error("%s is null with nnz = %lld entries", !rowidx ? "rowidx" : "val", (long long)nnz); return REO_EINVAL; }
+    const CscSrc<V> src{colptr, rowidx, val, nnz};
+    rc = set_matrix_all(c, &src, G, S, 0, dtype, false, kLayoutCsc);
+    if (!rc) {
+        c->csc_nnz = nnz;
+        for (reo_ctx *p : c->peers) p->csc_nnz = nnz;
+    }
+    return rc;
+}
+int32_t reo_set_matrix_csc_f64(reo_ctx *c, int64_t G, int64_t S, const int64_t *colptr, const int32_t *rowidx, const double *val) { return set_matrix_csc(c, G, S, colptr, rowidx, val, 1); }
+int32_t reo_set_matrix_csc_i64(reo_ctx *c, int64_t G, int64_t S, const int64_t *colptr, const int32_t *rowidx, const int64_t *val) { return set_matrix_csc(c, G, S, colptr, rowidx, val, 2); }
+int32_t reo_set_matrix_csc_f32(reo_ctx *c, int64_t G, int64_t S, const int64_t *colptr, const int32_t *rowidx, const float *val) { return set_matrix_csc(c, G, S, colptr, rowidx, val, 3); }
+int32_t reo_set_matrix_csc_i32(reo_ctx *c, int64_t G, int64_t S, const int64_t *colptr, const int32_t *rowidx, const int32_t *val) { return set_matrix_csc(c, G, S, colptr, rowidx, val, 4); }
 
 int32_t reo_set_groups(reo_ctx *c, const int32_t *group_id, int64_t len, int32_t ngroups)
 {
@@ -1239,12 +1277,13 @@ int32_t reo_get_timings(reo_ctx *c, double *ms, int32_t n)
 int32_t reo_get_info(reo_ctx *c, int64_t *info, int32_t n)
 {
     if (!c || !info) { set_error("null argument"); return REO_EINVAL; }
-    const int64_t v[22] = {c->G, c->S, c->Gp, static_cast<int64_t>(c->table.n * sizeof(uint32_t)), c->has_ties,
+    const int64_t v[24] = {c->G, c->S, c->Gp, static_cast<int64_t>(c->table.n * sizeof(uint32_t)), c->has_ties,
                            c->tiles_owned, c->tiles_total, kTileI, c->k1_cj, c->k1_q, kUnitH,
                            c->goff32.empty() ? 0 : c->goff32.back(), c->last_k1_shared,
                            static_cast<int64_t>(c->gcounts.n * sizeof(uint16_t)), c->transform_in_lds, c->xcc_local,
-                           c->it_cycle_period, c->it_cycle_at, c->it_cycle_skipped, c->narrowed_bytes, c->eager_range_launches, c->rowmajor_upload};
-    for (int i = 0; i < n && i < 22; ++i) info[i] = v[i];
+                           c->it_cycle_period, c->it_cycle_at, c->it_cycle_skipped, c->narrowed_bytes, c->eager_range_launches, c->rowmajor_upload,
+                           c->csc_upload, c->csc_nnz};
+    for (int i = 0; i < n && i < 24; ++i) info[i] = v[i];
     return REO_OK;
 }
 

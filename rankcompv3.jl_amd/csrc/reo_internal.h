@@ -233,6 +233,9 @@ struct reo_ctx {
     hipEvent_t ev_stage[3] = {nullptr, nullptr, nullptr}, ev_widen[3] = {nullptr, nullptr, nullptr};
     int64_t narrowed_bytes = 0;          // bytes the last pipelined upload put on the link (reo_get_info 19)
     int rowmajor_upload = 0;             // the last host matrix was read row-major in place (reo_set_matrix_rm_*; reo_get_info 21)
+    int csc_upload = 0;                  // the last host matrix came as CSC (reo_set_matrix_csc_*; reo_get_info 22) ...
+    int64_t csc_nnz = 0;                 // ... with this many stored entries (reo_get_info 23)
+    reo::DevBuf<int64_t> csc_colptr;     // its column pointer, which t_csc_columns reads (transform.hip, CscUploader)
     bool eager_k1 = false;               // reo_set_matrix has already launched the pair kernel of comparison 0 on this data, groups and thresholds
     int has_ties = 0;
     int transform_in_lds = 0;  // the last transform sorted each sample inside one workgroup's LDS (transform.hip)
@@ -339,8 +342,11 @@ namespace reo {
 // transform.hip
 int32_t run_transform(reo_ctx *c);
 // host matrix -> HBM in chunks, ranked (and paired) as they arrive (host_i32: the host array is Int32, the resident matrix Int64)
-int32_t eager_upload(reo_ctx *c, const void *hX, int64_t hld, bool with_k1, bool host_i32 = false, bool rowmajor = false);   // rowmajor: hX is genes x samples row-major, hld its pitch
-int32_t upload_columns(reo_ctx *c, const void *hX, int64_t hld, int64_t G, int64_t ncols, void *dX, int dtype, bool rowmajor = false);  // a host matrix into a device matrix (ld = G), chunked, Int64 narrowed
+// how a host matrix lies: column-major (hld = leading dimension), row-major (genes x samples, hld = its pitch), or CSC (hX points at the
+// reo::CscSrc<element type> of upload_csc.h, hld unused)
+enum { kLayoutColMajor = 0, kLayoutRowMajor = 1, kLayoutCsc = 2 };
+int32_t eager_upload(reo_ctx *c, const void *hX, int64_t hld, bool with_k1, bool host_i32 = false, int layout = kLayoutColMajor);
+int32_t upload_columns(reo_ctx *c, const void *hX, int64_t hld, int64_t G, int64_t ncols, void *dX, int dtype, int layout = kLayoutColMajor);  // a host matrix into a device matrix (ld = G), chunked, Int64 narrowed
 int32_t widen_device_i32(reo_ctx *c, const void *dX32, int64_t ld, int64_t G, int64_t S, void *dX64);  // a device Int32 matrix into a dense Int64 one, on c->stream
 int32_t ensure_upload_streams(reo_ctx *c);                                      // c->up, c->rk and their events (created on first use)
 int32_t ensure_staging(reo_ctx *c, size_t slot_bytes);                          // three pinned + device staging slots of at least that size, their events

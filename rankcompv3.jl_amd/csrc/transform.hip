@@ -41,6 +41,7 @@
 
 #include "reo_internal.h"
 #include "upload_rows.h"
+#include "upload_csc.h"
 
 namespace reo {
 
@@ -1679,14 +1680,15 @@ static bool rowmajor_pack_default()
 // REO_UPLOAD_TIMES=1 (tools/rowmajor_ab.py): HIP events in front of the copy, behind it and behind the transposition of every row-major
 // chunk; the uploader prints one line per chunk to stderr when it goes out of scope (the upload stream is idle by then).  Off: nothing.
 struct ChunkTimes {
-    struct Rec { int c0, nc, width; hipEvent_t e[3]; };
+    struct Rec { int c0, nc, width; double link_bytes; hipEvent_t e[3]; };
     bool on = false;
+    const char *kernel = "transposition";   // what follows the copy (CSC chunks: "densify")
     std::vector<Rec> recs;
     void init() { const char *e = getenv("REO_UPLOAD_TIMES"); on = e && e[0] == '1'; }
-    void mark(hipStream_t st, int k, int c0 = 0, int nc = 0, int width = 0)
+    void mark(hipStream_t st, int k, int c0 = 0, int nc = 0, int width = 0, double link_bytes = -1.0)   // link_bytes < 0: G x nc x width
     {
         if (!on) return;
-        if (k == 0) { recs.push_back(Rec{c0, nc, width, {nullptr, nullptr, nullptr}}); }
+        if (k == 0) { recs.push_back(Rec{c0, nc, width, link_bytes, {nullptr, nullptr, nullptr}}); }
         Rec &r = recs.back();
         if (hipEventCreate(&r.e[k]) == hipSuccess) (void)hipEventRecord(r.e[k], st);
     }
@@ -1701,8 +1703,8 @@ struct ChunkTimes {
             }
             float copy_ms = 0.f, tr_ms = 0.f;
             (void)hipEventElapsedTime(&copy_ms, r.e[0], r.e[1]); (void)hipEventElapsedTime(&tr_ms, r.e[1], r.e[2]);
-            fprintf(stderr, "  upload chunk: columns %d..%d, %d bytes per value, %.1f MB on the link: copy %.1f us, transposition %.1f us\n", r.c0, r.c0 + r.nc,
-                    r.width, static_cast<double>(G) * r.nc * r.width * 1e-6, copy_ms * 1e3, tr_ms * 1e3);
+            fprintf(stderr, "  upload chunk: columns %d..%d, %d bytes per value, %.1f MB on the link: copy %.1f us, %s %.1f us\n", r.c0, r.c0 + r.nc,
+                    r.width, (r.link_bytes < 0 ? static_cast<double>(G) * r.nc * r.width : r.link_bytes) * 1e-6, copy_ms * 1e3, kernel, tr_ms * 1e3);
         }
         clear();
     }
@@ -2009,8 +2011,228 @@ struct Uploader32 {
     }
 };
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Sparse host matrices (reo_set_matrix_csc_*): a run of CSC columns becomes the same columns of the resident column-major matrix.
+// t_csc_columns writes the dense matrix EXACTLY ONCE: a workgroup owns one (column, tile of kCscTile consecutive gene rows), clears the
+// tile in LDS, finds its entries by a binary search of the column's row indices (sorted, no duplicates: the host readers of
+// upload_csc.h have refused anything else, and every index is inside [0, G)) for the tile's two bounds, drops them into LDS -- widened to
+// W as they go -- and streams the tile out.  No memset pass in front of a scatter, no atomics, no read of the destination.
+//   rows / vals: the run's entries as they crossed the link (entry q of the run at [q]); colptr: the matrix's column pointer on the
+//   device, offset to the run's first column, e0 = its first entry; dst: that column's place in the resident matrix (ld = G).
+// kCscTile = 2048 rows: 16 KB of LDS for 8-byte elements, so 8 workgroups of 256 threads (the 32 waves a CU holds) fit into 160 KB
+// beside one another -- most tiles of a sparse column only store zeros and want many stores in flight, not a large tile -- and a
+// 20 000-gene column is 10 workgroups.  The tile sits in LDS at the offset its first element has behind a 16-byte boundary in global
+// memory (a column starts at any multiple of sizeof(W) when G is odd), so a 16-byte piece of LDS is a 16-byte aligned piece of the
+// column: the body leaves as 16-byte stores, 1 KB per wave instruction, the ragged ends as elements.
+constexpr int kCscTile = 2048;
+template <class RowT, class ValT, class W>
+__global__ __launch_bounds__(256) void t_csc_columns(const int64_t *__restrict__ colptr, int64_t e0, const RowT *__restrict__ rows,
+                                                     const ValT *__restrict__ vals, W *__restrict__ dst, int G)
+{
+    constexpr int VEC = 16 / static_cast<int>(sizeof(W));
+    __shared__ __attribute__((aligned(16))) W tile[kCscTile + VEC];
+    const int t = threadIdx.x;
+    const size_t col = blockIdx.x;
+    const int r0 = static_cast<int>(blockIdx.y) * kCscTile, len = min(kCscTile, G - r0);   // (the grid has no tile behind row G: len >= 1)
+    W *out = dst + col * static_cast<size_t>(G) + r0;
+    const int shift = static_cast<int>((reinterpret_cast<uintptr_t>(out) / sizeof(W)) % VEC);   // elements behind a 16-byte boundary
+    for (int v = t; v < (kCscTile + VEC) / VEC; v += 256) reinterpret_cast<uint4 *>(tile)[v] = uint4{0, 0, 0, 0};   // +0 of every W
+    __syncthreads();
+    const int64_t a = colptr[col] - e0, b = colptr[col + 1] - e0;   // the column's entries, relative to the run
+    if (a < b) {   // (workgroup-uniform, like the two searches: every lane reads the same words)
+        auto first_at_or_above = [&](int row) -> int64_t {
+            int64_t lo = a, hi = b;
+            while (lo < hi) {
+                const int64_t mid = lo + ((hi - lo) >> 1);
+                if (static_cast<int>(rows[mid]) < row) lo = mid + 1; else hi = mid;
+            }
+            return lo;
+        };
+        const int64_t f = first_at_or_above(r0), l = first_at_or_above(r0 + len);
+        for (int64_t q = f + t; q < l; q += 256) tile[shift + static_cast<int>(rows[q]) - r0] = static_cast<W>(vals[q]);   // (exact, as in t_widen; a stored -0.0 stays -0.0)
+    }
+    __syncthreads();
+    W *base = out - shift;   // 16-byte aligned; LDS position k is base[k], the tile is positions [shift, shift + len)
+    const int nvec = (shift + len + VEC - 1) / VEC;
+    for (int v = t; v < nvec; v += 256) {
+        const int k = v * VEC;
+        if (k >= shift && k + VEC <= shift + len) {
+            *reinterpret_cast<uint4 *>(base + k) = *reinterpret_cast<const uint4 *>(tile + k);
+        } else {
+#pragma unroll
+            for (int j = 0; j < VEC; ++j)
+                if (k + j >= shift && k + j < shift + len) base[k + j] = tile[k + j];
+        }
+    }
+}
+
+// One run of CSC columns per send(), for the plain and the pipelined upload alike (the interface of ChunkUploader).  A run is the entry
+// range colptr[c0] .. colptr[c0 + nc]: nothing or nc x G entries, so it crosses the link in PIECES of whole columns of at most `cap`
+// entries (a column has at most G <= cap), each through one slot of the staging ring -- the slots are sized by the entries, never by
+// nc x G.  Per piece the host threads check the row indices (upload_csc.h) and narrow them to 16 bits when G <= 65 536, and narrow
+// Int64 / Float64 values up the form ladder of ChunkUploader (the width only grows); Float32 / Int32 values, RAW values and -- with
+// REO_UPLOAD_THREADS=0, where the calling thread does the checking -- the row indices go from the caller's arrays as they are.  The
+// matrix's colptr goes to the device once, in init().  A container fault leaves the resident matrix incomplete: the context then holds
+// no matrix (dtype 0) until the next reo_set_matrix_*.
+template <class V, class T>
+struct CscUploader {
+    static constexpr bool kLadder = sizeof(V) == 8;
+    enum Form { I16 = 0, I32 = 1, F32 = 2, RAW = 3 };   // as ChunkUploader::Form
+    reo_ctx *c = nullptr;
+    CscSrc<V> src;
+    int64_t G = 0, cap = 0;
+    T *dX = nullptr;
+    int form = RAW, nslot = 0, nthreads = 1;
+    bool pinned = false, r16 = false;
+    size_t voff = 0;   // where a slot's values begin (bytes)
+    ChunkTimes times;
+    ~CscUploader() { if (times.on) times.report(c->up, G); }
+
+    int32_t init(reo_ctx *ctx, const CscSrc<V> *host, int64_t, int64_t genes, T *dev, int, bool = false, int64_t ncols = 0)
+    {
+        c = ctx; src = *host; G = genes; dX = dev;
+        int32_t rc;
+        if ((rc = ensure_upload_streams(c))) return rc;
+        times.init();
+        times.kernel = "densify";
+        pinned = c->upload_threads > 0;
+        r16 = pinned && G <= 65536;
+        cap = std::max<int64_t>(G, std::min<int64_t>(std::max<int64_t>(src.nnz, 1), int64_t(2) << 20));
+        voff = (static_cast<size_t>(cap) * (r16 ? 2 : 4) + 15) / 16 * 16;
+        if (pinned) {   // the pinned half holds narrowed values only
+            if ((rc = ensure_staging(c, voff + static_cast<size_t>(cap) * (kLadder ? 4 : 0)))) return rc;
+            nthreads = upload_host_threads(c);
+            if (kLadder) form = I16;
+        }
+        for (int q = 0; q < 3; ++q) {
+            if ((rc = c->stage_d[q].ensure(voff + static_cast<size_t>(cap) * sizeof(V)))) return rc;
+            if (!c->ev_widen[q]) REO_HIP_CHECK(handle_event(&c->ev_widen[q], 0));
+        }
+        if ((rc = c->csc_colptr.ensure(static_cast<size_t>(ncols) + 1))) return rc;
+        REO_HIP_CHECK(hipMemcpyAsync(c->csc_colptr.p, src.colptr, (static_cast<size_t>(ncols) + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->up));
+        c->narrowed_bytes = (ncols + 1) * static_cast<int64_t>(sizeof(int64_t));
+        return REO_OK;
+    }
+
+    int32_t send(int c0, int nc, hipEvent_t *ready)
+    {
+        int64_t at = 0;
+        if (check_colptr_run(src.colptr, c0, nc, G, src.nnz, &at) != kCscOk) {
+            c->dtype = 0;
+            set_error("colptr is not a column pointer at column %lld: it must be non-decreasing, stay inside [0, nnz = colptr[S] = %lld] and give no column "
+                      "more than G = %lld entries", (long long)at, (long long)src.nnz, (long long)G);
+            return REO_EINVAL;
+        }
+        for (int p0 = c0; p0 < c0 + nc;) {
+            int p1 = p0 + 1;
+            while (p1 < c0 + nc && src.colptr[p1 + 1] - src.colptr[p0] <= cap) ++p1;
+            const int32_t rc = send_piece(p0, p1, ready);
+            if (rc) return rc;
+            p0 = p1;
+        }
+        return REO_OK;
+    }
+
+private:
+    bool narrow_as(int f, const V *v, int64_t a, int64_t b, unsigned char *d) const
+    {
+        if constexpr (kLadder) {
+            if (f == I16) return narrow_values<int16_t>(v, a, b, reinterpret_cast<int16_t *>(d));
+            if (f == I32) return narrow_values<int32_t>(v, a, b, reinterpret_cast<int32_t *>(d));
+            if constexpr (std::is_same<V, double>::value) return narrow_values<float>(v, a, b, reinterpret_cast<float *>(d));
+        }
+        return false;
+    }
+
+    template <class RowT, class ValT>
+    hipError_t densify(const unsigned char *ds, int p0, int np, int64_t e0)
+    {
+        const dim3 grid(static_cast<unsigned>(np), static_cast<unsigned>((G + kCscTile - 1) / kCscTile));   // (G <= 262 143: 128 tiles)
+        t_csc_columns<RowT, ValT, T><<<grid, 256, 0, c->up>>>(c->csc_colptr.p + p0, e0, reinterpret_cast<const RowT *>(ds), reinterpret_cast<const ValT *>(ds + voff),
+                                                              dX + static_cast<size_t>(p0) * G, static_cast<int>(G));
+        return hipGetLastError();
+    }
+    template <class RowT>
+    hipError_t densify_form(int f, const unsigned char *ds, int p0, int np, int64_t e0)
+    {
+        if constexpr (kLadder) {
+            if (f == I16) return densify<RowT, int16_t>(ds, p0, np, e0);
+            if (f == I32) return densify<RowT, int32_t>(ds, p0, np, e0);
+            if constexpr (std::is_same<V, double>::value) if (f == F32) return densify<RowT, float>(ds, p0, np, e0);
+        }
+        return densify<RowT, V>(ds, p0, np, e0);
+    }
+
+    int32_t send_piece(int p0, int p1, hipEvent_t *ready)   // columns [p0, p1): at most cap entries
+    {
+        const int64_t e0 = src.colptr[p0], n = src.colptr[p1] - e0;
+        const int np = p1 - p0, sl = nslot % 3;
+        unsigned char *hs = c->stage_h[sl], *ds = c->stage_d[sl].p;
+        int sent = RAW;   // the form this piece's values take on the link
+        if (n > 0) {
+            const V *val = src.val + e0;
+            const int64_t per = (n + nthreads - 1) / nthreads;
+            // the slot's pinned half is free when the copy that read it is done (ev_stage); its device half when the kernel that read it
+            // is (the next copy into it follows on the same stream)
+            if (pinned && nslot >= 3) REO_HIP_CHECK(hipEventSynchronize(c->ev_stage[sl]));
+            std::atomic<int> verdict{kCscOk};
+            auto rows_of = [&](int64_t a, int64_t b) {
+                const CscVerdict v = !pinned ? read_rows<int32_t>(src.colptr, p0, np, src.rowidx, G, a, b, nullptr)
+                                   : r16     ? read_rows<uint16_t>(src.colptr, p0, np, src.rowidx, G, a, b, reinterpret_cast<uint16_t *>(hs))
+                                             : read_rows<int32_t>(src.colptr, p0, np, src.rowidx, G, a, b, reinterpret_cast<int32_t *>(hs));
+                int none = kCscOk;
+                if (v != kCscOk) verdict.compare_exchange_strong(none, v);
+            };
+            if (pinned) HostPool::get(nthreads).run(nthreads, [&](int t) { const int64_t a = std::min(n, t * per); rows_of(a, std::min(n, a + per)); });
+            else rows_of(0, n);
+            if (verdict.load() != kCscOk) {
+                c->dtype = 0;
+                if (verdict.load() == kCscRowRange) set_error("a row index in columns %d..%d is outside [0,%lld)", p0, p1, (long long)G);
+                else set_error("the row indices of a column in %d..%d are not strictly increasing (unsorted or duplicate entries)", p0, p1);
+                return REO_EINVAL;
+            }
+            while (pinned && form != RAW) {
+                if (form == F32 && !std::is_same<V, double>::value) { form = RAW; break; }
+                unsigned char probe[256 * 4];   // the head of the piece decides in microseconds what real Float64 data would find out after a whole converted piece per form
+                if (!narrow_as(form, val, 0, std::min<int64_t>(n, 256), probe)) { ++form; continue; }
+                std::atomic<int> fits{1};
+                const int f = form;
+                HostPool::get(nthreads).run(nthreads, [&](int t) {
+                    const int64_t a = std::min(n, t * per), b = std::min(n, a + per);
+                    if (a < b && !narrow_as(f, val, a, b, hs + voff)) fits.store(0);
+                });
+                if (fits.load()) break;
+                ++form;   // (this piece again, one form up)
+            }
+            sent = pinned ? form : RAW;
+        }
+        const size_t rb = r16 ? 2 : 4, width = sent == I16 ? 2 : (sent == RAW ? sizeof(V) : 4);
+        const size_t link = static_cast<size_t>(n) * (rb + width);
+        times.mark(c->up, 0, p0, np, static_cast<int>(width), static_cast<double>(link));
+        if (n > 0) {
+            if (pinned) REO_HIP_CHECK(hipMemcpyAsync(ds, hs, static_cast<size_t>(n) * rb, hipMemcpyHostToDevice, c->up));
+            else REO_HIP_CHECK(hipMemcpyAsync(ds, src.rowidx + e0, static_cast<size_t>(n) * rb, hipMemcpyHostToDevice, c->up));
+            if (sent != RAW) REO_HIP_CHECK(hipMemcpyAsync(ds + voff, hs + voff, static_cast<size_t>(n) * width, hipMemcpyHostToDevice, c->up));
+            else REO_HIP_CHECK(hipMemcpyAsync(ds + voff, src.val + e0, static_cast<size_t>(n) * width, hipMemcpyHostToDevice, c->up));   // pageable: returns when staged
+            if (pinned) REO_HIP_CHECK(hipEventRecord(c->ev_stage[sl], c->up));
+        }
+        times.mark(c->up, 1);
+        REO_HIP_CHECK((r16 ? densify_form<uint16_t>(sent, ds, p0, np, e0) : densify_form<int32_t>(sent, ds, p0, np, e0)));
+        times.mark(c->up, 2);
+        REO_HIP_CHECK(hipEventRecord(c->ev_widen[sl], c->up));
+        *ready = c->ev_widen[sl];
+        ++nslot;
+        c->narrowed_bytes += static_cast<int64_t>(link);
+        return REO_OK;
+    }
+};
+
 template <class H, class T>
-using UploaderFor = std::conditional_t<sizeof(H) == 4, Uploader32<H, T>, ChunkUploader<T>>;
+struct UploaderSel { using type = std::conditional_t<sizeof(H) == 4, Uploader32<H, T>, ChunkUploader<T>>; };
+template <class V, class T>
+struct UploaderSel<CscSrc<V>, T> { using type = CscUploader<V, T>; };
+template <class H, class T>
+using UploaderFor = typename UploaderSel<H, T>::type;
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Pipelined upload (round 5): reo_set_matrix_i64 / _f64 from HOST memory when groups (and thresholds) are already known.
@@ -2282,8 +2504,9 @@ int32_t ensure_staging(reo_ctx *c, size_t slot_bytes)
 // A whole host matrix (G x ncols, leading dimension hld) into a device matrix of leading dimension G, in chunks on the upload stream
 // (Int64 narrowed: ChunkUploader); the context's stream is ordered behind the last chunk, and the call returns when the host array has
 // been read.  dtype: 1 Float64, 2 Int64, 3 Float32, 4 Int32 on the host into an Int64 device matrix.
-int32_t upload_columns(reo_ctx *c, const void *hX, int64_t hld, int64_t G, int64_t ncols, void *dX, int dtype, bool rowmajor)
+int32_t upload_columns(reo_ctx *c, const void *hX, int64_t hld, int64_t G, int64_t ncols, void *dX, int dtype, int layout)
 {
+    const bool rowmajor = layout == kLayoutRowMajor;
     auto go = [&](auto *host, auto *dev) -> int32_t {
         using T = std::remove_pointer_t<decltype(dev)>;
         using H = std::remove_const_t<std::remove_pointer_t<decltype(host)>>;
@@ -2298,6 +2521,14 @@ int32_t upload_columns(reo_ctx *c, const void *hX, int64_t hld, int64_t G, int64
         REO_HIP_CHECK(hipStreamSynchronize(c->up));
         return REO_OK;
     };
+    if (layout == kLayoutCsc) {   // hX: the CscSrc of the host element type
+        switch (dtype) {
+        case 1: return go(static_cast<const CscSrc<double> *>(hX), static_cast<double *>(dX));
+        case 3: return go(static_cast<const CscSrc<float> *>(hX), static_cast<float *>(dX));
+        case 4: return go(static_cast<const CscSrc<int32_t> *>(hX), static_cast<int64_t *>(dX));
+        default: return go(static_cast<const CscSrc<int64_t> *>(hX), static_cast<int64_t *>(dX));
+        }
+    }
     switch (dtype) {
     case 1: return go(static_cast<const double *>(hX), static_cast<double *>(dX));
     case 3: return go(static_cast<const float *>(hX), static_cast<float *>(dX));
@@ -2315,8 +2546,15 @@ int32_t widen_device_i32(reo_ctx *c, const void *dX32, int64_t ld, int64_t G, in
     return REO_OK;
 }
 
-int32_t eager_upload(reo_ctx *c, const void *hX, int64_t hld, bool with_k1, bool host_i32, bool rowmajor)
+int32_t eager_upload(reo_ctx *c, const void *hX, int64_t hld, bool with_k1, bool host_i32, int layout)
 {
+    const bool rowmajor = layout == kLayoutRowMajor;
+    if (layout == kLayoutCsc) {   // hX: the CscSrc of the host element type
+        if (c->dtype == 1) return eager_upload_impl<double, CscSrc<double>>(c, static_cast<const CscSrc<double> *>(hX), hld, with_k1, false);
+        if (c->dtype == 3) return eager_upload_impl<float, CscSrc<float>>(c, static_cast<const CscSrc<float> *>(hX), hld, with_k1, false);
+        if (host_i32) return eager_upload_impl<int64_t, CscSrc<int32_t>>(c, static_cast<const CscSrc<int32_t> *>(hX), hld, with_k1, false);
+        return eager_upload_impl<int64_t, CscSrc<int64_t>>(c, static_cast<const CscSrc<int64_t> *>(hX), hld, with_k1, false);
+    }
     if (c->dtype == 1) return eager_upload_impl<double>(c, static_cast<const double *>(hX), hld, with_k1, rowmajor);
     if (c->dtype == 3) return eager_upload_impl<float>(c, static_cast<const float *>(hX), hld, with_k1, rowmajor);
     if (host_i32) return eager_upload_impl<int64_t, int32_t>(c, static_cast<const int32_t *>(hX), hld, with_k1, rowmajor);

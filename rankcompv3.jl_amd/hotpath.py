@@ -79,15 +79,17 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
     (numpy's default C order, column slices of a wider C-ordered array) is copied column-major on the host first, or, with REO_ROWMAJOR=1
     in the environment, read in place through reo_set_matrix_rm_* -- no transposing host copy, the library transposes on the device
     (_ffi.host_matrix_entry; opt-in until its timing has been recorded).
+    A scipy.sparse matrix (CSR / COO / CSC: AnnData's X) goes up as CSC -- no toarray(), the zeros never exist on the host or on the
+    link -- and becomes dense on the device (_ffi.csc_entry, reo_set_matrix_csc_*); the caller's matrix is not modified.
     Two groups: one comparison, group 1 vs
     group 2 (the reference's `gnum == 2` path, :387-389,431-434).  More groups: one comparison per
     group, that group vs every other sample (:375-390,396-436), 16 more columns each."""
     on_device = _ffi.is_device_tensor(data)   # a torch tensor on a ROCm device: used where it is (its device is the context's)
     if on_device:
         device = data.device.index if data.device.index is not None else -1
-    else:
+    elif not _ffi.is_sparse(data):   # (np.asarray of a sparse matrix is a 0-d object array)
         data = np.asarray(data)
-    if data.ndim != 2:
+    if len(data.shape) != 2:
         raise _ffi.DimensionMismatch(_ffi.REO_EINVAL, "'data' must be a genes x samples matrix")
     r, c = data.shape
     if c != len(group):  # :355
