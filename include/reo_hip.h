@@ -186,7 +186,15 @@ int32_t reo_set_allgather(reo_ctx *ctx, reo_allgather_fn fn, void *user);
  * Limits, ownership (everything has been read on return, no host pointer is kept), the NaN refusal, the +-Inf rule, the element-type
  * rules and both upload paths are those of the dense entries, and every result is BIT-IDENTICAL to reo_set_matrix_<type> on the
  * densified array, in every order of calls.  reo_get_info 19 counts what this upload sent (colptr included), 22 says that the last host
- * matrix came as CSC, 23 its nnz. */
+ * matrix came as CSC, 23 its nnz.
+ *
+ * CELLS.  reo_set_matrix_pseudobulk_csc_f64 / _csc_i64 / _dense_f64 / _dense_i64 (declared beside reo_pseudobulk_* below) make the pseudo-bulk
+ * profiles of a cell matrix the expression matrix without a trip through host memory, and reo_filter_matrix applies the reference's two
+ * low-expression filters (src/RankCompV3.jl:618, :626) to whatever matrix the context holds and compacts it in HBM.
+ * ORDER OF CALLS with them: matrix (any entry), then reo_filter_matrix, then reo_set_groups for the profiles that are LEFT, thresholds,
+ * reo_build_pairs.  The filter always invalidates what was derived from the matrix; groups of the old length then fail with the
+ * DimensionMismatch message until new ones are set.  A matrix that the pipelined upload has already ranked (groups set first, host
+ * entry) is ranked again after filtering: correct, but wasted -- filter first. */
 int32_t reo_set_matrix_f64(reo_ctx *ctx, const double *X, int64_t G, int64_t S, int64_t ld);
 int32_t reo_set_matrix_i64(reo_ctx *ctx, const int64_t *X, int64_t G, int64_t S, int64_t ld);
 int32_t reo_set_matrix_dev_f64(reo_ctx *ctx, const void *dX, int64_t G, int64_t S, int64_t ld);
@@ -292,12 +300,49 @@ int32_t reo_pseudobulk_csc_i64(reo_ctx *ctx, int64_t G, int64_t C, const int64_t
                                const int64_t *val, const int32_t *order, int64_t n_order,
                                const int32_t *chunk_ptr, int32_t n_out, int64_t *out);
 
+/* The same sums as the context's expression matrix.  Arguments, argument checks, the chunked and narrowed upload, the kernels and so the
+ * summation order (exact for Int64, bit-reproducible for Float64) are those of the reo_pseudobulk_* entry of the same name, without `out`:
+ * the G x n_out result is written into the context's own matrix in HBM (Float64 or Int64, ld = G) and becomes the expression matrix as if
+ * reo_set_matrix_dev_* had delivered it; nothing is copied to the host.  G and n_out must satisfy the limits of reo_set_matrix_* (G in
+ * [2, 262143], n_out in [2, 1048576]).  The context is invalidated as by reo_set_matrix_*; reo_get_info 19 and 21-23 read 0.  On ANY failure
+ * the context holds no matrix until the next reo_set_matrix_* (it stays usable).  Not available on a reo_create_multi context (REO_EINVAL;
+ * one process per GPU works, every rank has its own context). */
+int32_t reo_set_matrix_pseudobulk_dense_f64(reo_ctx *ctx, const double *X, int64_t G, int64_t C, int64_t ld,
+                                            const int32_t *order, int64_t n_order, const int32_t *chunk_ptr, int32_t n_out);
+int32_t reo_set_matrix_pseudobulk_dense_i64(reo_ctx *ctx, const int64_t *X, int64_t G, int64_t C, int64_t ld,
+                                            const int32_t *order, int64_t n_order, const int32_t *chunk_ptr, int32_t n_out);
+int32_t reo_set_matrix_pseudobulk_csc_f64(reo_ctx *ctx, int64_t G, int64_t C, const int64_t *colptr, const int32_t *rowidx,
+                                          const double *val, const int32_t *order, int64_t n_order,
+                                          const int32_t *chunk_ptr, int32_t n_out);
+int32_t reo_set_matrix_pseudobulk_csc_i64(reo_ctx *ctx, int64_t G, int64_t C, const int64_t *colptr, const int32_t *rowidx,
+                                          const int64_t *val, const int32_t *order, int64_t n_order,
+                                          const int32_t *chunk_ptr, int32_t n_out);
+
+/* The reference's low-expression filters on the resident matrix (any host entry, a _dev buffer, the pseudo-bulk entries; resident Float64,
+ * Int64 or Float32), :618 then :626 of src/RankCompV3.jl:
+ *   profile s is kept iff #{g : x[g,s] > 0} > min_profiles;
+ *   gene g is kept iff #{KEPT s : x[g,s] > 0} > min_features (a gene expressed only in dropped profiles goes too).
+ * `> 0` is the comparison of the element type: -0.0, negative values and NaN do not count, +Inf and subnormals do.
+ * profile_kept (S bytes) and gene_kept (G bytes) receive the 0 / 1 masks -- the caller subsets names, groups and a reference mask with them --
+ * and S_kept / G_kept the numbers S' and G'; any of the four may be NULL.  The compacted G' x S' matrix, order preserved, becomes the resident
+ * matrix (reo_get_info 0 and 1 then report G' and S').  When nothing is dropped no copy is made.  A caller's _dev buffer is never written:
+ * the compacted matrix lives in memory of the context's own, and the buffer may be released once the call has returned with something dropped.
+ * The call always invalidates the context (see CELLS / ORDER OF CALLS above).  G' < 2 or S' < 2: REO_EINVAL with the numbers in the message
+ * (masks and numbers are delivered all the same); the context then holds no matrix and stays usable.  Two counting kernels and one gather on
+ * the context's stream (stage timer 7), the G + S counts visit the host in between.  Not available on a reo_create_multi context (REO_EINVAL). */
+int32_t reo_filter_matrix(reo_ctx *ctx, int64_t min_profiles, int64_t min_features, uint8_t *profile_kept, uint8_t *gene_kept,
+                          int64_t *S_kept, int64_t *G_kept);
+
+/* Parity hook: the resident matrix as it stands, G x S column-major without the leading dimension, elements of 8 bytes (Float64 / Int64) or
+ * 4 (Float32); reo_get_info 24 says which.  `bytes` must be exactly G * S * element size (REO_EINVAL otherwise). */
+int32_t reo_get_matrix(reo_ctx *ctx, void *out, int64_t bytes);
+
 /* Stage timers (HIP events on the library's stream), milliseconds, summed
  * since the last reo_reset_timings.  Index: 0 rank/band transform, 1 pair
  * kernel K1, 2 tally stage K2 (full scan or incremental update, sum), 3 iteration passes in total (K2 + the
  * statistics kernels K3, sum), 4 number of K2 launches (passes enqueued after
  * convergence return at once and are counted too), 5 number of K1 launches,
- * 6 exchange of the class table between shards (HIP events), 7 pseudo-bulk kernel, 8 K2 stage of the passes that scanned the whole table (sum), 9 their
+ * 6 exchange of the class table between shards (HIP events), 7 pseudo-bulk kernel and the kernels of reo_filter_matrix, 8 K2 stage of the passes that scanned the whole table (sum), 9 their
  * number, 10 K2 stage of the passes that updated the tallies incrementally (sum), 11 host wall time inside reo_set_matrix_f64 / _i64 /
  * _f32 / _i32 (the upload from host memory, with whatever was pipelined behind it). */
 enum { REO_NTIMINGS = 12 };
@@ -326,7 +371,8 @@ int32_t reo_get_timings(reo_ctx *ctx, double *ms, int32_t n);
  * has arrived; the counts of a range wait in HBM for the group's last range, which classifies -- REO_EAGER_RANGES=1 in the environment
  * launches whole sides only, as in round 5; 2..6 asks for that many ranges per side; default: by the number of blocks), 21 the last
  * host matrix was read row-major in place (reo_set_matrix_rm_*: 1; every other reo_set_matrix_*: 0), 22 the last host matrix came as CSC
- * (reo_set_matrix_csc_*: 1; every other reo_set_matrix_*: 0), 23 the stored entries (nnz) of that CSC matrix. */
+ * (reo_set_matrix_csc_*: 1; every other reo_set_matrix_*: 0), 23 the stored entries (nnz) of that CSC matrix, 24 the element type of the
+ * resident matrix (0 none, 1 Float64, 2 Int64 -- Int32 input is widened --, 3 Float32). */
 int32_t reo_get_info(reo_ctx *ctx, int64_t *info, int32_t n);
 
 #ifdef __cplusplus

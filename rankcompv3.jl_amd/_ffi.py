@@ -30,6 +30,8 @@ SYMBOLS = [
     "reo_build_pairs", "reo_pair_counts", "reo_get_codes", "reo_tally", "reo_identify_degs", "reo_mccullagh",
     "reo_set_profiling", "reo_reset_timings", "reo_get_timings", "reo_get_info",
     "reo_pseudobulk_dense_f64", "reo_pseudobulk_dense_i64", "reo_pseudobulk_csc_f64", "reo_pseudobulk_csc_i64",
+    "reo_set_matrix_pseudobulk_dense_f64", "reo_set_matrix_pseudobulk_dense_i64", "reo_set_matrix_pseudobulk_csc_f64", "reo_set_matrix_pseudobulk_csc_i64",
+    "reo_filter_matrix", "reo_get_matrix",
 ]
 
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p)
@@ -126,6 +128,12 @@ def lib() -> ctypes.CDLL:
         "reo_pseudobulk_dense_i64": (i32, [vp, vp, i64, i64, i64, vp, i64, vp, i32, vp]),
         "reo_pseudobulk_csc_f64": (i32, [vp, i64, i64, vp, vp, vp, vp, i64, vp, i32, vp]),
         "reo_pseudobulk_csc_i64": (i32, [vp, i64, i64, vp, vp, vp, vp, i64, vp, i32, vp]),
+        "reo_set_matrix_pseudobulk_dense_f64": (i32, [vp, vp, i64, i64, i64, vp, i64, vp, i32]),
+        "reo_set_matrix_pseudobulk_dense_i64": (i32, [vp, vp, i64, i64, i64, vp, i64, vp, i32]),
+        "reo_set_matrix_pseudobulk_csc_f64": (i32, [vp, i64, i64, vp, vp, vp, vp, i64, vp, i32]),
+        "reo_set_matrix_pseudobulk_csc_i64": (i32, [vp, i64, i64, vp, vp, vp, vp, i64, vp, i32]),
+        "reo_filter_matrix": (i32, [vp, i64, i64, vp, vp, vp, vp]),
+        "reo_get_matrix": (i32, [vp, vp, i64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -454,10 +462,11 @@ class Context:
         return out
 
     # -- pseudo-bulk front end ------------------------------------------------------
-    def pseudobulk(self, cells, order, chunk_ptr) -> np.ndarray:
-        """Row-wise sums of groups of cells (src/RankCompV3.jl:56-67).  `cells` is a genes x cells
-        ndarray (Int64 / Float64) or a scipy.sparse matrix (converted to CSC); `order` lists the cells
-        of all output profiles back to back and chunk_ptr delimits them.  Returns genes x profiles."""
+    @staticmethod
+    def _pseudobulk_args(cells, order, chunk_ptr):
+        """The routing of pseudobulk / set_matrix_pseudobulk: ('csc' | 'dense', 'i64' | 'f64', the arguments up to n_out, G, arrays to
+        keep alive).  Sparse cells go up as CSC, everything else as a column-major array; integers as Int64, floats as Float64 (Float32
+        and Int32 cells are widened here)."""
         order = np.ascontiguousarray(order, dtype=np.int32)
         chunk_ptr = np.ascontiguousarray(chunk_ptr, dtype=np.int32)
         n_out = chunk_ptr.size - 1
@@ -469,17 +478,52 @@ class Context:
             val = np.ascontiguousarray(m.data, dtype=np.int64 if isint else np.float64)
             colptr = np.ascontiguousarray(m.indptr, dtype=np.int64)
             rowidx = np.ascontiguousarray(m.indices, dtype=np.int32)
-            out = np.zeros((G, n_out), dtype=val.dtype, order="F")
-            fn = self._L.reo_pseudobulk_csc_i64 if isint else self._L.reo_pseudobulk_csc_f64
-            check(fn(self._h, G, C, _ptr(colptr), _ptr(rowidx), _ptr(val), _ptr(order), order.size, _ptr(chunk_ptr), n_out, _ptr(out)))
-            return out
+            args = (G, C, _ptr(colptr), _ptr(rowidx), _ptr(val), _ptr(order), order.size, _ptr(chunk_ptr), n_out)
+            return "csc", "i64" if isint else "f64", args, G, (m, val, colptr, rowidx, order, chunk_ptr)
         X = np.asarray(cells)
         isint = np.issubdtype(X.dtype, np.integer)
         Xf = np.asfortranarray(X, dtype=np.int64 if isint else np.float64)
         G, C = Xf.shape
-        out = np.zeros((G, n_out), dtype=Xf.dtype, order="F")
-        fn = self._L.reo_pseudobulk_dense_i64 if isint else self._L.reo_pseudobulk_dense_f64
-        check(fn(self._h, _ptr(Xf), G, C, G, _ptr(order), order.size, _ptr(chunk_ptr), n_out, _ptr(out)))
+        args = (_ptr(Xf), G, C, G, _ptr(order), order.size, _ptr(chunk_ptr), n_out)
+        return "dense", "i64" if isint else "f64", args, G, (Xf, order, chunk_ptr)
+
+    def pseudobulk(self, cells, order, chunk_ptr) -> np.ndarray:
+        """Row-wise sums of groups of cells (src/RankCompV3.jl:56-67).  `cells` is a genes x cells
+        ndarray (Int64 / Float64) or a scipy.sparse matrix (converted to CSC); `order` lists the cells
+        of all output profiles back to back and chunk_ptr delimits them.  Returns genes x profiles."""
+        form, ty, args, G, keep = self._pseudobulk_args(cells, order, chunk_ptr)
+        out = np.zeros((G, args[-1]), dtype=np.int64 if ty == "i64" else np.float64, order="F")
+        check(getattr(self._L, f"reo_pseudobulk_{form}_{ty}")(self._h, *args, _ptr(out)))
+        return out
+
+    def set_matrix_pseudobulk(self, cells, order, chunk_ptr) -> None:
+        """The same sums, left on the device as the context's expression matrix (reo_set_matrix_pseudobulk_*): arguments and routing of
+        pseudobulk, nothing comes back to the host.  The profiles are the samples: set_groups wants one label per profile."""
+        form, ty, args, G, keep = self._pseudobulk_args(cells, order, chunk_ptr)
+        check(getattr(self._L, f"reo_set_matrix_pseudobulk_{form}_{ty}")(self._h, *args))
+        self.G, self.S = G, args[-1]
+
+    def filter_matrix(self, min_profiles: int = 0, min_features: int = 0):
+        """The reference's low-expression filters (src/RankCompV3.jl:618, :626) on the resident matrix, compacted on the device
+        (reo_filter_matrix).  Returns (profile_kept, gene_kept), bool masks over the samples and genes the matrix had; the context's G
+        and S are those of what is left, and groups have to be set (again) for the kept profiles."""
+        info = self.info()
+        pk = np.zeros(info["S"], dtype=np.uint8)
+        gk = np.zeros(info["G"], dtype=np.uint8)
+        sk, gkn = ctypes.c_int64(0), ctypes.c_int64(0)
+        check(self._L.reo_filter_matrix(self._h, int(min_profiles), int(min_features), _ptr(pk) if pk.size else None, _ptr(gk) if gk.size else None,
+                                        ctypes.byref(sk), ctypes.byref(gkn)))
+        self.G, self.S = int(gkn.value), int(sk.value)
+        return pk.astype(bool), gk.astype(bool)
+
+    def get_matrix(self) -> np.ndarray:
+        """The resident matrix as it stands (parity hook, reo_get_matrix): genes x samples, column-major, float64 / int64 / float32."""
+        info = self.info()
+        dt = {1: np.float64, 2: np.int64, 3: np.float32}.get(info["resident_dtype"])
+        if dt is None:
+            raise DimensionMismatch(REO_EINVAL, "no expression matrix set")
+        out = np.zeros((info["G"], info["S"]), dtype=dt, order="F")
+        check(self._L.reo_get_matrix(self._h, _ptr(out), out.nbytes))
         return out
 
     # -- instrumentation -------------------------------------------------------
@@ -497,12 +541,12 @@ class Context:
                 "k2_full_launches": int(ms[9]), "k2_delta_ms": ms[10], "set_matrix_host_wall_ms": ms[11]}
 
     def info(self) -> dict:
-        v = np.zeros(24, dtype=np.int64)
-        check(self._L.reo_get_info(self._h, _ptr(v), 24))
+        v = np.zeros(25, dtype=np.int64)
+        check(self._L.reo_get_info(self._h, _ptr(v), 25))
         return {"G": int(v[0]), "S": int(v[1]), "Gp": int(v[2]), "table_bytes": int(v[3]), "has_ties": int(v[4]),
                 "tiles_owned": int(v[5]), "tiles_total": int(v[6]), "tile_i": int(v[7]), "chunk_j": int(v[8]),
                 "chunks_per_panel": int(v[9]), "unit_h": int(v[10]), "sample_slots": int(v[11]),
                 "shared_group_counts": int(v[12]), "group_count_bytes": int(v[13]), "transform_in_lds": int(v[14]), "xcc_local_histograms": int(v[15]),
                 "cycle_period": int(v[16]), "cycle_found_at_pass": int(v[17]), "cycle_passes_skipped": int(v[18]), "upload_link_bytes": int(v[19]),
                 "eager_range_launches": int(v[20]), "rowmajor_upload": int(v[21]),
-                "csc_upload": int(v[22]), "csc_nnz": int(v[23])}
+                "csc_upload": int(v[22]), "csc_nnz": int(v[23]), "resident_dtype": int(v[24])}

@@ -578,7 +578,7 @@ using namespace reo;
 
 extern "C" {
 
-int32_t reo_version(void) { return 400; }
+int32_t reo_version(void) { return 500; }
 
 int32_t reo_trim_memory(void)
 {
@@ -823,6 +823,77 @@ int32_t reo_set_matrix_csc_f64(reo_ctx *c, int64_t G, int64_t S, const int64_t *
 int32_t reo_set_matrix_csc_i64(reo_ctx *c, int64_t G, int64_t S, const int64_t *colptr, const int32_t *rowidx, const int64_t *val) { return set_matrix_csc(c, G, S, colptr, rowidx, val, 2); }
 int32_t reo_set_matrix_csc_f32(reo_ctx *c, int64_t G, int64_t S, const int64_t *colptr, const int32_t *rowidx, const float *val) { return set_matrix_csc(c, G, S, colptr, rowidx, val, 3); }
 int32_t reo_set_matrix_csc_i32(reo_ctx *c, int64_t G, int64_t S, const int64_t *colptr, const int32_t *rowidx, const int32_t *val) { return set_matrix_csc(c, G, S, colptr, rowidx, val, 4); }
+
+// Pseudo-bulk profiles as the expression matrix (include/reo_hip.h, CELLS): reo_pseudobulk_*'s sums stay in the context's own matrix.
+// Whatever fails, the context holds no matrix afterwards (the old one may already have given its buffer to the new one).
+static int32_t no_multi(reo_ctx *c, const char *what)
+{
+    if (!c) { set_error("null context"); return REO_EINVAL; }
+    if (c->in_multi) {
+        set_error("%s is not available on a reo_create_multi context (every device would need the matrix: use one process per GPU, each with its own context)", what);
+        return REO_EINVAL;
+    }
+    return REO_OK;
+}
+
+static int32_t set_matrix_pseudobulk(reo_ctx *c, bool csc, bool is_int, const void *X, int64_t G, int64_t C, int64_t ld, const int64_t *colptr,
+                                     const int32_t *rowidx, const void *val, const int32_t *order, int64_t n_order, const int32_t *chunk_ptr,
+                                     int32_t n_out)
+{
+    int32_t rc = no_multi(c, "reo_set_matrix_pseudobulk");
+    if (rc) return rc;
+    invalidate(c);
+    c->dtype = 0; c->dX = nullptr;
+    c->narrowed_bytes = 0; c->rowmajor_upload = 0; c->csc_upload = 0; c->csc_nnz = 0;
+    if ((rc = use(c)) || (rc = check_shape(G, n_out))) return rc;
+    rc = csc ? pseudobulk_resident_csc(c, is_int, G, C, colptr, rowidx, val, order, n_order, chunk_ptr, n_out)
+             : pseudobulk_resident_dense(c, X, is_int, G, C, ld, order, n_order, chunk_ptr, n_out);
+    if (rc) return rc;
+    c->narrowed_bytes = 0;   // (the cells' upload is not the matrix's)
+    c->G = G; c->S = n_out; c->ld = G; c->dX = c->dX_owned.p; c->dtype = is_int ? 2 : 1;
+    return REO_OK;
+}
+
+int32_t reo_set_matrix_pseudobulk_dense_f64(reo_ctx *c, const double *X, int64_t G, int64_t C, int64_t ld, const int32_t *order, int64_t n_order,
+                                            const int32_t *chunk_ptr, int32_t n_out)
+{ return set_matrix_pseudobulk(c, false, false, X, G, C, ld, nullptr, nullptr, nullptr, order, n_order, chunk_ptr, n_out); }
+int32_t reo_set_matrix_pseudobulk_dense_i64(reo_ctx *c, const int64_t *X, int64_t G, int64_t C, int64_t ld, const int32_t *order, int64_t n_order,
+                                            const int32_t *chunk_ptr, int32_t n_out)
+{ return set_matrix_pseudobulk(c, false, true, X, G, C, ld, nullptr, nullptr, nullptr, order, n_order, chunk_ptr, n_out); }
+int32_t reo_set_matrix_pseudobulk_csc_f64(reo_ctx *c, int64_t G, int64_t C, const int64_t *colptr, const int32_t *rowidx, const double *val,
+                                          const int32_t *order, int64_t n_order, const int32_t *chunk_ptr, int32_t n_out)
+{ return set_matrix_pseudobulk(c, true, false, nullptr, G, C, 0, colptr, rowidx, val, order, n_order, chunk_ptr, n_out); }
+int32_t reo_set_matrix_pseudobulk_csc_i64(reo_ctx *c, int64_t G, int64_t C, const int64_t *colptr, const int32_t *rowidx, const int64_t *val,
+                                          const int32_t *order, int64_t n_order, const int32_t *chunk_ptr, int32_t n_out)
+{ return set_matrix_pseudobulk(c, true, true, nullptr, G, C, 0, colptr, rowidx, val, order, n_order, chunk_ptr, n_out); }
+
+int32_t reo_filter_matrix(reo_ctx *c, int64_t min_profiles, int64_t min_features, uint8_t *profile_kept, uint8_t *gene_kept,
+                          int64_t *S_kept, int64_t *G_kept)
+{
+    int32_t rc = no_multi(c, "reo_filter_matrix");
+    if (rc || (rc = use(c))) return rc;
+    if (c->dtype == 0) { set_error("no expression matrix set"); return REO_EINVAL; }
+    invalidate(c);   // always: the rows and columns of every derived table may move
+    return filter_matrix(c, min_profiles, min_features, profile_kept, gene_kept, S_kept, G_kept);
+}
+
+int32_t reo_get_matrix(reo_ctx *c, void *out, int64_t bytes)
+{
+    int32_t rc = use(c);
+    if (rc) return rc;
+    if (!out) { set_error("null argument"); return REO_EINVAL; }
+    if (c->dtype == 0) { set_error("no expression matrix set"); return REO_EINVAL; }
+    const size_t eb = c->dtype == 3 ? 4 : 8, row = static_cast<size_t>(c->G) * eb;
+    if (bytes < 0 || static_cast<uint64_t>(bytes) != static_cast<uint64_t>(row) * static_cast<uint64_t>(c->S)) {
+        set_error("the resident matrix is %lld x %lld elements of %zu bytes, not %lld bytes", (long long)c->G, (long long)c->S, eb, (long long)bytes);
+        return REO_EINVAL;
+    }
+    DrainOnExit drain(c);
+    REO_HIP_CHECK(hipMemcpy2DAsync(out, row, c->dX, static_cast<size_t>(c->ld) * eb, row, static_cast<size_t>(c->S), hipMemcpyDeviceToHost, c->stream));
+    REO_HIP_CHECK(hipStreamSynchronize(c->stream));
+    drain.dismiss();
+    return REO_OK;
+}
 
 int32_t reo_set_groups(reo_ctx *c, const int32_t *group_id, int64_t len, int32_t ngroups)
 {
@@ -1277,13 +1348,13 @@ int32_t reo_get_timings(reo_ctx *c, double *ms, int32_t n)
 int32_t reo_get_info(reo_ctx *c, int64_t *info, int32_t n)
 {
     if (!c || !info) { set_error("null argument"); return REO_EINVAL; }
-    const int64_t v[24] = {c->G, c->S, c->Gp, static_cast<int64_t>(c->table.n * sizeof(uint32_t)), c->has_ties,
+    const int64_t v[25] = {c->G, c->S, c->Gp, static_cast<int64_t>(c->table.n * sizeof(uint32_t)), c->has_ties,
                            c->tiles_owned, c->tiles_total, kTileI, c->k1_cj, c->k1_q, kUnitH,
                            c->goff32.empty() ? 0 : c->goff32.back(), c->last_k1_shared,
                            static_cast<int64_t>(c->gcounts.n * sizeof(uint16_t)), c->transform_in_lds, c->xcc_local,
                            c->it_cycle_period, c->it_cycle_at, c->it_cycle_skipped, c->narrowed_bytes, c->eager_range_launches, c->rowmajor_upload,
-                           c->csc_upload, c->csc_nnz};
-    for (int i = 0; i < n && i < 24; ++i) info[i] = v[i];
+                           c->csc_upload, c->csc_nnz, c->dtype};
+    for (int i = 0; i < n && i < 25; ++i) info[i] = v[i];
     return REO_OK;
 }
 

@@ -104,14 +104,27 @@ __global__ __launch_bounds__(kPbThreads) void pb_csc(const int64_t *__restrict__
     for (int t = threadIdx.x; t < r1 - r0; t += kPbThreads) out[static_cast<int64_t>(o) * G + r0 + t] = acc[t];
 }
 
+// Where the G x n_out sums go: out != null -- a scratch buffer that is copied into the caller's host array (reo_pseudobulk_*); out == null --
+// the context's own matrix (reo_set_matrix_pseudobulk_*: nothing travels to the host, the caller makes it the expression matrix).
+template <class T>
+int32_t pb_destination(reo_ctx *c, int64_t G, int32_t n_out, const T *out, DevBuf<T> &scratch, T **dst)
+{
+    int32_t rc;
+    if (out) { if ((rc = scratch.ensure(static_cast<size_t>(G) * n_out))) return rc; *dst = scratch.p; return REO_OK; }
+    if ((rc = c->dX_owned.ensure(static_cast<size_t>(G) * n_out * sizeof(T)))) return rc;
+    *dst = reinterpret_cast<T *>(c->dX_owned.p);
+    return REO_OK;
+}
+
 template <class T>
 int32_t run_dense(reo_ctx *c, const T *X, int64_t G, int64_t C, int64_t ld, const int32_t *order, int64_t n_order,
                   const int32_t *chunk_ptr, int32_t n_out, T *out)
 {
     DevBuf<T> dX, dOut;
     DevBuf<int32_t> dOrd, dPtr;
+    T *dst = nullptr;
     int32_t rc;
-    if ((rc = dX.ensure(static_cast<size_t>(G) * C)) || (rc = dOut.ensure(static_cast<size_t>(G) * n_out)) ||
+    if ((rc = dX.ensure(static_cast<size_t>(G) * C)) || (rc = pb_destination(c, G, n_out, out, dOut, &dst)) ||
         (rc = dOrd.ensure(std::max<int64_t>(n_order, 1))) || (rc = dPtr.ensure(n_out + 1)))
         return rc;
     struct Drain {   // no exit leaves a copy from or into the caller's arrays in flight
@@ -125,11 +138,11 @@ int32_t run_dense(reo_ctx *c, const T *X, int64_t G, int64_t C, int64_t ld, cons
     if (e == hipSuccess) e = hipMemcpyAsync(dPtr.p, chunk_ptr, (n_out + 1) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
         tic(c, 7);
-        pb_dense<T><<<dim3(static_cast<unsigned>((G + 255) / 256), n_out), 256, 0, c->stream>>>(dX.p, G, static_cast<int>(G), dOrd.p, dPtr.p, dOut.p);
+        pb_dense<T><<<dim3(static_cast<unsigned>((G + 255) / 256), n_out), 256, 0, c->stream>>>(dX.p, G, static_cast<int>(G), dOrd.p, dPtr.p, dst);
         toc(c);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, dOut.p, static_cast<size_t>(G) * n_out * sizeof(T), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && out) e = hipMemcpyAsync(out, dst, static_cast<size_t>(G) * n_out * sizeof(T), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) (void)hipStreamSynchronize(c->stream);   // nothing queued reads or writes the caller's arrays (or these buffers) after return
     dX.release(); dOut.release(); dOrd.release(); dPtr.release();
@@ -164,9 +177,10 @@ int32_t run_csc(reo_ctx *c, int64_t G, int64_t C, const int64_t *colptr, const i
     DevBuf<int64_t> dCp;
     DevBuf<int32_t> dRi, dOrd, dPtr;
     DevBuf<T> dVal, dOut;
+    T *dst = nullptr;
     int32_t rc;
     if ((rc = dCp.ensure(C + 1)) || (rc = dRi.ensure(std::max<int64_t>(nnz, 1))) || (rc = dVal.ensure(std::max<int64_t>(nnz, 1))) ||
-        (rc = dOut.ensure(static_cast<size_t>(G) * n_out)) || (rc = dOrd.ensure(std::max<int64_t>(n_order, 1))) ||
+        (rc = pb_destination(c, G, n_out, out, dOut, &dst)) || (rc = dOrd.ensure(std::max<int64_t>(n_order, 1))) ||
         (rc = dPtr.ensure(n_out + 1)))
         return rc;
     struct Drain {   // no exit leaves a copy from or into the caller's arrays in flight
@@ -250,11 +264,11 @@ int32_t run_csc(reo_ctx *c, int64_t G, int64_t C, const int64_t *colptr, const i
     if (e == hipSuccess) {
         tic(c, 7);
         pb_csc<T><<<dim3(n_out, static_cast<unsigned>((G + kPbRows - 1) / kPbRows)), kPbThreads, 0, c->stream>>>(
-            dCp.p, dRi.p, dVal.p, static_cast<int>(G), dOrd.p, dPtr.p, dOut.p);
+            dCp.p, dRi.p, dVal.p, static_cast<int>(G), dOrd.p, dPtr.p, dst);
         toc(c);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, dOut.p, static_cast<size_t>(G) * n_out * sizeof(T), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && out) e = hipMemcpyAsync(out, dst, static_cast<size_t>(G) * n_out * sizeof(T), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) { set_error("pseudobulk (CSC) failed: %s", hipGetErrorString(e)); return e == hipErrorOutOfMemory ? REO_ENOMEM : REO_EHIP; }
     collect_timings(c);
@@ -262,9 +276,9 @@ int32_t run_csc(reo_ctx *c, int64_t G, int64_t C, const int64_t *colptr, const i
 }
 
 int32_t check_args(reo_ctx *c, int64_t G, int64_t C, const int32_t *order, int64_t n_order, const int32_t *chunk_ptr,
-                   int32_t n_out, const void *in, const void *out)
+                   int32_t n_out, const void *in, const void *out, bool resident = false)
 {
-    if (!c || !in || !out || !chunk_ptr || (n_order > 0 && !order)) { set_error("null argument"); return REO_EINVAL; }
+    if (!c || !in || (!out && !resident) || !chunk_ptr || (n_order > 0 && !order)) { set_error("null argument"); return REO_EINVAL; }
     if (G < 1 || C < 1 || n_out < 1 || n_order < 0) { set_error("bad pseudobulk shape"); return REO_EINVAL; }
     if (chunk_ptr[0] != 0 || chunk_ptr[n_out] != n_order) { set_error("chunk_ptr must run from 0 to n_order"); return REO_EINVAL; }
     for (int o = 0; o < n_out; ++o)
@@ -276,6 +290,37 @@ int32_t check_args(reo_ctx *c, int64_t G, int64_t C, const int32_t *order, int64
 }
 
 }  // namespace
+
+static int32_t check_csc(int64_t G, int64_t C, const int64_t *colptr, const int32_t *rowidx)
+{
+    if (!colptr || colptr[0] != 0) { set_error("colptr must start at 0"); return REO_EINVAL; }
+    for (int64_t k = 0; k < C; ++k)
+        if (colptr[k + 1] < colptr[k]) { set_error("colptr must be non-decreasing"); return REO_EINVAL; }
+    if (colptr[C] > 0 && !rowidx) { set_error("rowidx is null"); return REO_EINVAL; }
+    (void)G;   // (the row indices are checked chunk by chunk while they are narrowed for the upload: run_csc)
+    return REO_OK;
+}
+
+// The resident forms (api.hip, reo_set_matrix_pseudobulk_*): the checks, the upload and the kernels of reo_pseudobulk_*, the sums written
+// into c->dX_owned (G x n_out, ld = G).  The caller does the context's bookkeeping.
+int32_t pseudobulk_resident_dense(reo_ctx *c, const void *X, bool is_int, int64_t G, int64_t C, int64_t ld, const int32_t *order,
+                                  int64_t n_order, const int32_t *chunk_ptr, int32_t n_out)
+{
+    int32_t rc = check_args(c, G, C, order, n_order, chunk_ptr, n_out, X, nullptr, true);
+    if (rc) return rc;
+    if (ld < G) { set_error("leading dimension < G"); return REO_EINVAL; }
+    if (is_int) return run_dense<long long>(c, static_cast<const long long *>(X), G, C, ld, order, n_order, chunk_ptr, n_out, nullptr);
+    return run_dense<double>(c, static_cast<const double *>(X), G, C, ld, order, n_order, chunk_ptr, n_out, nullptr);
+}
+
+int32_t pseudobulk_resident_csc(reo_ctx *c, bool is_int, int64_t G, int64_t C, const int64_t *colptr, const int32_t *rowidx, const void *val,
+                                const int32_t *order, int64_t n_order, const int32_t *chunk_ptr, int32_t n_out)
+{
+    int32_t rc = check_args(c, G, C, order, n_order, chunk_ptr, n_out, colptr, nullptr, true);
+    if (rc || (rc = check_csc(G, C, colptr, rowidx))) return rc;
+    if (is_int) return run_csc<long long>(c, G, C, colptr, rowidx, static_cast<const long long *>(val), order, n_order, chunk_ptr, n_out, nullptr);
+    return run_csc<double>(c, G, C, colptr, rowidx, static_cast<const double *>(val), order, n_order, chunk_ptr, n_out, nullptr);
+}
 
 }  // namespace reo
 
@@ -300,16 +345,6 @@ int32_t reo_pseudobulk_dense_i64(reo_ctx *c, const int64_t *X, int64_t G, int64_
     if (ld < G) { set_error("leading dimension < G"); return REO_EINVAL; }
     return run_dense<long long>(c, reinterpret_cast<const long long *>(X), G, C, ld, order, n_order, chunk_ptr, n_out,
                                 reinterpret_cast<long long *>(out));
-}
-
-static int32_t check_csc(int64_t G, int64_t C, const int64_t *colptr, const int32_t *rowidx)
-{
-    if (!colptr || colptr[0] != 0) { set_error("colptr must start at 0"); return REO_EINVAL; }
-    for (int64_t k = 0; k < C; ++k)
-        if (colptr[k + 1] < colptr[k]) { set_error("colptr must be non-decreasing"); return REO_EINVAL; }
-    if (colptr[C] > 0 && !rowidx) { set_error("rowidx is null"); return REO_EINVAL; }
-    (void)G;   // (the row indices are checked chunk by chunk while they are narrowed for the upload: run_csc)
-    return REO_OK;
 }
 
 int32_t reo_pseudobulk_csc_f64(reo_ctx *c, int64_t G, int64_t C, const int64_t *colptr, const int32_t *rowidx,

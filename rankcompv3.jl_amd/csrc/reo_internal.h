@@ -378,6 +378,15 @@ int32_t light_min_genes();
 int32_t light_window();
 int32_t launch_mccullagh(reo_ctx *c, const int32_t *d_cont, int64_t n, double *d_out);
 
+// pseudobulk.hip: the checks, upload and kernels of reo_pseudobulk_*, the G x n_out sums left in c->dX_owned (ld = G) instead of a host array
+int32_t pseudobulk_resident_dense(reo_ctx *c, const void *X, bool is_int, int64_t G, int64_t C, int64_t ld, const int32_t *order,
+                                  int64_t n_order, const int32_t *chunk_ptr, int32_t n_out);
+int32_t pseudobulk_resident_csc(reo_ctx *c, bool is_int, int64_t G, int64_t C, const int64_t *colptr, const int32_t *rowidx, const void *val,
+                                const int32_t *order, int64_t n_order, const int32_t *chunk_ptr, int32_t n_out);
+// filter.hip: the low-expression filters and the compaction of the resident matrix (reo_filter_matrix; host half: filter_maps.h)
+int32_t filter_matrix(reo_ctx *c, int64_t min_profiles, int64_t min_features, uint8_t *profile_kept, uint8_t *gene_kept,
+                      int64_t *S_kept, int64_t *G_kept);
+
 // comm.hip: in-library RCCL.  Returns REO_OK after enqueueing the sum on c->stream, 1 when no communicator is attached
 int32_t comm_allgather(reo_ctx *c, const void *send, void *recv, int64_t bytes_per_rank, hipStream_t st = nullptr);
 void comm_release(reo_ctx *c);

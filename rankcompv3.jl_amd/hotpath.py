@@ -10,10 +10,11 @@ in Julia.
 from __future__ import annotations
 
 from dataclasses import dataclass, field
+from typing import NamedTuple
 
 import numpy as np
 
-from . import _ffi
+from . import _ffi, synth
 
 HEADER = ["pval", "padj", "n11", "n12", "n13", "n21", "n22", "n23", "n31", "n32", "n33",
           "Δ1", "Δ2", "se", "z1", "up_down"]  # src/RankCompV3.jl:665
@@ -127,6 +128,83 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
     first = comps[0]
     return DegRun(result=first["result"], labels=first["labels"], levels=levels, thresholds=thr, iters_run=first["iters_run"],
                   trace=first["trace"], timings=timings, info=info, comparisons=comps, gene_names=list(gene_names))
+
+
+def cells_partition(cell_group, n_pseudo: int, seed: int = 0):
+    """The pseudo-bulk plan of a cell matrix whose column t belongs to group cell_group[t] (src/RankCompV3.jl:608-612), pure numpy: the
+    groups in order of first appearance, the cells of a group in column order, each group cut by reoa.pseudobulk_partition(c, n_pseudo,
+    seed, gi) -- the reference's shuffled chunks of ceil(c / n_pseudo) cells (:60-62) -- and the pieces concatenated.  Returns (order,
+    chunk_ptr, profile names `<g>_x<k>`, profile groups): what Context.pseudobulk / set_matrix_pseudobulk take, and what reoa.prepare
+    builds from its tables."""
+    from .reoa import pseudobulk_partition
+    gid, levels = encode_groups(cell_group)
+    orders, ptr, names, groups = [], [0], [], []
+    for gi, g in enumerate(levels):
+        cols = np.flatnonzero(gid == gi)
+        o, p = pseudobulk_partition(cols.size, n_pseudo, seed, gi)
+        orders.append(cols[o])
+        ptr += (p[1:].astype(np.int64) + ptr[-1]).tolist()
+        names += [f"{g}_x{k + 1}" for k in range(len(p) - 1)]
+        groups += [g] * (len(p) - 1)
+    order = np.concatenate(orders).astype(np.int32) if orders else np.zeros(0, dtype=np.int32)
+    return order, np.asarray(ptr, dtype=np.int32), names, groups
+
+
+class CellsDegRun(NamedTuple):
+    """identify_degs_cells: the DegRun of the pseudo-bulk profiles and what the filters kept."""
+    run: DegRun
+    gene_kept: np.ndarray        # bool over the input genes; run.gene_names are the kept ones
+    profile_kept: np.ndarray     # bool over the pseudo-bulk profiles cells_partition made
+    profile_names: list          # `<g>_x<k>` of the kept profiles (the columns of the matrix that was analysed)
+    profile_groups: list         # their groups
+
+
+def identify_degs_cells(cells, cell_group, gene_names, n_pseudo, pval_reo, pval_deg, padj_deg, ref_gene, n_iter, n_conv, *,
+                        min_profiles: int = 0, min_features: int = 0, ref_gene_max: int = 3000, seed: int = 0, device: int = 0,
+                        profile: bool = False) -> CellsDegRun:
+    """Cells to DEGs without a host trip for the profiles: `cells` is a genes x cells matrix (scipy.sparse or anything np.asarray takes),
+    cell_group one label per cell.  cells_partition -> the pseudo-bulk sums written into the context's matrix (set_matrix_pseudobulk) ->
+    the reference's two low-expression filters on the device (filter_matrix, :618 / :626) -> groups of the kept profiles, thresholds,
+    pair table and iteration as in run_identify_degs.  ref_gene is a bool mask over the INPUT genes (subset by gene_kept here), or None for
+    synth.ref_mask(G', min(G', ref_gene_max), seed), the draw reoa makes.  Bit-identical to Context.pseudobulk -> numpy filters ->
+    run_identify_degs on the same seed.  (reoa() keeps its host route: its writers want the profile matrix on the host.)"""
+    if not _ffi.is_sparse(cells):
+        cells = np.asarray(cells)
+    if len(cells.shape) != 2:
+        raise _ffi.DimensionMismatch(_ffi.REO_EINVAL, "'cells' must be a genes x cells matrix")
+    r, ncell = cells.shape
+    if ncell != len(cell_group):
+        raise _ffi.DimensionMismatch(_ffi.REO_EINVAL, "'cells' and 'cell_group' do not have compatible sizes")
+    if len(gene_names) != r or (ref_gene is not None and len(ref_gene) != r):
+        raise _ffi.DimensionMismatch(_ffi.REO_EINVAL, "gene_names / ref_gene length != number of rows of 'cells'")
+    if n_pseudo < 1:
+        raise _ffi.DimensionMismatch(_ffi.REO_EINVAL, "n_pseudo must be at least 1")
+    order, chunk_ptr, names, groups = cells_partition(cell_group, n_pseudo, seed)
+    comps = []
+    with _ffi.Context(device=device, seed=seed) as ctx:
+        ctx.set_profiling(profile)
+        ctx.set_matrix_pseudobulk(cells, order, chunk_ptr)
+        profile_kept, gene_kept = ctx.filter_matrix(min_profiles, min_features)
+        names = [n for n, k in zip(names, profile_kept) if k]
+        groups = [g for g, k in zip(groups, profile_kept) if k]
+        kept_genes = [n for n, k in zip(gene_names, gene_kept) if k]
+        gid, levels = encode_groups(groups)
+        if len(levels) < 2:  # :356
+            raise _ffi.DimensionMismatch(_ffi.REO_EINVAL, "Only 1 level in 'group1, at least 2 levels!")
+        G = len(kept_genes)
+        ref = synth.ref_mask(G, min(G, ref_gene_max), seed) if ref_gene is None else np.asarray(ref_gene, dtype=bool)[gene_kept]
+        ctx.set_groups(gid, len(levels))
+        thr = ctx.compute_thresholds(pval_reo)
+        for k in range(1 if len(levels) == 2 else len(levels)):
+            ctx.build_pairs(k)
+            result, iters, trace = ctx.identify_degs(ref, pval_deg, padj_deg, n_iter, n_conv)
+            comps.append({"k": k, "result": result, "labels": label_genes(result, pval_deg, padj_deg), "iters_run": iters, "trace": trace})
+        timings = ctx.timings() if profile else {}
+        info = ctx.info()
+    first = comps[0]
+    run = DegRun(result=first["result"], labels=first["labels"], levels=levels, thresholds=thr, iters_run=first["iters_run"],
+                 trace=first["trace"], timings=timings, info=info, comparisons=comps, gene_names=kept_genes)
+    return CellsDegRun(run, gene_kept, profile_kept, names, groups)
 
 
 def identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref_gene, n_iter, n_conv, **kw) -> np.ndarray:
