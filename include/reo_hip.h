@@ -372,7 +372,9 @@ int32_t reo_get_timings(reo_ctx *ctx, double *ms, int32_t n);
  * launches whole sides only, as in round 5; 2..6 asks for that many ranges per side; default: by the number of blocks), 21 the last
  * host matrix was read row-major in place (reo_set_matrix_rm_*: 1; every other reo_set_matrix_*: 0), 22 the last host matrix came as CSC
  * (reo_set_matrix_csc_*: 1; every other reo_set_matrix_*: 0), 23 the stored entries (nnz) of that CSC matrix, 24 the element type of the
- * resident matrix (0 none, 1 Float64, 2 Int64 -- Int32 input is widened --, 3 Float32). */
+ * resident matrix (0 none, 1 Float64, 2 Int64 -- Int32 input is widened --, 3 Float32), 25 the last class table was built with the genes
+ * in slot order (tie-free data of two groups on one shard; REO_K1_SLOTS=0 switches it off; the table is the same bit for bit), 26 the
+ * half-height tiles of that build whose count loop was skipped (counted when asked for, n > 26: one small kernel and a wait). */
 int32_t reo_get_info(reo_ctx *ctx, int64_t *info, int32_t n);
 
 #ifdef __cplusplus

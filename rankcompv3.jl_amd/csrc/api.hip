@@ -350,6 +350,9 @@ static void invalidate(reo_ctx *c)
     c->built_k = -1;
     c->gc_valid = false;
     c->eager_k1 = false;
+    // no class table any more: nothing is left of a build in slot order either (reo_get_info 25, 26 read 0; the maps and the item list that
+    // field 26 would count over belong to the old geometry)
+    c->last_k1_slots = 0; c->k1_slot_items = nullptr; c->k1_slot_items_n = 0; c->k1_slot_gp = 0;
 }
 
 // dtype: what the caller hands over -- 1 Float64, 2 Int64, 3 Float32, 4 Int32 (which becomes a resident Int64 matrix: its tie is equality)
@@ -635,6 +638,7 @@ int32_t reo_create(reo_ctx **out, int32_t device, uint64_t seed)
     c->seed = seed;
     if (const char *e = getenv("REO_K1_WAVE")) c->k1_wave = (e[0] != '0');
     if (const char *e = getenv("REO_K1_HALF")) c->k1_half = (e[0] != '0');
+    if (const char *e = getenv("REO_K1_SLOTS")) c->k1_slots = (e[0] != '0');
     if (const char *e = getenv("REO_K1_ORDER")) c->k1_order = std::max(0, std::min(2, atoi(e)));
     {
         int n = 0;
@@ -719,6 +723,7 @@ void reo_destroy(reo_ctx *c)
     release_event(c->ev_x, 0);
     for (auto &e : c->ev_k1) release_event(e, 0);
     c->t_pos16.release(); c->t_lo16.release(); c->t_hi16.release(); c->gcounts.release();
+    c->k1_slot_part.release(); c->k1_slot_maps.release(); c->pos_s.release(); c->lo_s.release();
     c->t_pos32.release(); c->t_lo32.release(); c->t_hi32.release(); c->t_vin32.release(); c->t_vout32.release();
     for (int t = 0; t < 2; ++t) { c->refbits[t].release(); c->refbytes[t].release(); }
     c->raw.release(); c->delta_list.release(); c->cont.release(); c->result.release(); c->sorted_d.release(); c->sorted_p.release();
@@ -1348,13 +1353,18 @@ int32_t reo_get_timings(reo_ctx *c, double *ms, int32_t n)
 int32_t reo_get_info(reo_ctx *c, int64_t *info, int32_t n)
 {
     if (!c || !info) { set_error("null argument"); return REO_EINVAL; }
-    const int64_t v[25] = {c->G, c->S, c->Gp, static_cast<int64_t>(c->table.n * sizeof(uint32_t)), c->has_ties,
+    int64_t separated = 0;
+    if (n > 26 && c->last_k1_slots) {   // (counted when asked for: nothing of it is on the pair kernel's path)
+        int32_t rc = use(c);
+        if (rc || (rc = launch_slot_separated(c, &separated))) return rc;
+    }
+    const int64_t v[27] = {c->G, c->S, c->Gp, static_cast<int64_t>(c->table.n * sizeof(uint32_t)), c->has_ties,
                            c->tiles_owned, c->tiles_total, kTileI, c->k1_cj, c->k1_q, kUnitH,
                            c->goff32.empty() ? 0 : c->goff32.back(), c->last_k1_shared,
                            static_cast<int64_t>(c->gcounts.n * sizeof(uint16_t)), c->transform_in_lds, c->xcc_local,
                            c->it_cycle_period, c->it_cycle_at, c->it_cycle_skipped, c->narrowed_bytes, c->eager_range_launches, c->rowmajor_upload,
-                           c->csc_upload, c->csc_nnz, c->dtype};
-    for (int i = 0; i < n && i < 25; ++i) info[i] = v[i];
+                           c->csc_upload, c->csc_nnz, c->dtype, c->last_k1_slots, separated};
+    for (int i = 0; i < n && i < 27; ++i) info[i] = v[i];
     return REO_OK;
 }
 

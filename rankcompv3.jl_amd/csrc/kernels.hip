@@ -46,6 +46,7 @@
 
 #include "reo_internal.h"
 #include "k1_items.h"
+#include "k1_slots.h"
 
 namespace reo {
 
@@ -271,6 +272,10 @@ struct K1Args {
     uint32_t *park;              // [items][kParkSlot], or null
     int32_t *park_ge;            // [items]: the slot's n_ge half is valid (the tie form stored it; else n_ge = n_gt: no tie in those samples)
     int park_mode;               // bit 0: add the parked counts of the blocks before this range; bit 1: park the sums instead of classifying
+    // SLOT ORDER (k1w_pairs_slots; k1_slots.h): P and AL are then the planes in slot order, every index of the kernel is a slot, and
+    // only the table's ROW is looked up (s2g); the columns come back in gene order afterwards (k1_unslot_columns).  Else null.
+    const uint32_t *s2g;         // [Gp] slot -> gene
+    const uint32_t *trng, *crng; // [2 sides][Gp / 32], [2 sides][Gp / 256]: position ranges (min | max << 16) of the i-tiles and wave chunks
 };
 constexpr size_t kParkSlot = 2 * 64 * 64;   // words per item: 64 count registers x 64 lanes, twice (32 KB)
 
@@ -322,7 +327,7 @@ __device__ __forceinline__ void emit_rows(bool near, int d, unsigned long long l
     }
 }
 
-template <int RI, bool SPLIT, typename F>
+template <int RI, bool SPLIT, bool SLOTS = false, typename F>
 __device__ __forceinline__ void emit_gene(const K1Args &a, int i0, int j, int bi, int lane, int pl, int hi_thr, int lo_thr, F val)
 {
     const int bj = __builtin_amdgcn_readfirstlane(j >> 6);  // wave-uniform, and the compiler should know it
@@ -340,7 +345,8 @@ __device__ __forceinline__ void emit_gene(const K1Args &a, int i0, int j, int bi
     else emit_rows<RI, 0>(near, d, lanes_ok, hi_thr, lo_thr, wL, wH, fLlo, fLhi, fHlo, fHhi, val);
     const bool diag = (bj == bi);
     if (lane < RI && i0 + lane < a.G) {
-        uint32_t *row = a.table + (static_cast<size_t>(i0 + lane) * kPlanes + pl) * a.Wp + 2 * bj;
+        const size_t gi = SLOTS ? a.s2g[i0 + lane] : static_cast<size_t>(i0 + lane);   // (slot order: the row of the gene in that slot)
+        uint32_t *row = a.table + (gi * kPlanes + pl) * a.Wp + 2 * bj;
         if (!diag) {
             *reinterpret_cast<uint2 *>(row) = uint2{fLlo, fLhi};
             *reinterpret_cast<uint2 *>(row + a.Wp) = uint2{fHlo, fHhi};
@@ -352,7 +358,8 @@ __device__ __forceinline__ void emit_gene(const K1Args &a, int i0, int j, int bi
         }
     }
     if (j < a.G) {  // mirror: pair (j, i) is in state 2 - state(i, j)
-        uint32_t *row = a.table + (static_cast<size_t>(j) * kPlanes + pl) * a.Wp + (i0 >> 5);
+        const size_t gj = SLOTS ? a.s2g[j] : static_cast<size_t>(j);
+        uint32_t *row = a.table + (gj * kPlanes + pl) * a.Wp + (i0 >> 5);
         if (RI == 16) {  // a half-height item owns one 16-bit half of the word (the other half: its twin, or nobody)
             const int half = (i0 >> 4) & 1;
             if (!diag) {
@@ -500,7 +507,10 @@ __device__ __forceinline__ void k1_loop(u32x8 &c0, u32x8 &c1, u32x8 &c2, u32x8 &
 
 // One item of k1w_pairs: RI = 32 gene rows from i0, or a half-height item of 16 (the items of a launch's last, partly filled
 // round are dealt as two halves each, launch_k1: the launch then ends half an item's time earlier).
-template <int NB, bool TIES, int RI>
+// SLOTS (tie-free data in slot order, k1_slots.h): an item whose i-tile and wave chunk are SEPARATED on its side -- every column gene
+// below every row gene in every sample, or above -- has the same count everywhere, the side's size or 0: the count loop is not
+// entered and the constants are classified like any other counts.
+template <int NB, bool TIES, int RI, bool SLOTS = false>
 __device__ __forceinline__ void k1w_item(const K1Args &a, uint4 *ring, int i0, int jw, int side, unsigned long long t_begin)
 {
     constexpr int RJ = kRJ, NE = TIES ? 2 : 1;
@@ -519,7 +529,12 @@ __device__ __forceinline__ void k1w_item(const K1Args &a, uint4 *ring, int i0, i
     Counts ge0 = 0, ge1 = 0, ge2 = 0, ge3 = 0;
     unsigned long long t_loop = 0, t_emit = 0;
     if (a.stamps) t_loop = __builtin_amdgcn_s_memrealtime();
-    if (be > bb) {
+    int sep = 0;   // wave-uniform: two scalar loads (a half-height item: its 32-row tile's range)
+    if constexpr (SLOTS) sep = __builtin_amdgcn_readfirstlane(slot_separated(a.trng[side * (a.Gp >> 5) + (i0 >> 5)], a.crng[side * (a.Gp >> 8) + (jw >> 8)]));
+    if (SLOTS && sep) {
+        const uint32_t ns = static_cast<uint32_t>(side ? a.nt : a.nc), v = sep > 0 ? (ns | ns << 16) : 0u;
+        gt0 = v; gt1 = v; gt2 = v; gt3 = v;
+    } else if (be > bb) {
         const char *pb = reinterpret_cast<const char *>(a.P) + static_cast<size_t>(bb) * LQ * a.Gp * 16;
         const size_t aoff = (static_cast<size_t>(bb) * a.Gp + i0) * ROWB;
         const uint32_t lds = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(ring));
@@ -590,7 +605,7 @@ __device__ __forceinline__ void k1w_item(const K1Args &a, uint4 *ring, int i0, i
 #pragma unroll
             for (int h = 0; h < RI / 2; ++h) cge[h] = park[r * (RI / 2) + h];  // (dynamic r: the array stays in memory)
         }
-        emit_gene<RI, true>(a, i0, jl + 64 * r, bi, lane, side ? 2 : 0, m, n - m, [&](int ii) {
+        emit_gene<RI, true, SLOTS>(a, i0, jl + 64 * r, bi, lane, side ? 2 : 0, m, n - m, [&](int ii) {
             const uint32_t w = cur[ii >> 1];
             int nre = static_cast<int>((ii & 1) ? (w >> 16) : (w & 0xFFFFu));
             if (TIES) {  // tie coins (:72-77): n = n_gt + Binomial(n_eq, 1/2) lies in [n_gt, n_ge].  The coins are drawn only
@@ -619,7 +634,7 @@ __device__ __forceinline__ void k1w_item(const K1Args &a, uint4 *ring, int i0, i
 // bit op -- the round-2 form, whose LDS pipe was busy 45 % of the cycles.
 // More than 65 535 genes (NB = 17, 18): the big plane layout of transform.hip (five pos quads per gene and block, edge
 // rows of 8 uint4), 180 registers, two waves per SIMD.
-template <int NB, bool TIES>
+template <int NB, bool TIES, bool SLOTS = false>
 __device__ __forceinline__ void k1w_body(const K1Args &a, uint4 *ring)
 {
     constexpr int RI = kTileI, RJ = kRJ;
@@ -631,9 +646,9 @@ __device__ __forceinline__ void k1w_body(const K1Args &a, uint4 *ring)
     const int tile0 = static_cast<int>(item & 0x3FFFu) * RI;
     if (__builtin_amdgcn_readfirstlane(static_cast<int>(item & 0x8000u))) {
         const int i0 = __builtin_amdgcn_readfirstlane(tile0 + ((item & 0x4000u) ? RI / 2 : 0));
-        k1w_item<NB, TIES, RI / 2>(a, ring, i0, jw, side, t_begin);
+        k1w_item<NB, TIES, RI / 2, SLOTS>(a, ring, i0, jw, side, t_begin);
     } else {
-        k1w_item<NB, TIES, RI>(a, ring, __builtin_amdgcn_readfirstlane(tile0), jw, side, t_begin);
+        k1w_item<NB, TIES, RI, SLOTS>(a, ring, __builtin_amdgcn_readfirstlane(tile0), jw, side, t_begin);
     }
 }
 
@@ -644,6 +659,181 @@ __global__ __launch_bounds__(64, NB > 16 ? 2 : 3) void k1w_pairs(K1Args a)
     constexpr int ROWB = NB > 16 ? 128 : 64;
     __shared__ uint4 ring[2 * RI * ROWB / 16];  // two slots of one block's tile operand: 2 x 2 KB (4 KB)
     k1w_body<NB, TIES>(a, ring);
+}
+
+// The tie-free form in SLOT ORDER (at most 65 535 genes): its own instantiation, so that the identity order's code does not change.
+template <int NB>
+__global__ __launch_bounds__(64, 3) void k1w_pairs_slots(K1Args a)
+{
+    static_assert(NB <= 16, "slot order: 16-bit positions");
+    __shared__ uint4 ring[2 * kTileI * 64 / 16];
+    k1w_body<NB, false, true>(a, ring);
+}
+
+// ---- slot order: the small kernels around the pair kernel (launch_k1 -> k1_slots; the rules: k1_slots.h)
+constexpr int kSlotSplits = 16;    // slices of a side's samples in k1_slot_part
+constexpr int kSlotRankSpan = 2048;  // genes g' that one workgroup of k1_slot_rank compares its 256 genes with
+
+// the position range of gene g on side z over slice y of the side's REAL sample slots (the first n of them from slot s0; padding slots
+// hold zeros and must not enter): part[y][z][g] = min | max << 16
+__global__ __launch_bounds__(256) void k1_slot_part(const uint16_t *__restrict__ pos16, int Gp, int G, int s0a, int na, int s0b, int nb, uint32_t *__restrict__ part)
+{
+    const int g = blockIdx.x * 256 + threadIdx.x, split = blockIdx.y, side = blockIdx.z;
+    if (g >= G) return;
+    const int s0 = side ? s0b : s0a, n = side ? nb : na;
+    const int per = (n + kSlotSplits - 1) / kSlotSplits;
+    const int b = min(n, split * per), e = min(n, b + per);
+    uint32_t mn = kSlotNoMin, mx = kSlotNoMax;
+#pragma unroll 4
+    for (int s = b; s < e; ++s) {
+        const uint32_t v = pos16[static_cast<size_t>(s0 + s) * Gp + g];
+        mn = min(mn, v); mx = max(mx, v);
+    }
+    part[(static_cast<size_t>(split) * 2 + side) * Gp + g] = slot_pack(mn, mx);
+}
+
+// ... joined over the slices: gmm[side][g], and the gene's key
+__global__ __launch_bounds__(256) void k1_slot_keys(const uint32_t *__restrict__ part, int Gp, int G, uint32_t *__restrict__ gmm, uint32_t *__restrict__ key)
+{
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= G) return;
+    uint32_t r0 = slot_pack(kSlotNoMin, kSlotNoMax), r1 = r0;
+#pragma unroll
+    for (int y = 0; y < kSlotSplits; ++y) {
+        r0 = slot_join(r0, part[(static_cast<size_t>(y) * 2) * Gp + g]);
+        r1 = slot_join(r1, part[(static_cast<size_t>(y) * 2 + 1) * Gp + g]);
+    }
+    gmm[g] = r0; gmm[Gp + g] = r1;
+    key[g] = slot_key(r0, r1);
+}
+
+// g2s[g] += the number of genes g' of span y with (key, g') < (key, g)   (g2s cleared by the host: a counting rank, G^2 comparisons)
+__global__ __launch_bounds__(256) void k1_slot_rank(const uint32_t *__restrict__ key, int G, uint32_t *__restrict__ g2s)
+{
+    __shared__ uint64_t sk[kSlotRankSpan];
+    const int h0 = blockIdx.y * kSlotRankSpan;
+    for (int t = threadIdx.x; t < kSlotRankSpan; t += 256)
+        sk[t] = h0 + t < G ? slot_order_key(key[h0 + t], static_cast<uint32_t>(h0 + t)) : ~0ull;   // (beyond the genes: below nobody)
+    __syncthreads();
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= G) return;
+    const uint64_t mine = slot_order_key(key[g], static_cast<uint32_t>(g));
+    uint32_t n = 0;
+#pragma unroll 8
+    for (int t = 0; t < kSlotRankSpan; ++t) n += sk[t] < mine ? 1u : 0u;   // broadcast reads
+    if (n) atomicAdd(&g2s[g], n);
+}
+
+// s2g from g2s; padding slots map to themselves
+__global__ __launch_bounds__(256) void k1_slot_invert(uint32_t *__restrict__ g2s, uint32_t *__restrict__ s2g, int G, int Gp)
+{
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= Gp) return;
+    if (g < G) { const uint32_t k = g2s[g]; if (k < static_cast<uint32_t>(G)) s2g[k] = static_cast<uint32_t>(g); }   // (k < G always: a rank among G genes)
+    else { g2s[g] = static_cast<uint32_t>(g); s2g[g] = static_cast<uint32_t>(g); }
+}
+
+// the position ranges of the i-tiles (32 slots) and wave chunks (256 slots) of side y, over their slots below G
+__global__ __launch_bounds__(256) void k1_slot_ranges(const uint32_t *__restrict__ gmm, const uint32_t *__restrict__ s2g, int G, int Gp,
+                                                      uint32_t *__restrict__ trng, uint32_t *__restrict__ crng)
+{
+    static_assert(kSlotTile == kTileI && kSlotChunk == 64 * kRJ, "k1_slots.h carries its own copy of the item geometry");
+    __shared__ uint32_t sm[8];
+    const int k = blockIdx.x * 256 + threadIdx.x, side = blockIdx.y;   // (Gp is a multiple of 1024: every thread has a slot)
+    uint32_t r = k < G ? gmm[static_cast<size_t>(side) * Gp + s2g[k]] : slot_pack(kSlotNoMin, kSlotNoMax);
+#pragma unroll
+    for (int o = 1; o < 32; o <<= 1) r = slot_join(r, static_cast<uint32_t>(__shfl_xor(static_cast<int>(r), o)));
+    if ((threadIdx.x & 31) == 0) { trng[static_cast<size_t>(side) * (Gp >> 5) + (k >> 5)] = r; sm[threadIdx.x >> 5] = r; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int q = 1; q < 8; ++q) r = slot_join(r, sm[q]);
+        crng[static_cast<size_t>(side) * (Gp >> 8) + blockIdx.x] = r;
+    }
+}
+
+// the planes of sample block y in slot order: Ps[(b 4 + q) Gp + k] = P[(b 4 + q) Gp + s2g[k]] (16 bytes each), and the 64-byte
+// records ALs[b Gp + k] = AL[b Gp + s2g[k]], four threads per record
+__global__ __launch_bounds__(256) void k1_slot_gather(const uint4 *__restrict__ P, const uint4 *__restrict__ AL, const uint32_t *__restrict__ s2g, int Gp,
+                                                      uint4 *__restrict__ Ps, uint4 *__restrict__ ALs)
+{
+    const int k = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
+    const uint32_t g = s2g[k];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) Ps[(static_cast<size_t>(b) * 4 + q) * Gp + k] = P[(static_cast<size_t>(b) * 4 + q) * Gp + g];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int kk = blockIdx.x * 256 + e * 64 + (threadIdx.x >> 2), q = threadIdx.x & 3;
+        ALs[(static_cast<size_t>(b) * Gp + kk) * 4 + q] = AL[(static_cast<size_t>(b) * Gp + s2g[kk]) * 4 + q];
+    }
+}
+
+// The table's columns back into gene order, in place: rows r0 .. r0 + nr - 1 of the table (whole rows: four planes of Wp words) go
+// into LDS as one uint4 per word index (the four planes side by side), then bit j of every (row, plane) = bit g2s[j] of what was
+// there, columns from G on zero.  A THREAD makes whole words: for each of its word's 32 columns it takes g2s[j] (eight 16-byte loads,
+// once for all R rows), and per row one 16-byte LDS read gives the four planes' words, out of which a shift and a funnel shift move
+// the bit into each plane's new word; the words of a bit row leave as coalesced 4-byte stores.  (The first form made 64 bits per
+// ballot, one lane per column: 25 instructions per row and 64 columns, 0.95 ms at config 3,
+// profiles/slots_kernel_stats_ballot_unslot.csv; this one 0.46 ms.)  Dynamic LDS = R x Wp x 16 bytes.
+template <int R>
+__global__ __launch_bounds__(256) void k1_unslot_columns(uint32_t *__restrict__ table, const uint32_t *__restrict__ g2s, int G, int Wp)
+{
+    extern __shared__ uint4 unslot_sm[];
+    uint32_t *sm = reinterpret_cast<uint32_t *>(unslot_sm);
+    const int r0 = blockIdx.x * R, nr = min(R, G - r0);
+    if (nr <= 0) return;
+    uint32_t *rows = table + static_cast<size_t>(r0) * kPlanes * Wp;
+    for (int rp = 0; rp < nr * kPlanes; ++rp)   // (coalesced reads; LDS word (r Wp + w) 4 + plane)
+        for (int w = threadIdx.x; w < Wp; w += 256) sm[(static_cast<size_t>(rp >> 2) * Wp + w) * 4 + (rp & 3)] = rows[static_cast<size_t>(rp) * Wp + w];
+    __syncthreads();   // every word of these rows is in LDS: from here on they are only written (no other workgroup touches them)
+    for (int wo = threadIdx.x; wo < Wp; wo += 256) {
+        uint32_t acc[R][4];
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[r][0] = acc[r][1] = acc[r][2] = acc[r][3] = 0;
+        const uint4 *kq = reinterpret_cast<const uint4 *>(g2s) + static_cast<size_t>(wo) * 8;   // (g2s holds Gp = 32 Wp slots, every one below Gp)
+#pragma unroll 2
+        for (int i = 0; i < 8; ++i) {
+            const uint4 k4 = kq[i];
+            const uint32_t ks[4] = {k4.x, k4.y, k4.z, k4.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const uint32_t k = ks[e], kw = min(k >> 5, static_cast<uint32_t>(Wp - 1)), kb = k & 31u;
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    if (r < nr) {   // (wave-uniform)
+                        const uint4 w = unslot_sm[static_cast<size_t>(r) * Wp + kw];
+                        acc[r][0] = __builtin_amdgcn_alignbit(w.x >> kb, acc[r][0], 1);   // the new bit comes in at the top: after 32 of them the first is bit 0
+                        acc[r][1] = __builtin_amdgcn_alignbit(w.y >> kb, acc[r][1], 1);
+                        acc[r][2] = __builtin_amdgcn_alignbit(w.z >> kb, acc[r][2], 1);
+                        acc[r][3] = __builtin_amdgcn_alignbit(w.w >> kb, acc[r][3], 1);
+                    }
+                }
+            }
+        }
+        const int left = G - 32 * wo;   // columns of this word that are genes
+        const uint32_t valid = left >= 32 ? 0xFFFFFFFFu : (left <= 0 ? 0u : (1u << left) - 1u);
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            if (r < nr) {
+#pragma unroll
+                for (int pl = 0; pl < 4; ++pl) rows[(static_cast<size_t>(r) * kPlanes + pl) * Wp + wo] = acc[r][pl] & valid;
+            }
+    }
+}
+
+// reo_get_info: half-height tiles of a launch's item list whose count loop the slot form skipped (a full item counts 2, a half item 1)
+__global__ __launch_bounds__(256) void k1_slot_count(const uint32_t *__restrict__ items, int n, const uint32_t *__restrict__ trng, const uint32_t *__restrict__ crng,
+                                                     int Gp, unsigned long long *__restrict__ out)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    int v = 0;
+    if (i < n) {
+        const uint32_t it = items[i];
+        const int side = slot_item_side(it);
+        if (slot_separated(trng[static_cast<size_t>(side) * (Gp >> 5) + slot_item_tile(it)], crng[static_cast<size_t>(side) * (Gp >> 8) + slot_item_chunk(it)]))
+            v = slot_item_halves(it);
+    }
+    const unsigned long long m1 = __ballot(v == 1), m2 = __ballot(v == 2);
+    if ((threadIdx.x & 63) == 0 && (m1 | m2)) atomicAdd(out, static_cast<unsigned long long>(__builtin_popcountll(m1) + 2 * __builtin_popcountll(m2)));
 }
 
 // The same with the tie form chosen on the DEVICE from the transform's flags (K1Args::gate): the pipelined upload launches a side of
@@ -3644,6 +3834,7 @@ static int plane_bits(int64_t G) { return G <= 4095 ? 12 : (G <= 32767 ? 15 : (G
 // and which units this shard owns.
 struct K1Plan {
     bool multi, wide, big, wave, shared, wcounts, wmulti;   // the form (k1_plan says what each means)
+    bool slots = false;     // the tie-free wave form in slot order (launch_k1 decides: k1_slots_wanted)
     int RJ, CJ, Q, NP;      // genes j per lane, per j-chunk; j-chunks per panel; panels
     unsigned grid;          // workgroups of the workgroup forms
     size_t plane_elems;     // elements of one group's count plane (shared counts)
@@ -3752,8 +3943,10 @@ static void launch_pairs(reo_ctx *c, const K1Args &a, const K1Plan &pl)
         else if (gridw > 0) by_ties([&](auto t) { k1w_pairs_multi<NB, decltype(t)::value><<<gridw, 64, 0, c->stream>>>(a); });
     } else if (wv) {  // one wave per workgroup, generated count loop (two groups)
         if (gridw == 0) return;
-        if constexpr (kWg)
+        if constexpr (kWg) {
             if (a.gate) { k1w_pairs_gated<NB><<<gridw, 64, 0, c->stream>>>(a); return; }   // the tie form is chosen on the device (K1Args::gate)
+            if (pl.slots) { k1w_pairs_slots<NB><<<gridw, 64, 0, c->stream>>>(a); return; }  // tie-free, genes in slot order (k1_slots)
+        }
         by_ties([&](auto t) { k1w_pairs<NB, decltype(t)::value><<<gridw, 64, 0, c->stream>>>(a); });
     } else if constexpr (kWg)
         by_ties([&](auto t) { k1_pairs<NB, decltype(t)::value, false><<<grid, 256, 0, c->stream>>>(a); });
@@ -3969,6 +4162,7 @@ static K1Args k1_args(const reo_ctx *c, int k)
     a.seed = c->seed;
     a.items = nullptr; a.stamps = nullptr; a.gate = nullptr;
     a.park = nullptr; a.park_ge = nullptr; a.park_mode = 0;
+    a.s2g = nullptr; a.trng = nullptr; a.crng = nullptr;
     return a;
 }
 
@@ -4006,6 +4200,99 @@ static int32_t apply_range(reo_ctx *c, K1Args &a, int sides, const K1Range *rang
     return REO_OK;
 }
 
+// ---- SLOT ORDER (k1_slots.h).  Tie-free data of two groups, one shard, whole sides, at most 65 535 genes: the pair kernel counts with
+// the genes ordered by level (the sum of the extremes of their positions on the two sides), which puts most items' tile and chunk
+// apart on the item's side -- every count of such an item is 0 or the side's size, and its count loop is skipped.  Slot order lives and
+// dies inside launch_k1: the table that leaves it is the identity order's, bit for bit, and nobody else learns that slots exist.
+
+// the parts of c->k1_slot_maps (uint32 each)
+struct SlotMaps { uint32_t *gmm, *key, *g2s, *s2g, *trng, *crng; unsigned long long *count; };
+static size_t slot_maps_words(int Gp) { return static_cast<size_t>(Gp) * 5 + static_cast<size_t>(Gp) / 16 + static_cast<size_t>(Gp) / 128 + 2; }
+static SlotMaps slot_maps(const reo_ctx *c)
+{
+    SlotMaps m;
+    const size_t Gp = static_cast<size_t>(c->Gp);
+    m.gmm = c->k1_slot_maps.p; m.key = m.gmm + 2 * Gp; m.g2s = m.key + Gp; m.s2g = m.g2s + Gp;
+    m.trng = m.s2g + Gp; m.crng = m.trng + Gp / 16;
+    m.count = reinterpret_cast<unsigned long long *>(m.crng + Gp / 128);   // (an even number of words in front of it)
+    return m;
+}
+
+static bool k1_slots_wanted(const reo_ctx *c, const K1Plan &pl, int sides, bool keep_table, const int32_t *gate, const K1Range *range, bool prepare)
+{
+    return c->k1_slots && pl.wave && !pl.wide && !pl.big && c->ngroups == 2 && sides == 3 && !c->has_ties && c->world == 1 && !c->in_multi &&
+           !gate && !range && !prepare && !keep_table && c->t_pos16.p && c->t_pos16.n >= static_cast<size_t>(c->goff32[2]) * c->Gp;
+}
+
+// the slot form's buffers; a failure means the identity order (the caller clears the error state)
+static int32_t k1_slots_alloc(reo_ctx *c)
+{
+    int32_t rc;
+    const size_t nq = static_cast<size_t>(c->goff32[2] / 32) * c->Gp * 4;
+    if ((rc = c->k1_slot_part.ensure(static_cast<size_t>(kSlotSplits) * 2 * c->Gp)) || (rc = c->k1_slot_maps.ensure(slot_maps_words(c->Gp))) ||
+        (rc = c->pos_s.ensure(nq)) || (rc = c->lo_s.ensure(nq)))
+        return rc;
+    return REO_OK;
+}
+
+// in front of the pair kernel: ranges, keys, order, planes in slot order, tile and chunk ranges; a's operands become the slot form's
+static int32_t k1_slots_front(reo_ctx *c, K1Args &a)
+{
+    const int G = a.G, Gp = a.Gp, nblk = c->goff32[2] / 32;
+    const SlotMaps m = slot_maps(c);
+    const unsigned gb = static_cast<unsigned>((G + 255) / 256);
+    REO_HIP_CHECK(hipMemsetAsync(m.g2s, 0, static_cast<size_t>(Gp) * 2 * sizeof(uint32_t), c->stream));   // (g2s is summed up; s2g: no stray index, whatever happens)
+    k1_slot_part<<<dim3(gb, kSlotSplits, 2), 256, 0, c->stream>>>(c->t_pos16.p, Gp, G, a.cb * 32, a.nc, a.tb * 32, a.nt, c->k1_slot_part.p);
+    k1_slot_keys<<<gb, 256, 0, c->stream>>>(c->k1_slot_part.p, Gp, G, m.gmm, m.key);
+    k1_slot_rank<<<dim3(gb, static_cast<unsigned>((G + kSlotRankSpan - 1) / kSlotRankSpan)), 256, 0, c->stream>>>(m.key, G, m.g2s);
+    k1_slot_invert<<<static_cast<unsigned>(Gp / 256), 256, 0, c->stream>>>(m.g2s, m.s2g, G, Gp);
+    k1_slot_ranges<<<dim3(static_cast<unsigned>(Gp / 256), 2), 256, 0, c->stream>>>(m.gmm, m.s2g, G, Gp, m.trng, m.crng);
+    k1_slot_gather<<<dim3(static_cast<unsigned>(Gp / 256), static_cast<unsigned>(nblk)), 256, 0, c->stream>>>(c->pos.p, c->lo.p, m.s2g, Gp, c->pos_s.p, c->lo_s.p);
+    REO_HIP_CHECK(hipGetLastError());
+    a.P = c->pos_s.p; a.AL = c->lo_s.p; a.AH = c->lo_s.p;   // (the tie-free form reads no hi planes)
+    a.s2g = m.s2g; a.trng = m.trng; a.crng = m.crng;
+    return REO_OK;
+}
+
+// behind it: the table's columns back into gene order (its rows were written in gene order)
+static int32_t k1_slots_back(reo_ctx *c, const K1Args &a)
+{
+    // rows per workgroup: as many as fit 60 KB of LDS (six up to 20 480 genes, four up to 30 720, two up to 61 440, else one).  60 and not
+    // the 64 KB that a launch may ask for without a function attribute: 16 bytes x Gp / 32 per row and Gp a multiple of 1 024 make a row a
+    // multiple of 512 bytes, six rows of 20 480 genes and four of 30 720 are 60 KB exactly, and two such workgroups (120 KB) still share a
+    // CU's 160 KB with room for a third kernel's workgroups; between 60 and 64 KB no gene count gains a row.
+    const size_t row_bytes = static_cast<size_t>(a.Wp) * 16;
+    auto go = [&](auto rtag) {
+        constexpr int R = decltype(rtag)::value;
+        k1_unslot_columns<R><<<static_cast<unsigned>((a.G + R - 1) / R), 256, R * row_bytes, c->stream>>>(a.table, slot_maps(c).g2s, a.G, a.Wp);
+    };
+    if (6 * row_bytes <= 61440) go(std::integral_constant<int, 6>{});
+    else if (4 * row_bytes <= 61440) go(std::integral_constant<int, 4>{});
+    else if (2 * row_bytes <= 61440) go(std::integral_constant<int, 2>{});
+    else go(std::integral_constant<int, 1>{});
+    REO_HIP_CHECK(hipGetLastError());
+    return REO_OK;
+}
+
+int32_t launch_slot_separated(reo_ctx *c, int64_t *half_tiles)
+{
+    *half_tiles = 0;
+    // only over what the last build left: its item list still in its buffer, its maps laid out for the context's geometry (whatever
+    // cleared or moved either has ended the snapshot: api.hip, invalidate)
+    if (!c->last_k1_slots || !c->k1_slot_items || !c->k1_slot_items_n || !c->k1_slot_maps.p) return REO_OK;
+    const reo_ctx::ItemList &il = c->k1_wave_items[0];
+    if (c->k1_slot_gp != c->Gp || c->k1_slot_maps.n < slot_maps_words(c->Gp) || c->k1_slot_items != il.buf.p || c->k1_slot_items_n > il.buf.n) return REO_OK;
+    const SlotMaps m = slot_maps(c);
+    unsigned long long n = 0;
+    REO_HIP_CHECK(hipMemsetAsync(m.count, 0, sizeof n, c->stream));
+    k1_slot_count<<<static_cast<unsigned>((c->k1_slot_items_n + 255) / 256), 256, 0, c->stream>>>(c->k1_slot_items, static_cast<int>(c->k1_slot_items_n), m.trng, m.crng, c->Gp, m.count);
+    REO_HIP_CHECK(hipGetLastError());
+    REO_HIP_CHECK(hipMemcpyAsync(&n, m.count, sizeof n, hipMemcpyDeviceToHost, c->stream));
+    REO_HIP_CHECK(hipStreamSynchronize(c->stream));
+    *half_tiles = static_cast<int64_t>(n);
+    return REO_OK;
+}
+
 // sides (wave form, two groups): which sides' items are launched -- bit 0 the comparison's own group, bit 1 the rest; 3 = the whole
 // table.  keep_table: the class table has been cleared by the caller and holds other sides' planes already (the pipelined upload,
 // transform.hip eager_upload, launches a side as soon as its group's samples are ranked).
@@ -4023,6 +4310,7 @@ int32_t launch_k1(reo_ctx *c, int k, int sides, bool keep_table, const int32_t *
     if ((rc = upload_unit_map(c, units))) return rc;
     a.unit_map = c->unit_map.p;
     a.gate = gate;
+    if (!prepare) { c->last_k1_slots = 0; c->k1_slot_items = nullptr; c->k1_slot_items_n = 0; c->k1_slot_gp = 0; }
     if ((range || prepare) && (sides != 1 && sides != 2)) { set_error("a range of sample blocks / a prepared launch: one side of the pair kernel"); return REO_EINVAL; }
     if (gate && (!pl.wave || pl.wide || pl.big)) { set_error("a gated launch of the pair kernel: wave form, at most 65535 genes and samples"); return REO_EINVAL; }
     c->x_pipelined = false;
@@ -4055,10 +4343,21 @@ int32_t launch_k1(reo_ctx *c, int k, int sides, bool keep_table, const int32_t *
     }
     if (units.empty()) return REO_OK;
     c->last_k1_shared = pl.shared ? 1 : 0;
+    // slot order, where it applies and its buffers can be had (else the identity order, as for every other case)
+    if (k1_slots_wanted(c, pl, sides, keep_table, gate, range, prepare) && c->k1_items_n) {
+        if (k1_slots_alloc(c) == REO_OK) pl.slots = true;
+        else (void)hipGetLastError();
+    }
     if (a.stamps) k_time_mark<<<1, 64, 0, c->stream>>>(a.stamps + c->k1_items_n * 4);
     tic(c, 1);
+    if (pl.slots && (rc = k1_slots_front(c, a))) { toc(c); return rc; }
     dispatch_pairs(c, a, pl);
+    if (pl.slots && (rc = k1_slots_back(c, a))) { toc(c); return rc; }
     toc(c);
+    if (pl.slots) {
+        c->last_k1_slots = 1;
+        c->k1_slot_items = a.items; c->k1_slot_items_n = c->k1_items_n; c->k1_slot_gp = a.Gp;
+    }
     if (a.stamps) k_time_mark<<<1, 64, 0, c->stream>>>(a.stamps + c->k1_items_n * 4 + 1);
     REO_HIP_CHECK(hipGetLastError());
     if (a.stamps) return report_k1_stamps(c, a.stamps);

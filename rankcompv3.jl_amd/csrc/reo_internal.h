@@ -257,6 +257,16 @@ struct reo_ctx {
     int k1_wave = 1;                    // REO_K1_WAVE=0: the workgroup form of the pair kernel (round 2) instead of the wave form
     int k1_order = 0;                   // REO_K1_ORDER=1 (experiment): the wave form's items i-tile-fastest inside a chunk instead of chunk-fastest inside an i-tile
     int k1_half = 1;                    // REO_K1_HALF=0: no half-height items in the last round of the wave form's launch
+    // slot order of the pair kernel (kernels.hip, k1_slots; index rules: k1_slots.h): tie-free data of two groups on one shard is counted
+    // with the genes ordered by level, and the table's rows and columns come back in gene order before launch_k1 returns
+    int k1_slots = 1;                   // REO_K1_SLOTS=0: the identity order for everything (A/B, tests)
+    int last_k1_slots = 0;              // reo_get_info 25: the last build of the class table used the slot order
+    const uint32_t *k1_slot_items = nullptr;   // ... and its item list (one of k1_wave_items), for the count of separated items (reo_get_info 26)
+    size_t k1_slot_items_n = 0;
+    int k1_slot_gp = 0;                 // ... and the padded gene count its maps and ranges are laid out for
+    reo::DevBuf<uint32_t> k1_slot_part; // [kSlotSplits][2][Gp] the sides' position ranges of every gene over a slice of the samples (min | max << 16)
+    reo::DevBuf<uint32_t> k1_slot_maps; // [2][Gp] ranges per side, [Gp] keys, [Gp] g2s, [Gp] s2g, [2][Gp / 32] tile ranges, [2][Gp / 256] chunk ranges, [2] a count
+    reo::DevBuf<uint4> pos_s, lo_s;     // the pos and lo planes in slot order (the layouts of pos and lo)
     int n_cus = 256;                    // compute units of the device (the wave form's item slots = CUs x 4 SIMDs x waves per SIMD)
     int share_counts = 1;               // REO_SHARE_GROUP_COUNTS=0 recounts per comparison instead
     int last_k1_shared = 0;             // reo_get_info: how the last class table was built
@@ -363,6 +373,7 @@ int64_t exchange_unit_words(const reo_ctx *c);   // uint32 per packed work unit
 int32_t exchange_units_per_rank(const reo_ctx *c);
 int32_t launch_pack_units(reo_ctx *c, int m0 = 0, int mcnt = -1, uint32_t *send = nullptr, hipStream_t st = nullptr);    // this shard's units (all, or slots m0 .. m0 + mcnt - 1) -> c->xsend / send
 int32_t launch_expand_units(reo_ctx *c, int m0 = 0, int mcnt = -1, const uint32_t *recv = nullptr, hipStream_t st = nullptr);  // every shard's pack -> the table: the others' words and their mirrors
+int32_t launch_slot_separated(reo_ctx *c, int64_t *half_tiles);   // half-height tiles of the last build whose count loop was skipped (0 without slot order; waits for the stream)
 int32_t launch_counts(reo_ctx *c, int64_t i0, int64_t i1, int64_t j0, int64_t j1, uint16_t *d_gt, uint16_t *d_eq);
 int32_t launch_check_table(reo_ctx *c, int *bad);  // consistency of an exchanged class table (kernels.hip, k_check_table)
 int32_t launch_decode(reo_ctx *c, int64_t i0, int64_t i1, int64_t j0, int64_t j1, uint8_t *d_code);
