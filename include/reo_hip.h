@@ -318,6 +318,57 @@ int32_t reo_set_matrix_pseudobulk_csc_i64(reo_ctx *ctx, int64_t G, int64_t C, co
                                           const int64_t *val, const int32_t *order, int64_t n_order,
                                           const int32_t *chunk_ptr, int32_t n_out);
 
+/* SPARSE ON THE DEVICE.  The same three families for a matrix whose arrays already live in HBM on the context's device (a torch sparse_csc
+ * tensor on the GPU is this container as it is): nothing crosses the link, the caller's buffers are only read and have been read when the
+ * call returns (it waits for the context's stream, so nothing has to be kept alive beyond the call).  The suffix names the element type of
+ * d_val / dX; d_colptr ([S + 1] or [C + 1]) and d_rowidx ([nnz]) are both int32 (index_bits = 32) or both int64 (64; torch's default); nnz,
+ * the length of d_rowidx and d_val, is passed in so that nothing is read back before buffers are sized, and must equal colptr[last].
+ * order and chunk_ptr stay HOST arrays, checked as in the host entries.
+ *   reo_set_matrix_csc_dev_<T> is reo_set_matrix_csc_<T>: row indices strictly increasing inside a column, stored zeros and -0.0 kept as
+ *     stored, the resident matrix Float64 / Int64 / Float32 (compared in Float32) / Int64 for Int32 values, in the context's own memory
+ *     (ld = G), bit-identical to the host entry on the same arrays in every order of calls.
+ *   reo_set_matrix_pseudobulk_csc_dev_<T> / _dense_dev_<T> are reo_set_matrix_pseudobulk_csc_* / _dense_*: cells in the given order,
+ *     left-to-right sums.  Float32 and Int32 cells are widened AS THEY ARE READ and summed in Float64 / Int64, so the sums are
+ *     bit-identical to the host entry on the widened values (that is this library's rule for such cells, not the reference's arithmetic
+ *     for a Matrix{Float32}).
+ * THE CHECK.  The index arrays are untrusted and the kernels index with them, so one kernel checks them first (one stream over the
+ * index bytes): per column its two colptr words -- inside [0, nnz], non-decreasing, at most G apart, colptr[0] = 0, colptr[last] = nnz
+ * -- and only then the column's row indices -- inside [0, G), strictly increasing.  The verdict returns to the host (8 bytes) before the
+ * consuming kernel is queued.  A fault is REO_EINVAL and the message names its class and the lowest offending column; so are an
+ * index_bits other than 32 / 64, an nnz that no such matrix has and a null d_rowidx / d_val with nnz > 0.  The arrays must not be written
+ * by the caller while the call runs.
+ * On ANY failure the context holds no matrix until the next reo_set_matrix_* (it stays usable).  Not available on a reo_create_multi
+ * context (REO_EINVAL).  reo_get_info 27 reads 1 after reo_set_matrix_csc_dev_* (and 23 its nnz; 19, 21 and 22 read 0: nothing was
+ * uploaded); after the pseudo-bulk entries 19 and 21-23 and 27 read 0, as after the host ones. */
+int32_t reo_set_matrix_csc_dev_f64(reo_ctx *ctx, int64_t G, int64_t S, int64_t nnz, const void *d_colptr, const void *d_rowidx,
+                                   int32_t index_bits /* 32 or 64 */, const void *d_val);
+int32_t reo_set_matrix_csc_dev_i64(reo_ctx *ctx, int64_t G, int64_t S, int64_t nnz, const void *d_colptr, const void *d_rowidx,
+                                   int32_t index_bits /* 32 or 64 */, const void *d_val);
+int32_t reo_set_matrix_csc_dev_f32(reo_ctx *ctx, int64_t G, int64_t S, int64_t nnz, const void *d_colptr, const void *d_rowidx,
+                                   int32_t index_bits /* 32 or 64 */, const void *d_val);
+int32_t reo_set_matrix_csc_dev_i32(reo_ctx *ctx, int64_t G, int64_t S, int64_t nnz, const void *d_colptr, const void *d_rowidx,
+                                   int32_t index_bits /* 32 or 64 */, const void *d_val);
+int32_t reo_set_matrix_pseudobulk_csc_dev_f64(reo_ctx *ctx, int64_t G, int64_t C, int64_t nnz, const void *d_colptr, const void *d_rowidx,
+                                              int32_t index_bits, const void *d_val, const int32_t *order, int64_t n_order,
+                                              const int32_t *chunk_ptr, int32_t n_out);
+int32_t reo_set_matrix_pseudobulk_csc_dev_i64(reo_ctx *ctx, int64_t G, int64_t C, int64_t nnz, const void *d_colptr, const void *d_rowidx,
+                                              int32_t index_bits, const void *d_val, const int32_t *order, int64_t n_order,
+                                              const int32_t *chunk_ptr, int32_t n_out);
+int32_t reo_set_matrix_pseudobulk_csc_dev_f32(reo_ctx *ctx, int64_t G, int64_t C, int64_t nnz, const void *d_colptr, const void *d_rowidx,
+                                              int32_t index_bits, const void *d_val, const int32_t *order, int64_t n_order,
+                                              const int32_t *chunk_ptr, int32_t n_out);
+int32_t reo_set_matrix_pseudobulk_csc_dev_i32(reo_ctx *ctx, int64_t G, int64_t C, int64_t nnz, const void *d_colptr, const void *d_rowidx,
+                                              int32_t index_bits, const void *d_val, const int32_t *order, int64_t n_order,
+                                              const int32_t *chunk_ptr, int32_t n_out);
+int32_t reo_set_matrix_pseudobulk_dense_dev_f64(reo_ctx *ctx, const void *dX, int64_t G, int64_t C, int64_t ld, const int32_t *order,
+                                                int64_t n_order, const int32_t *chunk_ptr, int32_t n_out);
+int32_t reo_set_matrix_pseudobulk_dense_dev_i64(reo_ctx *ctx, const void *dX, int64_t G, int64_t C, int64_t ld, const int32_t *order,
+                                                int64_t n_order, const int32_t *chunk_ptr, int32_t n_out);
+int32_t reo_set_matrix_pseudobulk_dense_dev_f32(reo_ctx *ctx, const void *dX, int64_t G, int64_t C, int64_t ld, const int32_t *order,
+                                                int64_t n_order, const int32_t *chunk_ptr, int32_t n_out);
+int32_t reo_set_matrix_pseudobulk_dense_dev_i32(reo_ctx *ctx, const void *dX, int64_t G, int64_t C, int64_t ld, const int32_t *order,
+                                                int64_t n_order, const int32_t *chunk_ptr, int32_t n_out);
+
 /* The reference's low-expression filters on the resident matrix (any host entry, a _dev buffer, the pseudo-bulk entries; resident Float64,
  * Int64 or Float32), :618 then :626 of src/RankCompV3.jl:
  *   profile s is kept iff #{g : x[g,s] > 0} > min_profiles;
@@ -374,7 +425,8 @@ int32_t reo_get_timings(reo_ctx *ctx, double *ms, int32_t n);
  * (reo_set_matrix_csc_*: 1; every other reo_set_matrix_*: 0), 23 the stored entries (nnz) of that CSC matrix, 24 the element type of the
  * resident matrix (0 none, 1 Float64, 2 Int64 -- Int32 input is widened --, 3 Float32), 25 the last class table was built with the genes
  * in slot order (tie-free data of two groups on one shard; REO_K1_SLOTS=0 switches it off; the table is the same bit for bit), 26 the
- * half-height tiles of that build whose count loop was skipped (counted when asked for, n > 26: one small kernel and a wait). */
+ * half-height tiles of that build whose count loop was skipped (counted when asked for, n > 26: one small kernel and a wait), 27 the matrix
+ * was made dense from CSC arrays on the device (reo_set_matrix_csc_dev_*: 1, and 23 then reports its nnz; every other reo_set_matrix_*: 0). */
 int32_t reo_get_info(reo_ctx *ctx, int64_t *info, int32_t n);
 
 #ifdef __cplusplus

@@ -32,7 +32,7 @@ SYMBOLS = [
     "reo_pseudobulk_dense_f64", "reo_pseudobulk_dense_i64", "reo_pseudobulk_csc_f64", "reo_pseudobulk_csc_i64",
     "reo_set_matrix_pseudobulk_dense_f64", "reo_set_matrix_pseudobulk_dense_i64", "reo_set_matrix_pseudobulk_csc_f64", "reo_set_matrix_pseudobulk_csc_i64",
     "reo_filter_matrix", "reo_get_matrix",
-]
+] + [f"reo_set_matrix_{form}_{t}" for form in ("csc_dev", "pseudobulk_csc_dev", "pseudobulk_dense_dev") for t in ("f64", "i64", "f32", "i32")]
 
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p)
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p)
@@ -135,6 +135,10 @@ def lib() -> ctypes.CDLL:
         "reo_filter_matrix": (i32, [vp, i64, i64, vp, vp, vp, vp]),
         "reo_get_matrix": (i32, [vp, vp, i64]),
     }
+    for t in ("f64", "i64", "f32", "i32"):   # SPARSE ON THE DEVICE
+        sig["reo_set_matrix_csc_dev_" + t] = (i32, [vp, i64, i64, i64, vp, vp, i32, vp])
+        sig["reo_set_matrix_pseudobulk_csc_dev_" + t] = (i32, [vp, i64, i64, i64, vp, vp, i32, vp, vp, i64, vp, i32])
+        sig["reo_set_matrix_pseudobulk_dense_dev_" + t] = (i32, [vp, vp, i64, i64, i64, vp, i64, vp, i32])
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
         fn.restype = res
@@ -291,6 +295,54 @@ def device_matrix(t):
     return int(t.data_ptr()), int(G), int(S), int(t.stride(1)) if S > 1 else int(max(G, 1)), names[t.dtype], t
 
 
+def is_device_sparse(t) -> bool:
+    """A torch tensor on a GPU whose layout is sparse_csc, sparse_csr or sparse_coo (without importing torch for anything that is not a
+    tensor).  Such a tensor has no strides and no data_ptr: it never goes to device_matrix."""
+    if not (type(t).__module__.split(".")[0] == "torch" and hasattr(t, "layout") and bool(getattr(t, "is_cuda", False))):
+        return False
+    import torch
+    return t.layout in (torch.sparse_csc, torch.sparse_csr, torch.sparse_coo)
+
+
+def device_csc_entry(t):
+    """(type suffix, G, S, nnz, colptr tensor, rowidx tensor, value tensor, index_bits, tensors to keep alive) for a 2-D sparse torch
+    tensor (genes x samples, or genes x cells): what reo_set_matrix_csc_dev_<suffix> / reo_set_matrix_pseudobulk_csc_dev_<suffix> take.
+    Pure: no library and no GPU (a CPU tensor gets the same answer).  A sparse_csc tensor is used IN PLACE: ccol_indices(), row_indices()
+    and values() are the caller's own storage -- and so is the .t() of a cells x genes sparse_csr tensor (AnnData's orientation), which
+    torch answers with a sparse_csc view.  Every other layout goes through to_sparse_csc() on the tensor's device.  The index dtype
+    (int32 / int64) is kept; value dtypes follow csc_entry's rule: float64 / int64 / float32 / int32 as they are, narrower integers and
+    bool to int64, every other float type to float64, cast on the device.
+    Nothing is sorted or coalesced here: torch accepts a CSC tensor whose row indices are unsorted or repeated inside a column
+    (check_invariants=False), the library refuses it (REO_EINVAL, "not strictly increasing"), and
+    t.to_sparse_coo().coalesce().to_sparse_csc() is the canonical form of such a tensor.  The stream that produced the tensor is
+    synchronised before the pointers are handed over, as in device_matrix."""
+    import torch
+    if t.dim() != 2:
+        raise DimensionMismatch(REO_EINVAL, "expression matrix must be 2-D (genes x samples): batched sparse tensors are not taken")
+    t = t.detach()
+    if t.layout != torch.sparse_csc:
+        t = t.to_sparse_csc()
+    G, S = t.shape
+    colptr, rowidx, val = t.ccol_indices(), t.row_indices(), t.values()
+    if val.dim() != 1:
+        raise DimensionMismatch(REO_EINVAL, "expression matrix must be 2-D (genes x samples): block or hybrid sparse tensors are not taken")
+    names = {torch.float64: "f64", torch.int64: "i64", torch.float32: "f32", torch.int32: "i32"}
+    if val.dtype not in names:
+        val = val.to(torch.float64 if val.dtype.is_floating_point else torch.int64)
+    if colptr.dtype != rowidx.dtype or colptr.dtype not in (torch.int32, torch.int64):
+        colptr, rowidx = colptr.to(torch.int64), rowidx.to(torch.int64)
+    colptr, rowidx, val = colptr.contiguous(), rowidx.contiguous(), val.contiguous()
+    if t.is_cuda:
+        torch.cuda.current_stream(t.device).synchronize()
+    bits = 32 if colptr.dtype == torch.int32 else 64
+    return names[val.dtype], int(G), int(S), int(rowidx.numel()), colptr, rowidx, val, bits, [t, colptr, rowidx, val]
+
+
+def _dptr(t):
+    """the device pointer of a tensor, None for an empty one"""
+    return ctypes.c_void_p(int(t.data_ptr())) if t.numel() else None
+
+
 class Context:
     """One reo_ctx: one GPU (or, with n_gpus, all GPUs of this process behind one handle), one expression matrix."""
 
@@ -348,7 +400,14 @@ class Context:
         self.G, self.S = G, S
 
     def set_matrix_tensor(self, t) -> None:
-        """A torch tensor on the context's device (genes x samples) as the expression matrix: see device_matrix."""
+        """A torch tensor on the context's device (genes x samples) as the expression matrix: a strided one is used where it is
+        (device_matrix), a sparse one (sparse_csc / sparse_csr / sparse_coo) is checked and made dense on the device from its CSC arrays
+        (device_csc_entry, reo_set_matrix_csc_dev_*; the tensor may go once the call has returned)."""
+        if is_device_sparse(t):
+            ty, G, S, nnz, colptr, rowidx, val, bits, keep = device_csc_entry(t)
+            check(getattr(self._L, "reo_set_matrix_csc_dev_" + ty)(self._h, G, S, nnz, _dptr(colptr), _dptr(rowidx), bits, _dptr(val)))
+            self.G, self.S = G, S
+            return
         ptr, G, S, ld, dtype, keep = device_matrix(t)
         self.set_matrix_device(ptr, G, S, ld, dtype, keepalive=keep)
 
@@ -498,7 +557,23 @@ class Context:
 
     def set_matrix_pseudobulk(self, cells, order, chunk_ptr) -> None:
         """The same sums, left on the device as the context's expression matrix (reo_set_matrix_pseudobulk_*): arguments and routing of
-        pseudobulk, nothing comes back to the host.  The profiles are the samples: set_groups wants one label per profile."""
+        pseudobulk, nothing comes back to the host.  The profiles are the samples: set_groups wants one label per profile.
+        Cells that are a torch tensor on the context's device are read where they are (reo_set_matrix_pseudobulk_*_dev_*): a sparse one
+        through device_csc_entry, a strided one column-major as device_matrix makes it; float32 / int32 cells are summed in Float64 /
+        Int64, like the host cells that _pseudobulk_args widens."""
+        if is_device_sparse(cells) or is_device_tensor(cells):
+            order = np.ascontiguousarray(order, dtype=np.int32)
+            chunk_ptr = np.ascontiguousarray(chunk_ptr, dtype=np.int32)
+            n_out = chunk_ptr.size - 1
+            tail = (_ptr(order) if order.size else None, order.size, _ptr(chunk_ptr), n_out)
+            if is_device_sparse(cells):
+                ty, G, C, nnz, colptr, rowidx, val, bits, keep = device_csc_entry(cells)
+                check(getattr(self._L, "reo_set_matrix_pseudobulk_csc_dev_" + ty)(self._h, G, C, nnz, _dptr(colptr), _dptr(rowidx), bits, _dptr(val), *tail))
+            else:
+                ptr, G, C, ld, ty, keep = device_matrix(cells)
+                check(getattr(self._L, "reo_set_matrix_pseudobulk_dense_dev_" + ty)(self._h, ctypes.c_void_p(ptr), G, C, ld, *tail))
+            self.G, self.S = G, n_out
+            return
         form, ty, args, G, keep = self._pseudobulk_args(cells, order, chunk_ptr)
         check(getattr(self._L, f"reo_set_matrix_pseudobulk_{form}_{ty}")(self._h, *args))
         self.G, self.S = G, args[-1]
@@ -541,8 +616,8 @@ class Context:
                 "k2_full_launches": int(ms[9]), "k2_delta_ms": ms[10], "set_matrix_host_wall_ms": ms[11]}
 
     def info(self) -> dict:
-        v = np.zeros(27, dtype=np.int64)
-        check(self._L.reo_get_info(self._h, _ptr(v), 27))
+        v = np.zeros(28, dtype=np.int64)
+        check(self._L.reo_get_info(self._h, _ptr(v), 28))
         return {"G": int(v[0]), "S": int(v[1]), "Gp": int(v[2]), "table_bytes": int(v[3]), "has_ties": int(v[4]),
                 "tiles_owned": int(v[5]), "tiles_total": int(v[6]), "tile_i": int(v[7]), "chunk_j": int(v[8]),
                 "chunks_per_panel": int(v[9]), "unit_h": int(v[10]), "sample_slots": int(v[11]),
@@ -550,4 +625,4 @@ class Context:
                 "cycle_period": int(v[16]), "cycle_found_at_pass": int(v[17]), "cycle_passes_skipped": int(v[18]), "upload_link_bytes": int(v[19]),
                 "eager_range_launches": int(v[20]), "rowmajor_upload": int(v[21]),
                 "csc_upload": int(v[22]), "csc_nnz": int(v[23]), "resident_dtype": int(v[24]),
-                "k1_slot_order": int(v[25]), "k1_half_tiles_separated": int(v[26])}
+                "k1_slot_order": int(v[25]), "k1_half_tiles_separated": int(v[26]), "csc_device": int(v[27])}

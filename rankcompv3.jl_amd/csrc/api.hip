@@ -384,7 +384,7 @@ static int32_t set_matrix(reo_ctx *c, const void *X, int64_t G, int64_t S, int64
     if (layout == kLayoutColMajor && ld < G) { set_error("leading dimension %lld < G = %lld", (long long)ld, (long long)G); return REO_EINVAL; }
     invalidate(c);
     c->rowmajor_upload = 0;
-    c->csc_upload = 0; c->csc_nnz = 0;
+    c->csc_upload = 0; c->csc_nnz = 0; c->csc_device = 0;
     const bool host_i32 = dtype == 4 && !on_device;
     const size_t resident = static_cast<size_t>(G) * S * (dtype == 3 ? 4 : 8);   // bytes of the matrix the kernels read
     c->G = G; c->S = S; c->dtype = dtype == 4 ? 2 : dtype;
@@ -849,7 +849,7 @@ static int32_t set_matrix_pseudobulk(reo_ctx *c, bool csc, bool is_int, const vo
     if (rc) return rc;
     invalidate(c);
     c->dtype = 0; c->dX = nullptr;
-    c->narrowed_bytes = 0; c->rowmajor_upload = 0; c->csc_upload = 0; c->csc_nnz = 0;
+    c->narrowed_bytes = 0; c->rowmajor_upload = 0; c->csc_upload = 0; c->csc_nnz = 0; c->csc_device = 0;
     if ((rc = use(c)) || (rc = check_shape(G, n_out))) return rc;
     rc = csc ? pseudobulk_resident_csc(c, is_int, G, C, colptr, rowidx, val, order, n_order, chunk_ptr, n_out)
              : pseudobulk_resident_dense(c, X, is_int, G, C, ld, order, n_order, chunk_ptr, n_out);
@@ -871,6 +871,72 @@ int32_t reo_set_matrix_pseudobulk_csc_f64(reo_ctx *c, int64_t G, int64_t C, cons
 int32_t reo_set_matrix_pseudobulk_csc_i64(reo_ctx *c, int64_t G, int64_t C, const int64_t *colptr, const int32_t *rowidx, const int64_t *val,
                                           const int32_t *order, int64_t n_order, const int32_t *chunk_ptr, int32_t n_out)
 { return set_matrix_pseudobulk(c, true, true, nullptr, G, C, 0, colptr, rowidx, val, order, n_order, chunk_ptr, n_out); }
+
+// SPARSE ON THE DEVICE (include/reo_hip.h): the CSC arrays are in HBM.  Nothing is uploaded; a kernel checks the index arrays
+// (csc_device.hip) before t_csc_columns / pb_csc index with them.  Whatever fails, the context holds no matrix afterwards.
+static int32_t begin_device_entry(reo_ctx *c, const char *what, int64_t G, int64_t S)
+{
+    int32_t rc = no_multi(c, what);
+    if (rc) return rc;
+    invalidate(c);
+    c->dtype = 0; c->dX = nullptr;
+    c->narrowed_bytes = 0; c->rowmajor_upload = 0; c->csc_upload = 0; c->csc_nnz = 0; c->csc_device = 0;
+    if ((rc = use(c)) || (rc = check_shape(G, S))) return rc;
+    return REO_OK;
+}
+
+static int32_t set_matrix_csc_dev(reo_ctx *c, int64_t G, int64_t S, int64_t nnz, const void *d_colptr, const void *d_rowidx, int32_t index_bits,
+                                  const void *d_val, int dtype)
+{
+    int32_t rc = begin_device_entry(c, "reo_set_matrix_csc_dev", G, S);
+    if (rc) return rc;
+    if (dtype >= 3 && getenv("REO_TRANSFORM") && getenv("REO_TRANSFORM")[0] == 's') {
+        set_error("REO_TRANSFORM=segmented: the segmented sort of the A/B build takes Float64 and Int64 matrices only, not Float32 / Int32");
+        return REO_EINVAL;
+    }
+    DrainOnExit drain(c);   // the caller's arrays have been read on every return
+    const int64_t *colptr = nullptr;
+    if ((rc = csc_device_check(c, G, S, nnz, d_colptr, d_rowidx, index_bits, d_val, &colptr))) return rc;
+    if ((rc = c->dX_owned.ensure(static_cast<size_t>(G) * S * (dtype == 3 ? 4 : 8)))) return rc;
+    if ((rc = densify_device_csc(c, G, S, colptr, d_rowidx, index_bits, d_val, dtype, c->dX_owned.p))) return rc;
+    REO_HIP_CHECK(hipStreamSynchronize(c->stream));
+    drain.dismiss();
+    c->G = G; c->S = S; c->ld = G; c->dX = c->dX_owned.p; c->dtype = dtype == 4 ? 2 : dtype;
+    c->csc_nnz = nnz; c->csc_device = 1;
+    return REO_OK;
+}
+
+static int32_t set_matrix_pseudobulk_dev(reo_ctx *c, bool csc, int dtype, const void *dX, int64_t G, int64_t C, int64_t ld, int64_t nnz,
+                                         const void *d_colptr, const void *d_rowidx, int32_t index_bits, const void *d_val, const int32_t *order,
+                                         int64_t n_order, const int32_t *chunk_ptr, int32_t n_out)
+{
+    int32_t rc = begin_device_entry(c, "reo_set_matrix_pseudobulk", G, n_out);
+    if (rc) return rc;
+    DrainOnExit drain(c);
+    rc = csc ? pseudobulk_device_csc(c, dtype, G, C, nnz, d_colptr, d_rowidx, index_bits, d_val, order, n_order, chunk_ptr, n_out)
+             : pseudobulk_device_dense(c, dtype, dX, G, C, ld, order, n_order, chunk_ptr, n_out);
+    if (rc) return rc;
+    drain.dismiss();   // (the run has waited for the stream)
+    c->G = G; c->S = n_out; c->ld = G; c->dX = c->dX_owned.p; c->dtype = (dtype == 2 || dtype == 4) ? 2 : 1;
+    return REO_OK;
+}
+
+#define REO_DEVICE_SPARSE_ENTRIES(T, DT)                                                                                                        \
+    int32_t reo_set_matrix_csc_dev_##T(reo_ctx *c, int64_t G, int64_t S, int64_t nnz, const void *d_colptr, const void *d_rowidx,               \
+                                       int32_t index_bits, const void *d_val)                                                                   \
+    { return set_matrix_csc_dev(c, G, S, nnz, d_colptr, d_rowidx, index_bits, d_val, DT); }                                                     \
+    int32_t reo_set_matrix_pseudobulk_csc_dev_##T(reo_ctx *c, int64_t G, int64_t C, int64_t nnz, const void *d_colptr, const void *d_rowidx,    \
+                                                  int32_t index_bits, const void *d_val, const int32_t *order, int64_t n_order,                 \
+                                                  const int32_t *chunk_ptr, int32_t n_out)                                                      \
+    { return set_matrix_pseudobulk_dev(c, true, DT, nullptr, G, C, 0, nnz, d_colptr, d_rowidx, index_bits, d_val, order, n_order, chunk_ptr, n_out); } \
+    int32_t reo_set_matrix_pseudobulk_dense_dev_##T(reo_ctx *c, const void *dX, int64_t G, int64_t C, int64_t ld, const int32_t *order,         \
+                                                    int64_t n_order, const int32_t *chunk_ptr, int32_t n_out)                                   \
+    { return set_matrix_pseudobulk_dev(c, false, DT, dX, G, C, ld, 0, nullptr, nullptr, 0, nullptr, order, n_order, chunk_ptr, n_out); }
+REO_DEVICE_SPARSE_ENTRIES(f64, 1)
+REO_DEVICE_SPARSE_ENTRIES(i64, 2)
+REO_DEVICE_SPARSE_ENTRIES(f32, 3)
+REO_DEVICE_SPARSE_ENTRIES(i32, 4)
+#undef REO_DEVICE_SPARSE_ENTRIES
 
 int32_t reo_filter_matrix(reo_ctx *c, int64_t min_profiles, int64_t min_features, uint8_t *profile_kept, uint8_t *gene_kept,
                           int64_t *S_kept, int64_t *G_kept)
@@ -1358,13 +1424,13 @@ int32_t reo_get_info(reo_ctx *c, int64_t *info, int32_t n)
         int32_t rc = use(c);
         if (rc || (rc = launch_slot_separated(c, &separated))) return rc;
     }
-    const int64_t v[27] = {c->G, c->S, c->Gp, static_cast<int64_t>(c->table.n * sizeof(uint32_t)), c->has_ties,
+    const int64_t v[28] = {c->G, c->S, c->Gp, static_cast<int64_t>(c->table.n * sizeof(uint32_t)), c->has_ties,
                            c->tiles_owned, c->tiles_total, kTileI, c->k1_cj, c->k1_q, kUnitH,
                            c->goff32.empty() ? 0 : c->goff32.back(), c->last_k1_shared,
                            static_cast<int64_t>(c->gcounts.n * sizeof(uint16_t)), c->transform_in_lds, c->xcc_local,
                            c->it_cycle_period, c->it_cycle_at, c->it_cycle_skipped, c->narrowed_bytes, c->eager_range_launches, c->rowmajor_upload,
-                           c->csc_upload, c->csc_nnz, c->dtype, c->last_k1_slots, separated};
-    for (int i = 0; i < n && i < 27; ++i) info[i] = v[i];
+                           c->csc_upload, c->csc_nnz, c->dtype, c->last_k1_slots, separated, c->csc_device};
+    for (int i = 0; i < n && i < 28; ++i) info[i] = v[i];
     return REO_OK;
 }
 

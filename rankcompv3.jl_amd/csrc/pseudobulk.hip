@@ -8,6 +8,8 @@
 //   CSC    colptr i64 [C+1], rowidx i32 [nnz], val f64/i64 [nnz]  (this build's own container for
 //          sparse single-cell counts; the reference has no sparse input format)
 // Both are HBM-bound streams: every needed input byte is read once.
+// Cells that already live on the device (reo_set_matrix_pseudobulk_*_dev_*) are read where they are by the same two kernels: int32 or int64
+// index arrays -- checked by csc_device.hip's kernel first --, f64 / i64 / f32 / i32 values widened at the load and summed in f64 / i64.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -23,16 +25,17 @@ namespace {
 
 // dense: one thread per gene row, one workgroup column per output profile; the threads of a wave
 // read consecutive rows of the same cell column (coalesced), cells in the given order.
-template <class T>
-__global__ __launch_bounds__(256) void pb_dense(const T *__restrict__ X, int64_t ld, int G,
+// ValT: the cells' element type; AccT: the type they are summed in (Float32 / Int32 cells of a device matrix are widened as they are read)
+template <class ValT, class AccT>
+__global__ __launch_bounds__(256) void pb_dense(const ValT *__restrict__ X, int64_t ld, int G,
                                                 const int32_t *__restrict__ order,
-                                                const int32_t *__restrict__ chunk_ptr, T *__restrict__ out)
+                                                const int32_t *__restrict__ chunk_ptr, AccT *__restrict__ out)
 {
     const int g = blockIdx.x * 256 + threadIdx.x;
     const int o = blockIdx.y;
     if (g >= G) return;
-    T acc = 0;
-    for (int t = chunk_ptr[o]; t < chunk_ptr[o + 1]; ++t) acc += X[static_cast<int64_t>(order[t]) * ld + g];
+    AccT acc = 0;
+    for (int t = chunk_ptr[o]; t < chunk_ptr[o + 1]; ++t) acc += static_cast<AccT>(X[static_cast<int64_t>(order[t]) * ld + g]);
     out[static_cast<int64_t>(o) * G + g] = acc;
 }
 
@@ -54,9 +57,11 @@ struct PbCell {
     T v[kPbPer];
 };
 
-template <class T>
-__device__ __forceinline__ void pb_fetch(PbCell<T> &cell, const int64_t *__restrict__ colptr, const int32_t *__restrict__ rowidx,
-                                         const T *__restrict__ val, const int32_t *__restrict__ order, int t, int t_end)
+// IdxT: the row indices' type (a 64-bit index of a device matrix is narrowed to int as it is loaded: it has been checked, so it is below
+// 2^18, and a PbCell holds what it held); ValT / AccT as in pb_dense: the value is widened at the load
+template <class IdxT, class ValT, class AccT>
+__device__ __forceinline__ void pb_fetch(PbCell<AccT> &cell, const int64_t *__restrict__ colptr, const IdxT *__restrict__ rowidx,
+                                         const ValT *__restrict__ val, const int32_t *__restrict__ order, int t, int t_end)
 {
     cell.e0 = cell.e1 = 0;
 #pragma unroll
@@ -67,13 +72,13 @@ __device__ __forceinline__ void pb_fetch(PbCell<T> &cell, const int64_t *__restr
 #pragma unroll
     for (int i = 0; i < kPbPer; ++i) {
         const int64_t e = cell.e0 + static_cast<int64_t>(i) * kPbThreads + threadIdx.x;
-        if (e < cell.e1) { cell.r[i] = rowidx[e]; cell.v[i] = val[e]; }
+        if (e < cell.e1) { cell.r[i] = static_cast<int>(rowidx[e]); cell.v[i] = static_cast<AccT>(val[e]); }
     }
 }
 
-template <class T>
-__global__ __launch_bounds__(kPbThreads) void pb_csc(const int64_t *__restrict__ colptr, const int32_t *__restrict__ rowidx,
-                                                     const T *__restrict__ val, int G, const int32_t *__restrict__ order,
+template <class IdxT, class ValT, class T>
+__global__ __launch_bounds__(kPbThreads) void pb_csc(const int64_t *__restrict__ colptr, const IdxT *__restrict__ rowidx,
+                                                     const ValT *__restrict__ val, int G, const int32_t *__restrict__ order,
                                                      const int32_t *__restrict__ chunk_ptr, T *__restrict__ out)
 {
     __shared__ T acc[kPbRows];
@@ -94,8 +99,8 @@ __global__ __launch_bounds__(kPbThreads) void pb_csc(const int64_t *__restrict__
             for (int i = 0; i < kPbPer; ++i)
                 if (a.r[i] >= r0 && a.r[i] < r1) acc[a.r[i] - r0] += a.v[i];
             for (int64_t e = a.e0 + static_cast<int64_t>(kPbPer) * kPbThreads + threadIdx.x; e < a.e1; e += kPbThreads) {
-                const int r = rowidx[e];
-                if (r >= r0 && r < r1) acc[r - r0] += val[e];
+                const int r = static_cast<int>(rowidx[e]);
+                if (r >= r0 && r < r1) acc[r - r0] += static_cast<T>(val[e]);
             }
             pb_fetch(a, colptr, rowidx, val, order, t + d + kPbDepth, t1);
             __syncthreads();
@@ -138,7 +143,7 @@ int32_t run_dense(reo_ctx *c, const T *X, int64_t G, int64_t C, int64_t ld, cons
     if (e == hipSuccess) e = hipMemcpyAsync(dPtr.p, chunk_ptr, (n_out + 1) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
         tic(c, 7);
-        pb_dense<T><<<dim3(static_cast<unsigned>((G + 255) / 256), n_out), 256, 0, c->stream>>>(dX.p, G, static_cast<int>(G), dOrd.p, dPtr.p, dst);
+        pb_dense<T, T><<<dim3(static_cast<unsigned>((G + 255) / 256), n_out), 256, 0, c->stream>>>(dX.p, G, static_cast<int>(G), dOrd.p, dPtr.p, dst);
         toc(c);
         e = hipGetLastError();
     }
@@ -263,7 +268,7 @@ int32_t run_csc(reo_ctx *c, int64_t G, int64_t C, const int64_t *colptr, const i
     if (bad_row) { set_error("a row index is outside [0,%lld)", (long long)G); return REO_EINVAL; }
     if (e == hipSuccess) {
         tic(c, 7);
-        pb_csc<T><<<dim3(n_out, static_cast<unsigned>((G + kPbRows - 1) / kPbRows)), kPbThreads, 0, c->stream>>>(
+        pb_csc<int32_t, T, T><<<dim3(n_out, static_cast<unsigned>((G + kPbRows - 1) / kPbRows)), kPbThreads, 0, c->stream>>>(
             dCp.p, dRi.p, dVal.p, static_cast<int>(G), dOrd.p, dPtr.p, dst);
         toc(c);
         e = hipGetLastError();
@@ -320,6 +325,79 @@ int32_t pseudobulk_resident_csc(reo_ctx *c, bool is_int, int64_t G, int64_t C, c
     if (rc || (rc = check_csc(G, C, colptr, rowidx))) return rc;
     if (is_int) return run_csc<long long>(c, G, C, colptr, rowidx, static_cast<const long long *>(val), order, n_order, chunk_ptr, n_out, nullptr);
     return run_csc<double>(c, G, C, colptr, rowidx, static_cast<const double *>(val), order, n_order, chunk_ptr, n_out, nullptr);
+}
+
+// The cells already on the device (reo_set_matrix_pseudobulk_*_dev_*): no upload, the kernels read the caller's arrays where they are --
+// Float32 / Int32 cells widened at the load and summed in Float64 / Int64 -- and write the sums into c->dX_owned (G x n_out, ld = G).
+// order and chunk_ptr are the host arrays of the host entries.  dtype: 1 Float64, 2 Int64, 3 Float32, 4 Int32 cells.
+namespace {
+
+template <class Launch>
+int32_t run_device(reo_ctx *c, const char *what, int64_t G, const int32_t *order, int64_t n_order, const int32_t *chunk_ptr, int32_t n_out,
+                   Launch launch)
+{
+    DevBuf<int32_t> dOrd, dPtr;
+    int32_t rc;
+    if ((rc = c->dX_owned.ensure(static_cast<size_t>(G) * n_out * 8)) || (rc = dOrd.ensure(std::max<int64_t>(n_order, 1))) || (rc = dPtr.ensure(n_out + 1)))
+        return rc;
+    hipError_t e = hipSuccess;
+    if (n_order) e = hipMemcpyAsync(dOrd.p, order, n_order * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dPtr.p, chunk_ptr, (n_out + 1) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        tic(c, 7);
+        launch(dOrd.p, dPtr.p);
+        toc(c);
+        e = hipGetLastError();
+    }
+    const hipError_t es = hipStreamSynchronize(c->stream);   // the caller's arrays (and these buffers) have been read on every return
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) { set_error("pseudobulk (%s) failed: %s", what, hipGetErrorString(e)); return e == hipErrorOutOfMemory ? REO_ENOMEM : REO_EHIP; }
+    collect_timings(c);
+    return REO_OK;
+}
+
+}  // namespace
+
+int32_t pseudobulk_device_dense(reo_ctx *c, int dtype, const void *dX, int64_t G, int64_t C, int64_t ld, const int32_t *order, int64_t n_order,
+                                const int32_t *chunk_ptr, int32_t n_out)
+{
+    int32_t rc = check_args(c, G, C, order, n_order, chunk_ptr, n_out, dX, nullptr, true);
+    if (rc) return rc;
+    if (ld < G) { set_error("leading dimension < G"); return REO_EINVAL; }
+    return run_device(c, "dense, device", G, order, n_order, chunk_ptr, n_out, [&](const int32_t *dOrd, const int32_t *dPtr) {
+        const dim3 grid(static_cast<unsigned>((G + 255) / 256), n_out);
+        void *dst = c->dX_owned.p;
+        const int g = static_cast<int>(G);
+        switch (dtype) {
+        case 1: pb_dense<double, double><<<grid, 256, 0, c->stream>>>(static_cast<const double *>(dX), ld, g, dOrd, dPtr, static_cast<double *>(dst)); break;
+        case 3: pb_dense<float, double><<<grid, 256, 0, c->stream>>>(static_cast<const float *>(dX), ld, g, dOrd, dPtr, static_cast<double *>(dst)); break;
+        case 4: pb_dense<int32_t, long long><<<grid, 256, 0, c->stream>>>(static_cast<const int32_t *>(dX), ld, g, dOrd, dPtr, static_cast<long long *>(dst)); break;
+        default: pb_dense<long long, long long><<<grid, 256, 0, c->stream>>>(static_cast<const long long *>(dX), ld, g, dOrd, dPtr, static_cast<long long *>(dst)); break;
+        }
+    });
+}
+
+int32_t pseudobulk_device_csc(reo_ctx *c, int dtype, int64_t G, int64_t C, int64_t nnz, const void *d_colptr, const void *d_rowidx,
+                              int32_t index_bits, const void *d_val, const int32_t *order, int64_t n_order, const int32_t *chunk_ptr, int32_t n_out)
+{
+    int32_t rc = check_args(c, G, C, order, n_order, chunk_ptr, n_out, d_colptr, nullptr, true);
+    if (rc) return rc;
+    const int64_t *colptr = nullptr;
+    if ((rc = csc_device_check(c, G, C, nnz, d_colptr, d_rowidx, index_bits, d_val, &colptr))) return rc;   // before pb_csc addresses LDS by a row index
+    return run_device(c, "CSC, device", G, order, n_order, chunk_ptr, n_out, [&](const int32_t *dOrd, const int32_t *dPtr) {
+        const dim3 grid(n_out, static_cast<unsigned>((G + kPbRows - 1) / kPbRows));
+        void *dst = c->dX_owned.p;
+        const int g = static_cast<int>(G);
+        auto go = [&](auto *rows) {
+            switch (dtype) {
+            case 1: pb_csc<<<grid, kPbThreads, 0, c->stream>>>(colptr, rows, static_cast<const double *>(d_val), g, dOrd, dPtr, static_cast<double *>(dst)); break;
+            case 3: pb_csc<<<grid, kPbThreads, 0, c->stream>>>(colptr, rows, static_cast<const float *>(d_val), g, dOrd, dPtr, static_cast<double *>(dst)); break;
+            case 4: pb_csc<<<grid, kPbThreads, 0, c->stream>>>(colptr, rows, static_cast<const int32_t *>(d_val), g, dOrd, dPtr, static_cast<long long *>(dst)); break;
+            default: pb_csc<<<grid, kPbThreads, 0, c->stream>>>(colptr, rows, static_cast<const long long *>(d_val), g, dOrd, dPtr, static_cast<long long *>(dst)); break;
+            }
+        };
+        if (index_bits == 32) go(static_cast<const int32_t *>(d_rowidx)); else go(static_cast<const int64_t *>(d_rowidx));
+    });
 }
 
 }  // namespace reo

@@ -236,6 +236,7 @@ struct reo_ctx {
     int csc_upload = 0;                  // the last host matrix came as CSC (reo_set_matrix_csc_*; reo_get_info 22) ...
     int64_t csc_nnz = 0;                 // ... with this many stored entries (reo_get_info 23)
     reo::DevBuf<int64_t> csc_colptr;     // its column pointer, which t_csc_columns reads (transform.hip, CscUploader)
+    int csc_device = 0;                  // the matrix came from CSC arrays on the device (reo_set_matrix_csc_dev_*; reo_get_info 27)
     bool eager_k1 = false;               // reo_set_matrix has already launched the pair kernel of comparison 0 on this data, groups and thresholds
     int has_ties = 0;
     int transform_in_lds = 0;  // the last transform sorted each sample inside one workgroup's LDS (transform.hip)
@@ -358,6 +359,8 @@ enum { kLayoutColMajor = 0, kLayoutRowMajor = 1, kLayoutCsc = 2 };
 int32_t eager_upload(reo_ctx *c, const void *hX, int64_t hld, bool with_k1, bool host_i32 = false, int layout = kLayoutColMajor);
 int32_t upload_columns(reo_ctx *c, const void *hX, int64_t hld, int64_t G, int64_t ncols, void *dX, int dtype, int layout = kLayoutColMajor);  // a host matrix into a device matrix (ld = G), chunked, Int64 narrowed
 int32_t widen_device_i32(reo_ctx *c, const void *dX32, int64_t ld, int64_t G, int64_t S, void *dX64);  // a device Int32 matrix into a dense Int64 one, on c->stream
+int32_t densify_device_csc(reo_ctx *c, int64_t G, int64_t S, const int64_t *colptr, const void *rows, int32_t index_bits, const void *vals,
+                           int dtype, void *dX);  // a checked device CSC matrix into a dense one (ld = G), on c->stream
 int32_t ensure_upload_streams(reo_ctx *c);                                      // c->up, c->rk and their events (created on first use)
 int32_t ensure_staging(reo_ctx *c, size_t slot_bytes);                          // three pinned + device staging slots of at least that size, their events
 void host_parallel(int nthreads, int ntasks, const std::function<void(int)> &fn);   // fn(0 .. ntasks - 1) on the process-wide pool of host threads (and the caller)
@@ -394,6 +397,15 @@ int32_t pseudobulk_resident_dense(reo_ctx *c, const void *X, bool is_int, int64_
                                   int64_t n_order, const int32_t *chunk_ptr, int32_t n_out);
 int32_t pseudobulk_resident_csc(reo_ctx *c, bool is_int, int64_t G, int64_t C, const int64_t *colptr, const int32_t *rowidx, const void *val,
                                 const int32_t *order, int64_t n_order, const int32_t *chunk_ptr, int32_t n_out);
+// the cells on the device (reo_set_matrix_pseudobulk_*_dev_*): read where they are; dtype 1 Float64, 2 Int64, 3 Float32, 4 Int32 (summed in Float64 / Int64)
+int32_t pseudobulk_device_dense(reo_ctx *c, int dtype, const void *dX, int64_t G, int64_t C, int64_t ld, const int32_t *order, int64_t n_order,
+                                const int32_t *chunk_ptr, int32_t n_out);
+int32_t pseudobulk_device_csc(reo_ctx *c, int dtype, int64_t G, int64_t C, int64_t nnz, const void *d_colptr, const void *d_rowidx,
+                              int32_t index_bits, const void *d_val, const int32_t *order, int64_t n_order, const int32_t *chunk_ptr, int32_t n_out);
+// csc_device.hip: arguments and container of a device CSC matrix, checked by a kernel before anything indexes with them (csc_check.h);
+// *colptr64: the column pointer as int64 on the device (32-bit ones widened into c->csc_colptr)
+int32_t csc_device_check(reo_ctx *c, int64_t G, int64_t S, int64_t nnz, const void *d_colptr, const void *d_rowidx, int32_t index_bits,
+                         const void *d_val, const int64_t **colptr64);
 // filter.hip: the low-expression filters and the compaction of the resident matrix (reo_filter_matrix; host half: filter_maps.h)
 int32_t filter_matrix(reo_ctx *c, int64_t min_profiles, int64_t min_features, uint8_t *profile_kept, uint8_t *gene_kept,
                       int64_t *S_kept, int64_t *G_kept);

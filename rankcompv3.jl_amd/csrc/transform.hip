@@ -2546,6 +2546,36 @@ int32_t widen_device_i32(reo_ctx *c, const void *dX32, int64_t ld, int64_t G, in
     return REO_OK;
 }
 
+// A CSC matrix whose arrays are on the device (reo_set_matrix_csc_dev_*) into the dense matrix dX (ld = G), on the context's stream:
+// t_csc_columns over all S columns with e0 = 0, straight from the caller's arrays, which csc_device_check has checked (the kernel
+// searches and scatters by the row indices).  colptr: int64 on the device.  dtype as in upload_columns (4: Int32 values, Int64 matrix).
+// Launches of at most 65 535 columns keep gridDim.x in range whatever S is.
+int32_t densify_device_csc(reo_ctx *c, int64_t G, int64_t S, const int64_t *colptr, const void *rows, int32_t index_bits, const void *vals,
+                           int dtype, void *dX)
+{
+    auto go = [&](auto *r, auto *v, auto *dev) -> int32_t {
+        using RowT = std::remove_const_t<std::remove_pointer_t<decltype(r)>>;
+        using ValT = std::remove_const_t<std::remove_pointer_t<decltype(v)>>;
+        using W = std::remove_pointer_t<decltype(dev)>;
+        const unsigned tiles = static_cast<unsigned>((G + kCscTile - 1) / kCscTile);   // (G <= 262 143: 128 tiles)
+        for (int64_t p0 = 0; p0 < S; p0 += 65535) {
+            const unsigned np = static_cast<unsigned>(std::min<int64_t>(65535, S - p0));
+            t_csc_columns<RowT, ValT, W><<<dim3(np, tiles), 256, 0, c->stream>>>(colptr + p0, 0, r, v, dev + static_cast<size_t>(p0) * G, static_cast<int>(G));
+            REO_HIP_CHECK(hipGetLastError());
+        }
+        return REO_OK;
+    };
+    auto rows_as = [&](auto *v, auto *dev) -> int32_t {
+        return index_bits == 32 ? go(static_cast<const int32_t *>(rows), v, dev) : go(static_cast<const int64_t *>(rows), v, dev);
+    };
+    switch (dtype) {
+    case 1: return rows_as(static_cast<const double *>(vals), static_cast<double *>(dX));
+    case 3: return rows_as(static_cast<const float *>(vals), static_cast<float *>(dX));
+    case 4: return rows_as(static_cast<const int32_t *>(vals), static_cast<int64_t *>(dX));
+    default: return rows_as(static_cast<const int64_t *>(vals), static_cast<int64_t *>(dX));
+    }
+}
+
 int32_t eager_upload(reo_ctx *c, const void *hX, int64_t hld, bool with_k1, bool host_i32, int layout)
 {
     const bool rowmajor = layout == kLayoutRowMajor;

@@ -82,10 +82,14 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
     (_ffi.host_matrix_entry; opt-in until its timing has been recorded).
     A scipy.sparse matrix (CSR / COO / CSC: AnnData's X) goes up as CSC -- no toarray(), the zeros never exist on the host or on the
     link -- and becomes dense on the device (_ffi.csc_entry, reo_set_matrix_csc_*); the caller's matrix is not modified.
+    A sparse torch tensor on a ROCm device (sparse_csc, the .t() of a cells x genes sparse_csr, or COO / CSR through to_sparse_csc()) never
+    leaves the device: its index arrays are checked by a kernel and the matrix becomes dense where it is (_ffi.device_csc_entry,
+    reo_set_matrix_csc_dev_*).  The mirror does not canonicalise: unsorted or repeated row indices inside a column are refused.
     Two groups: one comparison, group 1 vs
     group 2 (the reference's `gnum == 2` path, :387-389,431-434).  More groups: one comparison per
     group, that group vs every other sample (:375-390,396-436), 16 more columns each."""
-    on_device = _ffi.is_device_tensor(data)   # a torch tensor on a ROCm device: used where it is (its device is the context's)
+    # a torch tensor on a ROCm device: a strided one is used where it is, a sparse one is made dense there (its device is the context's)
+    on_device = _ffi.is_device_sparse(data) or _ffi.is_device_tensor(data)
     if on_device:
         device = data.device.index if data.device.index is not None else -1
     elif not _ffi.is_sparse(data):   # (np.asarray of a sparse matrix is a 0-d object array)
@@ -162,13 +166,17 @@ class CellsDegRun(NamedTuple):
 def identify_degs_cells(cells, cell_group, gene_names, n_pseudo, pval_reo, pval_deg, padj_deg, ref_gene, n_iter, n_conv, *,
                         min_profiles: int = 0, min_features: int = 0, ref_gene_max: int = 3000, seed: int = 0, device: int = 0,
                         profile: bool = False) -> CellsDegRun:
-    """Cells to DEGs without a host trip for the profiles: `cells` is a genes x cells matrix (scipy.sparse or anything np.asarray takes),
+    """Cells to DEGs without a host trip for the profiles: `cells` is a genes x cells matrix (scipy.sparse, anything np.asarray takes, or
+    a torch tensor on a ROCm device -- sparse or strided -- which is read where it is: reo_set_matrix_pseudobulk_*_dev_*),
     cell_group one label per cell.  cells_partition -> the pseudo-bulk sums written into the context's matrix (set_matrix_pseudobulk) ->
     the reference's two low-expression filters on the device (filter_matrix, :618 / :626) -> groups of the kept profiles, thresholds,
     pair table and iteration as in run_identify_degs.  ref_gene is a bool mask over the INPUT genes (subset by gene_kept here), or None for
     synth.ref_mask(G', min(G', ref_gene_max), seed), the draw reoa makes.  Bit-identical to Context.pseudobulk -> numpy filters ->
     run_identify_degs on the same seed.  (reoa() keeps its host route: its writers want the profile matrix on the host.)"""
-    if not _ffi.is_sparse(cells):
+    on_device = _ffi.is_device_sparse(cells) or _ffi.is_device_tensor(cells)
+    if on_device:   # a torch tensor on a ROCm device, sparse or strided: summed where it is, on its own device
+        device = cells.device.index if cells.device.index is not None else -1
+    elif not _ffi.is_sparse(cells):
         cells = np.asarray(cells)
     if len(cells.shape) != 2:
         raise _ffi.DimensionMismatch(_ffi.REO_EINVAL, "'cells' must be a genes x cells matrix")
