@@ -639,6 +639,8 @@ int32_t reo_create(reo_ctx **out, int32_t device, uint64_t seed)
     if (const char *e = getenv("REO_K1_WAVE")) c->k1_wave = (e[0] != '0');
     if (const char *e = getenv("REO_K1_HALF")) c->k1_half = (e[0] != '0');
     if (const char *e = getenv("REO_K1_SLOTS")) c->k1_slots = (e[0] != '0');
+    if (const char *e = getenv("REO_K1_QUEUE")) c->k1_queue = (e[0] != '0');
+    if (const char *e = getenv("REO_K1_WORKERS")) c->k1_workers = std::max(1, atoi(e));
     if (const char *e = getenv("REO_K1_ORDER")) c->k1_order = std::max(0, std::min(2, atoi(e)));
     {
         int n = 0;
@@ -723,7 +725,7 @@ void reo_destroy(reo_ctx *c)
     release_event(c->ev_x, 0);
     for (auto &e : c->ev_k1) release_event(e, 0);
     c->t_pos16.release(); c->t_lo16.release(); c->t_hi16.release(); c->gcounts.release();
-    c->k1_slot_part.release(); c->k1_slot_maps.release(); c->pos_s.release(); c->lo_s.release();
+    c->k1_slot_part.release(); c->k1_slot_maps.release(); c->pos_s.release(); c->lo_s.release(); c->k1_queue_ctr.release();
     c->t_pos32.release(); c->t_lo32.release(); c->t_hi32.release(); c->t_vin32.release(); c->t_vout32.release();
     for (int t = 0; t < 2; ++t) { c->refbits[t].release(); c->refbytes[t].release(); }
     c->raw.release(); c->delta_list.release(); c->cont.release(); c->result.release(); c->sorted_d.release(); c->sorted_p.release();

@@ -96,9 +96,12 @@ inline std::vector<uint32_t> k1_item_list(const K1ItemGeom &g, const std::vector
     for (size_t k = 0; k < per; ++k)
         for (auto &l : lists)
             if (k < l.size()) items.push_back(l[k]);
-    // All items take the same time -- in the identity order.  (In slot order, k1_slots.h, they do not: a separated item lasts 10 us, the
-    // others about 100, the launch no longer proceeds in rounds, and neither this dealing of halves nor the levelling above is tuned for
-    // that; the list is the same for both orders.  DESIGN 3.2 and 9.)  So the resident waves (slots) work through the list in rounds; when the last
+    // All items take the same time -- in the identity order.  (In slot order, k1_slots.h, they do not: a separated item writes constant
+    // words and is gone, the others count for about 100 us.  There the list is not worked through in rounds of workgroups at all:
+    // resident waves take its items from eight queues, item 8 m + x being entry m of queue x, and a wave whose queue is dry takes from
+    // the others' -- k1_queue.h.  The list is the same for both orders: the levelling above still gives every queue the same NUMBER of
+    // items, not the same time, and the halves below still shorten only the tail of a launch in rounds; neither is tuned for slot
+    // order.  DESIGN 3.2 and 9.)  So the resident waves (slots) work through the list in rounds; when the last
     // round fills at most half of the slots, its items are dealt as two half-height items each (rows 0-15 and 16-31
     // of the tile: bit 15 set, bit 14 = which half) and the launch ends half an item's time earlier -- 0.45 of a round
     // out of 16.45 at config 3; a shard of one eighth of the tiles has 2.06 rounds.  Both halves of an item stay

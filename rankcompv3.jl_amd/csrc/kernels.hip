@@ -47,6 +47,7 @@
 #include "reo_internal.h"
 #include "k1_items.h"
 #include "k1_slots.h"
+#include "k1_queue.h"
 
 namespace reo {
 
@@ -276,6 +277,10 @@ struct K1Args {
     // only the table's ROW is looked up (s2g); the columns come back in gene order afterwards (k1_unslot_columns).  Else null.
     const uint32_t *s2g;         // [Gp] slot -> gene
     const uint32_t *trng, *crng; // [2 sides][Gp / 32], [2 sides][Gp / 256]: position ranges (min | max << 16) of the i-tiles and wave chunks
+    // ITEM QUEUES (k1w_pairs_slots; k1_queue.h): the launch has one workgroup per wave slot of the device, and each takes items of the
+    // list from these counters until none is left.  Null: workgroup b runs item b and ends (REO_K1_QUEUE=0, the A/B partner).
+    uint32_t *queue;             // [kQueueWords]: eight counters, kQueueStride words apart, zero before every launch
+    uint32_t n_items;            // length of `items`
 };
 constexpr size_t kParkSlot = 2 * 64 * 64;   // words per item: 64 count registers x 64 lanes, twice (32 KB)
 
@@ -374,6 +379,43 @@ __device__ __forceinline__ void emit_gene(const K1Args &a, int i0, int j, int bi
         } else {
             if (wH) atomicOr(row, wH);
             if (wL) atomicOr(row + a.Wp, wL);
+        }
+    }
+}
+
+// A SEPARATED item of the slot form (k1w_item): every pair of it has the same count n on its side -- the side's size or 0 -- so its words
+// are known without one row of emit_rows.  ONE class for the whole item, from the same comparisons as there (n >= hi_thr, else
+// n <= lo_thr, else neither: nothing to write).  Forward words of rows i0 + lane: the real columns (j < G, emit_gene's lanes_ok) of each
+// of the wave's four 64-gene blocks, in the class's plane; mirror word of every real column gene: all RI row bits -- a half-height
+// item: its 16-bit half -- in the swapped plane.  Rows from G on and blocks from Gp on are skipped as in emit_gene.
+// No atomicOr and no d > ii mask: a separated item is never diagonal and never near.  A tile inside its chunk never qualifies
+// (k1_slots.h, slot_separated: the ranges nest), and a live item's chunk does not end left of its tile's 64-gene block (k1_items.h), so
+// the chunk of a separated item begins at or beyond the end of the tile's own chunk: jw >= i0 + RI.
+// Only the plane that holds the ones is stored; the other plane stays as the clear in front of the launch left it (launch_k1).
+template <int RI>
+__device__ __forceinline__ void emit_constant(const K1Args &a, int i0, int jl, int side, int n)
+{
+    static_assert(kSlotChunk % 64 == 0 && kSlotChunk >= 64 && kSlotTile <= 64, "a tile's 64-gene block lies inside its chunk (slot_separated)");
+    const int lane = threadIdx.x, bi = i0 >> 6;
+    const int hi_thr = side ? a.m2 : a.m1, lo_thr = (side ? a.nt : a.nc) - hi_thr;
+    int fwd = side ? 2 : 0, mir = fwd;   // class L: forward words in the side's first plane, mirror words in its second (L and H swap)
+    if (n >= hi_thr) ++fwd;
+    else if (n <= lo_thr) ++mir;
+    else return;
+    const bool row_ok = lane < RI && i0 + lane < a.G;
+    uint32_t *frow = a.table + (static_cast<size_t>(row_ok ? a.s2g[i0 + lane] : 0u) * kPlanes + fwd) * a.Wp;
+#pragma unroll
+    for (int r = 0; r < kRJ; ++r) {
+        const int j = jl + 64 * r;
+        const int bj = __builtin_amdgcn_readfirstlane(j >> 6);
+        if ((bj << 6) >= a.Gp || bj <= bi) continue;   // (bj <= bi: never, see above; emit_gene's bj < bi plus the diagonal)
+        const unsigned long long lanes_ok = __ballot(j < a.G);
+        if (!lanes_ok) continue;
+        if (row_ok) *reinterpret_cast<uint2 *>(frow + 2 * bj) = uint2{static_cast<uint32_t>(lanes_ok), static_cast<uint32_t>(lanes_ok >> 32)};
+        if (j < a.G) {
+            uint32_t *row = a.table + (static_cast<size_t>(a.s2g[j]) * kPlanes + mir) * a.Wp + (i0 >> 5);
+            if (RI == 16) reinterpret_cast<uint16_t *>(row)[(i0 >> 4) & 1] = 0xFFFFu;   // (its half of the word, as in emit_gene)
+            else *row = 0xFFFFFFFFu;
         }
     }
 }
@@ -511,7 +553,7 @@ __device__ __forceinline__ void k1_loop(u32x8 &c0, u32x8 &c1, u32x8 &c2, u32x8 &
 // below every row gene in every sample, or above -- has the same count everywhere, the side's size or 0: the count loop is not
 // entered and the constants are classified like any other counts.
 template <int NB, bool TIES, int RI, bool SLOTS = false>
-__device__ __forceinline__ void k1w_item(const K1Args &a, uint4 *ring, int i0, int jw, int side, unsigned long long t_begin)
+__device__ __forceinline__ void k1w_item(const K1Args &a, uint4 *ring, uint32_t idx, int i0, int jw, int side, unsigned long long t_begin)
 {
     constexpr int RJ = kRJ, NE = TIES ? 2 : 1;
     constexpr bool BIG = NB > 16;
@@ -532,8 +574,9 @@ __device__ __forceinline__ void k1w_item(const K1Args &a, uint4 *ring, int i0, i
     int sep = 0;   // wave-uniform: two scalar loads (a half-height item: its 32-row tile's range)
     if constexpr (SLOTS) sep = __builtin_amdgcn_readfirstlane(slot_separated(a.trng[side * (a.Gp >> 5) + (i0 >> 5)], a.crng[side * (a.Gp >> 8) + (jw >> 8)]));
     if (SLOTS && sep) {
-        const uint32_t ns = static_cast<uint32_t>(side ? a.nt : a.nc), v = sep > 0 ? (ns | ns << 16) : 0u;
-        gt0 = v; gt1 = v; gt2 = v; gt3 = v;
+        // the words are written at once (emit_constant): no count registers, no emit_gene.  (One way through the item for both kinds,
+        // no return from here: the worker loop of k1w_pairs_slots keeps ONE back edge, and with it its registers.)
+        emit_constant<RI>(a, i0, jl, side, sep > 0 ? (side ? a.nt : a.nc) : 0);
     } else if (be > bb) {
         const char *pb = reinterpret_cast<const char *>(a.P) + static_cast<size_t>(bb) * LQ * a.Gp * 16;
         const size_t aoff = (static_cast<size_t>(bb) * a.Gp + i0) * ROWB;
@@ -559,9 +602,9 @@ __device__ __forceinline__ void k1w_item(const K1Args &a, uint4 *ring, int i0, i
         for (int h = 0; h < ((TIES && !PARK_REGS) ? RJ * (RI / 2) : 1); ++h) park[h] = 0;
     }
     if (a.stamps) t_emit = __builtin_amdgcn_s_memrealtime();
-    if (a.park_mode) {   // (wave-uniform) range items: the counts of the side's earlier sample blocks come in, or these go out
+    if (!SLOTS && a.park_mode) {   // (wave-uniform; never in slot order) range items: the counts of the side's earlier sample blocks come in, or these go out
         constexpr int W4 = RI / 8;   // uint4 per gene and lane
-        uint4 *slot = reinterpret_cast<uint4 *>(a.park + static_cast<size_t>(blockIdx.x) * kParkSlot) + lane;   // [gene c][q][64 lanes]
+        uint4 *slot = reinterpret_cast<uint4 *>(a.park + static_cast<size_t>(idx) * kParkSlot) + lane;   // [gene c][q][64 lanes]
         auto add4 = [&](Counts &v, const uint4 *p) {
 #pragma unroll
             for (int q = 0; q < W4; ++q) { const uint4 w = p[q * 64]; v[4 * q] += w.x; v[4 * q + 1] += w.y; v[4 * q + 2] += w.z; v[4 * q + 3] += w.w; }   // (no carry between the halves: a count is at most S < 65 536)
@@ -572,7 +615,7 @@ __device__ __forceinline__ void k1w_item(const K1Args &a, uint4 *ring, int i0, i
         };
         if (a.park_mode & 1) {
             // n_ge of the earlier blocks: parked by the tie form, or equal to their n_gt (the tie-free form ran: no tie in those samples)
-            const uint4 *ge_from = slot + ((TIES && __builtin_amdgcn_readfirstlane(a.park_ge[blockIdx.x])) ? 4 * W4 * 64 : 0);
+            const uint4 *ge_from = slot + ((TIES && __builtin_amdgcn_readfirstlane(a.park_ge[idx])) ? 4 * W4 * 64 : 0);
             if constexpr (TIES && PARK_REGS) { add4(ge0, ge_from); add4(ge1, ge_from + W4 * 64); add4(ge2, ge_from + 2 * W4 * 64); add4(ge3, ge_from + 3 * W4 * 64); }
             else if constexpr (TIES) {   // (n_ge waits in the private segment: a real loop, one line at a time -- unrolled it took 64 more registers)
 #pragma clang loop unroll(disable)
@@ -588,7 +631,7 @@ __device__ __forceinline__ void k1w_item(const K1Args &a, uint4 *ring, int i0, i
 #pragma clang loop unroll(disable)
                 for (int cq = 0; cq < 4 * W4; ++cq) ge_to[cq * 64] = uint4{park[4 * cq], park[4 * cq + 1], park[4 * cq + 2], park[4 * cq + 3]};
             }
-            if (lane == 0) a.park_ge[blockIdx.x] = TIES ? 1 : 0;
+            if (lane == 0) a.park_ge[idx] = TIES ? 1 : 0;
             return;   // the side's last range classifies
         }
     }
@@ -597,7 +640,7 @@ __device__ __forceinline__ void k1w_item(const K1Args &a, uint4 *ring, int i0, i
     // the four genes one after the other in a real loop (the count registers rotate): a quarter of the code of the
     // unrolled form (41 KB beside a 20 KB count loop)
 #pragma clang loop unroll(disable)
-    for (int r = 0; r < RJ; ++r) {
+    for (int r = 0; r < ((SLOTS && sep) ? 0 : RJ); ++r) {
         const Counts cur = gt0;
         Counts cge = 0;
         if constexpr (TIES && PARK_REGS) cge = ge0;
@@ -623,7 +666,7 @@ __device__ __forceinline__ void k1w_item(const K1Args &a, uint4 *ring, int i0, i
         if constexpr (TIES && PARK_REGS) { ge0 = ge1; ge1 = ge2; ge2 = ge3; }
     }
     if (a.stamps && lane == 0) {
-        unsigned long long *st = a.stamps + static_cast<size_t>(blockIdx.x) * 4;
+        unsigned long long *st = a.stamps + static_cast<size_t>(idx) * 4;
         st[0] = t_begin; st[1] = t_loop; st[2] = t_emit; st[3] = __builtin_amdgcn_s_memrealtime();
     }
 }
@@ -635,20 +678,20 @@ __device__ __forceinline__ void k1w_item(const K1Args &a, uint4 *ring, int i0, i
 // More than 65 535 genes (NB = 17, 18): the big plane layout of transform.hip (five pos quads per gene and block, edge
 // rows of 8 uint4), 180 registers, two waves per SIMD.
 template <int NB, bool TIES, bool SLOTS = false>
-__device__ __forceinline__ void k1w_body(const K1Args &a, uint4 *ring)
+__device__ __forceinline__ void k1w_body(const K1Args &a, uint4 *ring, uint32_t idx)   // idx: the item's place in the list (its park slot, its stamps)
 {
     constexpr int RI = kTileI, RJ = kRJ;
     const unsigned long long t_begin = a.stamps ? __builtin_amdgcn_s_memrealtime() : 0;
     // item: side << 31 | wave chunk << 16 | half-height << 15 | which half << 14 | i-tile
-    const uint32_t item = a.items[blockIdx.x];
+    const uint32_t item = a.items[idx];
     const int jw = __builtin_amdgcn_readfirstlane(static_cast<int>((item >> 16) & 0x7FFFu) * (64 * RJ));
     const int side = __builtin_amdgcn_readfirstlane(static_cast<int>(item >> 31));
     const int tile0 = static_cast<int>(item & 0x3FFFu) * RI;
     if (__builtin_amdgcn_readfirstlane(static_cast<int>(item & 0x8000u))) {
         const int i0 = __builtin_amdgcn_readfirstlane(tile0 + ((item & 0x4000u) ? RI / 2 : 0));
-        k1w_item<NB, TIES, RI / 2, SLOTS>(a, ring, i0, jw, side, t_begin);
+        k1w_item<NB, TIES, RI / 2, SLOTS>(a, ring, idx, i0, jw, side, t_begin);
     } else {
-        k1w_item<NB, TIES, RI, SLOTS>(a, ring, __builtin_amdgcn_readfirstlane(tile0), jw, side, t_begin);
+        k1w_item<NB, TIES, RI, SLOTS>(a, ring, idx, __builtin_amdgcn_readfirstlane(tile0), jw, side, t_begin);
     }
 }
 
@@ -658,7 +701,7 @@ __global__ __launch_bounds__(64, NB > 16 ? 2 : 3) void k1w_pairs(K1Args a)
     constexpr int RI = kTileI;
     constexpr int ROWB = NB > 16 ? 128 : 64;
     __shared__ uint4 ring[2 * RI * ROWB / 16];  // two slots of one block's tile operand: 2 x 2 KB (4 KB)
-    k1w_body<NB, TIES>(a, ring);
+    k1w_body<NB, TIES>(a, ring, blockIdx.x);
 }
 
 // The tie-free form in SLOT ORDER (at most 65 535 genes): its own instantiation, so that the identity order's code does not change.
@@ -667,7 +710,35 @@ __global__ __launch_bounds__(64, 3) void k1w_pairs_slots(K1Args a)
 {
     static_assert(NB <= 16, "slot order: 16-bit positions");
     __shared__ uint4 ring[2 * kTileI * 64 / 16];
-    k1w_body<NB, false, true>(a, ring);
+    // A resident wave that takes items until the list is exhausted (k1_queue.h): its own label's queue first, then the others'.  One
+    // lane draws, relaxed and at agent scope -- nothing but the uniqueness of the number is needed: an item reads what earlier launches
+    // wrote and writes words that no other item writes (the halves of a half-height pair: different 16-bit halves).  No workgroup ever
+    // waits for another: no flag, no spin, no barrier across workgroups, so the launch needs no co-residency.
+    // Without counters (a.queue null, wave-uniform: REO_K1_QUEUE=0) the workgroup runs item blockIdx.x and ends -- the same copy of the code.
+    // The ring (LDS) is reused from item to item without a wait of its own: the generated loop ends with s_waitcnt vmcnt(0) lgkmcnt(0)
+    // (gen_k1_loop.py), i.e. every LDS-DMA write and every LDS read of an item has completed before the next item's first one.
+    const bool pull = a.queue != nullptr;
+    const int x = static_cast<int>(blockIdx.x) & (kQueues - 1);
+    int s = 0;   // queues given up so far
+#pragma clang loop unroll(disable)
+    for (;;) {
+        uint32_t idx = blockIdx.x;
+        if (pull) {
+            bool got = false;
+#pragma clang loop unroll(disable)
+            while (s < kQueues) {
+                const int q = queue_steal(x, s);
+                uint32_t m = 0;
+                if (threadIdx.x == 0) m = __hip_atomic_fetch_add(a.queue + q * kQueueStride, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                m = __builtin_amdgcn_readfirstlane(m);
+                if (m < queue_len(a.n_items, q)) { idx = queue_index(q, m); got = true; break; }
+                ++s;   // dry: the next queue
+            }
+            if (!got) break;
+        }
+        k1w_body<NB, false, true>(a, ring, idx);
+        if (!pull) break;
+    }
 }
 
 // ---- slot order: the small kernels around the pair kernel (launch_k1 -> k1_slots; the rules: k1_slots.h)
@@ -848,8 +919,8 @@ __global__ __launch_bounds__(64, NB > 16 ? 2 : 3) void k1w_pairs_gated(K1Args a)
     __shared__ uint4 ring[2 * RI * ROWB / 16];
     const int bad = a.gate[0] | a.gate[4] | a.gate[5], ties = a.gate[1];   // (wave-uniform: scalar loads)
     if (bad) return;
-    if (ties) k1w_body<NB, true>(a, ring);
-    else k1w_body<NB, false>(a, ring);
+    if (ties) k1w_body<NB, true>(a, ring, blockIdx.x);
+    else k1w_body<NB, false>(a, ring, blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------
@@ -3945,7 +4016,11 @@ static void launch_pairs(reo_ctx *c, const K1Args &a, const K1Plan &pl)
         if (gridw == 0) return;
         if constexpr (kWg) {
             if (a.gate) { k1w_pairs_gated<NB><<<gridw, 64, 0, c->stream>>>(a); return; }   // the tie form is chosen on the device (K1Args::gate)
-            if (pl.slots) { k1w_pairs_slots<NB><<<gridw, 64, 0, c->stream>>>(a); return; }  // tie-free, genes in slot order (k1_slots)
+            if (pl.slots) {   // tie-free, genes in slot order (k1_slots); with the item queues: one workgroup per wave slot of the device (k1_queue.h)
+                const unsigned workers = a.queue ? queue_workers(gridw, c->n_cus, c->k1_workers) : gridw;
+                k1w_pairs_slots<NB><<<workers, 64, 0, c->stream>>>(a);
+                return;
+            }
         }
         by_ties([&](auto t) { k1w_pairs<NB, decltype(t)::value><<<gridw, 64, 0, c->stream>>>(a); });
     } else if constexpr (kWg)
@@ -4163,6 +4238,7 @@ static K1Args k1_args(const reo_ctx *c, int k)
     a.items = nullptr; a.stamps = nullptr; a.gate = nullptr;
     a.park = nullptr; a.park_ge = nullptr; a.park_mode = 0;
     a.s2g = nullptr; a.trng = nullptr; a.crng = nullptr;
+    a.queue = nullptr; a.n_items = 0;
     return a;
 }
 
@@ -4232,6 +4308,8 @@ static int32_t k1_slots_alloc(reo_ctx *c)
     if ((rc = c->k1_slot_part.ensure(static_cast<size_t>(kSlotSplits) * 2 * c->Gp)) || (rc = c->k1_slot_maps.ensure(slot_maps_words(c->Gp))) ||
         (rc = c->pos_s.ensure(nq)) || (rc = c->lo_s.ensure(nq)))
         return rc;
+    // the item queues' counters; without them the one-item-per-workgroup launch (the caller of this one clears the error state)
+    if (c->k1_queue && c->k1_queue_ctr.ensure(kQueueWords)) (void)hipGetLastError();
     return REO_OK;
 }
 
@@ -4251,6 +4329,12 @@ static int32_t k1_slots_front(reo_ctx *c, K1Args &a)
     REO_HIP_CHECK(hipGetLastError());
     a.P = c->pos_s.p; a.AL = c->lo_s.p; a.AH = c->lo_s.p;   // (the tie-free form reads no hi planes)
     a.s2g = m.s2g; a.trng = m.trng; a.crng = m.crng;
+    // the item queues start at zero for EVERY launch (a launch leaves each counter beyond its queue's length)
+    a.n_items = static_cast<uint32_t>(c->k1_items_n);
+    if (c->k1_queue && c->k1_queue_ctr.p && c->k1_queue_ctr.n >= static_cast<size_t>(kQueueWords)) {
+        REO_HIP_CHECK(hipMemsetAsync(c->k1_queue_ctr.p, 0, kQueueWords * sizeof(uint32_t), c->stream));
+        a.queue = c->k1_queue_ctr.p;
+    }
     return REO_OK;
 }
 
@@ -4338,6 +4422,7 @@ int32_t launch_k1(reo_ctx *c, int k, int sides, bool keep_table, const int32_t *
     // (every reader of the table -- the passes, the pack, a sum hook's element count, the scan of a hook's table -- works on
     //  G * kPlanes * Wp words, which is also what the transform's early clear covers; a grow-only buffer may be larger)
     if (!keep_table) {
+        // (the slot form's constant emit relies on this clear: a separated item stores only the plane that holds its ones, emit_constant)
         if (!c->table_prezeroed) REO_HIP_CHECK(hipMemsetAsync(c->table.p, 0, static_cast<size_t>(c->G) * kPlanes * c->Wp * sizeof(uint32_t), c->stream));
         c->table_prezeroed = false;
     }

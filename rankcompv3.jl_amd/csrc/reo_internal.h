@@ -268,6 +268,10 @@ struct reo_ctx {
     reo::DevBuf<uint32_t> k1_slot_part; // [kSlotSplits][2][Gp] the sides' position ranges of every gene over a slice of the samples (min | max << 16)
     reo::DevBuf<uint32_t> k1_slot_maps; // [2][Gp] ranges per side, [Gp] keys, [Gp] g2s, [Gp] s2g, [2][Gp / 32] tile ranges, [2][Gp / 256] chunk ranges, [2] a count
     reo::DevBuf<uint4> pos_s, lo_s;     // the pos and lo planes in slot order (the layouts of pos and lo)
+    // item queues of the slot form (kernels.hip, k1w_pairs_slots; index rules: k1_queue.h): resident waves take items from eight counters
+    int k1_queue = 1;                   // REO_K1_QUEUE=0: one workgroup per item, as the identity order's kernels (A/B, tests)
+    int k1_workers = 0;                 // REO_K1_WORKERS=n (tests): workgroups of the launch instead of CUs x 4 SIMDs x 3 waves
+    reo::DevBuf<uint32_t> k1_queue_ctr; // [kQueueWords] the counters, each on its own 128-byte line; cleared on the stream before every launch
     int n_cus = 256;                    // compute units of the device (the wave form's item slots = CUs x 4 SIMDs x waves per SIMD)
     int share_counts = 1;               // REO_SHARE_GROUP_COUNTS=0 recounts per comparison instead
     int last_k1_shared = 0;             // reo_get_info: how the last class table was built
