@@ -272,6 +272,39 @@ int32_t reo_identify_degs(reo_ctx *ctx, const uint8_t *ref0, double pval_deg, do
                           int32_t n_iter, int32_t n_conv, double *result,
                           int32_t *iters_run, int32_t *trace);
 
+/* The reference set behind the returned tallies.  ref_mask (G bytes, 0 / 1) receives the mask over which the last reo_identify_degs on the
+ * current class table counted the n11 .. n33 it returned -- ref_gene_vec of its last executed pass (src/RankCompV3.jl:399-424): ref0 when one
+ * pass ran, otherwise the `inds` of the pass before the last -- and *nref (may be NULL) its number of genes.  The labels of `result` do NOT
+ * give this set: they are the last pass's own `inds`, the set a further pass would have used.  The rule holds however the loop ended
+ * (converged, n_iter exhausted on either kind of pass, whole periods skipped by the cycle watch); reo_tally(ctx, ref_mask) reproduces
+ * result[:, 2:11] exactly.  The mask is read where the passes left it: reo_identify_degs does no extra work for it.
+ * REO_EINVAL, with a message that says why, when there is no such mask or it is out of date: before any reo_identify_degs, after a failed
+ * one or one with n_iter <= 0, and after reo_tally (it uploads its own mask into the iteration's buffers), reo_build_pairs, any
+ * reo_set_matrix_*, reo_filter_matrix, reo_set_groups, reo_set_shard or a change of the thresholds.  A wrong mask is never delivered. */
+int32_t reo_get_ref_mask(reo_ctx *ctx, uint8_t *ref_mask /* G bytes, 0 / 1 */, int32_t *nref /* may be NULL */);
+
+/* Pair lists: WHICH partner genes make up a gene's tallies.  The reference has no such output (its R BitArray dies inside identify_degs,
+ * src/RankCompV3.jl:363-392); the class table of reo_build_pairs holds every pair, and this call extracts rows of it on the device.
+ * For query q, gene i = genes[q] (any order, repeats allowed, each entry is its own row), partner[rowptr[q] .. rowptr[q+1]) lists in ascending
+ * order every gene j != i with partner_mask[j] != 0 whose ordered pair (i, j), seen from gene i, has a selected class, and code[...] holds that
+ * class: 3*(ic-1)+(it-1) in 0..8, what reo_get_codes returns, the position of the pair's tally among n11 .. n33.  class_mask bit c selects
+ * class c (0x1 .. 0x1FF; n13 | n31, the reversed pairs, is 0x44).  partner_mask NULL = the mask of reo_get_ref_mask, read where it lies;
+ * row q then has result[i, 2 + c] entries of class c (the diagonal contributes nothing, as in :403).
+ * rowptr has n_genes + 1 entries (64-bit), partner and code `capacity` entries.  partner == NULL (then code is NULL and capacity 0): count
+ * only, rowptr is still filled -- call once to size the arrays, once to fill them.  With arrays and rowptr[n_genes] > capacity: REO_EINVAL,
+ * the message names the needed total, rowptr is delivered and nothing is written to partner / code.
+ * Two kernels on the context's stream, one wave per query row (csrc/pairlist.hip): a count pass, whose n_genes counts visit the host for
+ * the prefix sums, and a fill pass; device temporaries are sized from the counted total.  Should the two passes ever disagree about a row,
+ * nothing is written outside that row's range and the call answers REO_EHIP.
+ * Host arrays only; totals above 2^31 entries have not been run (the offsets are 64-bit).
+ * REO_EINVAL, each with its own message: no class table; a NULL genes or rowptr; n_genes < 1 (or above 2^30); a gene outside [0, G); a class_mask of 0 or with
+ * bits above 8; partner without code (or the reverse) or a negative capacity; a NULL partner_mask while reo_get_ref_mask would refuse; a
+ * reo_create_multi context.  An incomplete sharded table: REO_ECOMM, as reo_tally. */
+int32_t reo_pair_list(reo_ctx *ctx, const int32_t *genes, int64_t n_genes,
+                      const uint8_t *partner_mask /* G bytes; NULL = the mask of reo_get_ref_mask */,
+                      uint32_t class_mask /* bit c selects class code c = 3*(ic-1)+(it-1), c in 0..8; 1..0x1FF */,
+                      int64_t *rowptr /* n_genes + 1 */, int32_t *partner, uint8_t *code, int64_t capacity);
+
 /* McCullagh test on 3x3 tables given as 9 tallies each (n x 9 row-major),
  * evaluated by the device routine the iteration uses; out is n x 5 row-major
  * (pval, delta1, delta2, se, z1) -- src/RankCompV3.jl:225-259. */

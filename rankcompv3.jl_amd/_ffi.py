@@ -8,6 +8,7 @@ from __future__ import annotations
 import ctypes
 import os
 import subprocess
+from typing import NamedTuple
 
 import numpy as np
 
@@ -31,7 +32,7 @@ SYMBOLS = [
     "reo_set_profiling", "reo_reset_timings", "reo_get_timings", "reo_get_info",
     "reo_pseudobulk_dense_f64", "reo_pseudobulk_dense_i64", "reo_pseudobulk_csc_f64", "reo_pseudobulk_csc_i64",
     "reo_set_matrix_pseudobulk_dense_f64", "reo_set_matrix_pseudobulk_dense_i64", "reo_set_matrix_pseudobulk_csc_f64", "reo_set_matrix_pseudobulk_csc_i64",
-    "reo_filter_matrix", "reo_get_matrix",
+    "reo_filter_matrix", "reo_get_matrix", "reo_get_ref_mask", "reo_pair_list",
 ] + [f"reo_set_matrix_{form}_{t}" for form in ("csc_dev", "pseudobulk_csc_dev", "pseudobulk_dense_dev") for t in ("f64", "i64", "f32", "i32")]
 
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p)
@@ -134,6 +135,8 @@ def lib() -> ctypes.CDLL:
         "reo_set_matrix_pseudobulk_csc_i64": (i32, [vp, i64, i64, vp, vp, vp, vp, i64, vp, i32]),
         "reo_filter_matrix": (i32, [vp, i64, i64, vp, vp, vp, vp]),
         "reo_get_matrix": (i32, [vp, vp, i64]),
+        "reo_get_ref_mask": (i32, [vp, vp, vp]),
+        "reo_pair_list": (i32, [vp, vp, i64, vp, ctypes.c_uint32, vp, vp, vp, i64]),
     }
     for t in ("f64", "i64", "f32", "i32"):   # SPARSE ON THE DEVICE
         sig["reo_set_matrix_csc_dev_" + t] = (i32, [vp, i64, i64, i64, vp, vp, i32, vp])
@@ -258,6 +261,57 @@ def csc_entry(M):
     rowidx = np.ascontiguousarray(m.indices, dtype=np.int32)
     colptr = np.ascontiguousarray(m.indptr, dtype=np.int64)
     return "reo_set_matrix_csc_" + _NATIVE[want], colptr, rowidx, val, int(G), int(S)
+
+
+# the nine classes of an ordered pair in the order of their codes 3*(ic-1)+(it-1): the tally columns of the result (hotpath.HEADER[2:11])
+CLASS_NAMES = ("n11", "n12", "n13", "n21", "n22", "n23", "n31", "n32", "n33")
+CLASS_ALL = 0x1FF
+
+
+def class_mask(classes) -> int:
+    """The class_mask of reo_pair_list from a selection.  Pure: no library, no GPU.  An int is the mask itself (bit c selects class code c);
+    "reversed" is {n13, n31}, the pairs whose order is stable one way in one group and the other way in the other; a name "n11" .. "n33" or
+    an iterable of names and / or codes 0 .. 8 selects those.  Anything that selects no class, an unknown name, a code outside 0 .. 8 and a mask
+    outside 1 .. 0x1FF raise DimensionMismatch."""
+    def bad(why):
+        return DimensionMismatch(REO_EINVAL, f"pair classes {classes!r}: {why}")
+    if isinstance(classes, (bool, np.bool_)) or classes is None:
+        raise bad("a mask, \"reversed\", or names / codes are needed")
+    if isinstance(classes, (int, np.integer)):
+        m = int(classes)
+        if m < 1 or m > CLASS_ALL:
+            raise bad("a mask lies in 1 .. 0x1FF (bit c selects class code c)")
+        return m
+    if isinstance(classes, str):
+        classes = [classes]
+    m = 0
+    for c in classes:
+        if isinstance(c, str):
+            if c == "reversed":
+                m |= (1 << 2) | (1 << 6)
+            elif c in CLASS_NAMES:
+                m |= 1 << CLASS_NAMES.index(c)
+            else:
+                raise bad(f"{c!r} is not one of {', '.join(CLASS_NAMES)} or \"reversed\"")
+        elif isinstance(c, (int, np.integer)) and not isinstance(c, (bool, np.bool_)) and 0 <= int(c) <= 8:
+            m |= 1 << int(c)
+        else:
+            raise bad(f"{c!r} is not a class code 0 .. 8")
+    if m == 0:
+        raise bad("no class selected")
+    return m
+
+
+class PairList(NamedTuple):
+    """reo_pair_list's CSR: partner[rowptr[q]:rowptr[q + 1]] are the partners of genes[q], ascending, and code[...] their class codes."""
+    genes: np.ndarray      # int32, the queries as given
+    rowptr: np.ndarray     # int64, len(genes) + 1
+    partner: np.ndarray    # int32
+    code: np.ndarray       # uint8, index into CLASS_NAMES
+
+    def row(self, q: int):
+        a, b = int(self.rowptr[q]), int(self.rowptr[q + 1])
+        return self.partner[a:b], self.code[a:b]
 
 
 UNIQUE_ID_BYTES = 128
@@ -513,6 +567,40 @@ class Context:
         check(self._L.reo_identify_degs(self._h, _ptr(ref), float(pval_deg), float(padj_deg), int(n_iter), int(n_conv),
                                         _ptr(result), ctypes.byref(iters), _ptr(trace)))
         return result, iters.value, [tuple(int(v) for v in t) for t in trace[: iters.value]]
+
+    def ref_mask(self) -> np.ndarray:
+        """reo_get_ref_mask: the reference set (bool over the genes) that the last identify_degs counted its returned tallies over --
+        tally(ref_mask()) equals result[:, 2:11].  Raises DimensionMismatch when there is none or it is out of date."""
+        m = np.zeros(max(self.G, 1), dtype=np.uint8)
+        check(self._L.reo_get_ref_mask(self._h, _ptr(m), None))
+        return m[: self.G].astype(bool)
+
+    def pair_list_raw(self, genes, mask: int, partner_mask, rowptr, partner, code, capacity: int) -> None:
+        """reo_pair_list on caller-made arrays (partner and code None: count only); pair_list is the convenient form."""
+        check(self._L.reo_pair_list(self._h, _ptr(genes) if genes is not None and genes.size else None, 0 if genes is None else genes.size,
+                                    None if partner_mask is None else _ptr(partner_mask), ctypes.c_uint32(mask & 0xFFFFFFFF),
+                                    None if rowptr is None else _ptr(rowptr), None if partner is None else _ptr(partner),
+                                    None if code is None else _ptr(code), int(capacity)))
+
+    def pair_list(self, genes, classes, partner_mask=None) -> PairList:
+        """The partner genes behind the tallies of `genes` (reo_pair_list): for every query gene the partners j, ascending, with
+        partner_mask[j] set (None: the reference set of the last identify_degs, ref_mask()) whose pair with it has one of `classes` -- an
+        int mask, names "n11" .. "n33", codes 0 .. 8 or "reversed" (class_mask).  Counts first, allocates, then fills."""
+        mask = class_mask(classes)
+        g = np.ascontiguousarray(genes, dtype=np.int32).reshape(-1)
+        pm = None
+        if partner_mask is not None:
+            pm = np.ascontiguousarray(np.asarray(partner_mask) != 0, dtype=np.uint8)
+            if pm.size != self.G:
+                raise DimensionMismatch(REO_EINVAL, "partner mask length != number of genes")
+        rowptr = np.zeros(g.size + 1, dtype=np.int64)
+        self.pair_list_raw(g, mask, pm, rowptr, None, None, 0)
+        total = int(rowptr[-1])
+        partner = np.zeros(total, dtype=np.int32)
+        code = np.zeros(total, dtype=np.uint8)
+        if total:
+            self.pair_list_raw(g, mask, pm, rowptr, partner, code, total)
+        return PairList(g, rowptr, partner, code)
 
     def mccullagh(self, cont) -> np.ndarray:
         cont = np.ascontiguousarray(cont, dtype=np.int32).reshape(-1, 9)

@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "pair_list.h"
 #include "reo_internal.h"
 #include "upload_csc.h"
 
@@ -307,6 +308,14 @@ static double wall_us()
     return ts.tv_sec * 1e6 + ts.tv_nsec * 1e-3;
 }
 
+// The reference set that reo_get_ref_mask hands out (reo_internal.h, ref_slot) is gone or out of date, and why: whatever overwrites a mask
+// slot, replaces the class table or changes what it was built from says so here.  reo_identify_degs alone makes it valid again.
+static void drop_ref_mask(reo_ctx *c, const char *why)
+{
+    c->ref_slot = -1;
+    c->ref_gone = why;
+}
+
 // The wait of a call that may be the first to see an asynchronous failure of the pair kernel (reo_build_pairs returns with
 // it in flight on one GPU): the table cannot be trusted then, and a retry must rebuild it.
 static int32_t wait_or_drop_table(reo_ctx *c)
@@ -315,6 +324,7 @@ static int32_t wait_or_drop_table(reo_ctx *c)
     if (e == hipSuccess) return REO_OK;
     c->built_k = -1;
     c->table_complete = false;
+    drop_ref_mask(c, "a kernel queued on this context failed and the class table was dropped");
     set_error("a kernel queued on this context failed: %s (the class table was dropped: call reo_build_pairs again)", hipGetErrorString(e));
     return REO_EHIP;
 }
@@ -346,6 +356,8 @@ static int32_t use(reo_ctx *c)
 
 static void invalidate(reo_ctx *c)
 {
+    drop_ref_mask(c, "the matrix or the groups changed after the last reo_identify_degs (reo_set_matrix_*, reo_filter_matrix, reo_set_groups): "
+                     "the class table it ran on is gone");
     c->transformed = false;
     c->built_k = -1;
     c->gc_valid = false;
@@ -581,7 +593,7 @@ using namespace reo;
 
 extern "C" {
 
-int32_t reo_version(void) { return 500; }
+int32_t reo_version(void) { return 600; }
 
 int32_t reo_trim_memory(void)
 {
@@ -747,6 +759,7 @@ int32_t reo_set_shard(reo_ctx *c, int32_t rank, int32_t world)
     if (!c->peers.empty()) { set_error("a multi-GPU context (reo_create_multi) shards by itself"); return REO_EINVAL; }
     c->rank = rank; c->world = world;
     c->built_k = -1;
+    drop_ref_mask(c, "reo_set_shard dropped the class table that the last reo_identify_degs ran on");
     c->eager_k1 = false;
     c->gc_valid = false;
     c->table_complete = false;
@@ -1022,6 +1035,7 @@ int32_t reo_compute_thresholds(reo_ctx *c, double pval_reo)
     c->thr_set = true;
     c->built_k = -1;
     c->eager_k1 = false;
+    drop_ref_mask(c, "the thresholds changed after the last reo_identify_degs (reo_compute_thresholds, reo_set_thresholds): the class table it ran on is gone");
     for (reo_ctx *p : c->peers) { p->thr = c->thr; p->thr_set = true; p->built_k = -1; }
     return REO_OK;
 }
@@ -1033,6 +1047,7 @@ int32_t reo_set_thresholds(reo_ctx *c, const int32_t *m)
     c->thr_set = true;
     c->built_k = -1;
     c->eager_k1 = false;
+    drop_ref_mask(c, "the thresholds changed after the last reo_identify_degs (reo_compute_thresholds, reo_set_thresholds): the class table it ran on is gone");
     for (reo_ctx *p : c->peers) { p->thr = c->thr; p->thr_set = true; p->built_k = -1; }
     return REO_OK;
 }
@@ -1069,6 +1084,7 @@ static int32_t build_local(reo_ctx *c, int32_t k)
 int32_t reo_build_pairs(reo_ctx *c, int32_t k)
 {
     int32_t rc;
+    if (c) drop_ref_mask(c, "reo_build_pairs has replaced the class table that the last reo_identify_degs ran on: no reo_identify_degs has run on the current one");
     if (c && !c->peers.empty()) {
         if ((rc = multi_build_pairs(c, k, build_local))) return rc;
     } else {
@@ -1167,6 +1183,7 @@ int32_t reo_tally(reo_ctx *c, const uint8_t *ref_mask, int32_t *cont)
     if ((rc = need_complete_table(c))) return rc;
     if (!ref_mask || !cont) { set_error("null argument"); return REO_EINVAL; }
     if ((rc = ensure_iter_buffers(c))) return rc;
+    drop_ref_mask(c, "reo_tally has run since the last reo_identify_degs: it uploads its own mask into the iteration's buffers");
     DrainOnExit drain(c);   // ref_mask in, cont out
     int32_t nref = 0;
     if ((rc = upload_ref(c, ref_mask, 0, &nref))) return rc;
@@ -1184,6 +1201,8 @@ int32_t reo_identify_degs(reo_ctx *c, const uint8_t *ref0, double pval_deg, doub
 {
     int32_t rc = use(c);
     if (rc) return rc;
+    // reo_get_ref_mask: only a call that ends well leaves a mask to hand out (set at the end; no stream operation, no wait for it)
+    drop_ref_mask(c, "the last reo_identify_degs on this context failed");
     if ((rc = need_complete_table(c))) return rc;
     if (!ref0 || !result) { set_error("null argument"); return REO_EINVAL; }
     if ((rc = ensure_iter_buffers(c))) return rc;
@@ -1369,7 +1388,101 @@ int32_t reo_identify_degs(reo_ctx *c, const uint8_t *ref0, double pval_deg, doub
     drain.dismiss();
     if (c->debug_passes) fprintf(stderr, "  result copy: enqueued in %.0f us, waited %.0f us\n", w_copied - w_copy, wall_us() - w_copied);
     collect_timings(c);
-    return pass_fault(c);  // (the replay, too, derives every gene's tallies)
+    if ((rc = pass_fault(c))) return rc;  // (the replay, too, derives every gene's tallies)
+    // The returned n11 .. n33 were counted over ref_gene_vec of the last executed pass (:399-424), pass t = passes - 1.  The mask of pass t
+    // lives in slot t & 1 from the moment pass t - 1 (or, for t = 0, k_iter_init) wrote it: pass t itself writes the NEXT set into the other
+    // slot, the replay of a light pass reads slot t & 1 and writes none, a converged call enqueues nothing that runs after it, and the
+    // cycle watch skips an even number of passes, which keeps the parity of every pass that is still executed.
+    if (passes > 0) c->ref_slot = (passes - 1) & 1;
+    else drop_ref_mask(c, "the last reo_identify_degs was called with n_iter <= 0: no pass ran, no tallies were counted");
+    return REO_OK;
+}
+
+// The reference set of the tallies that the last reo_identify_degs returned: a copy out of the slot recorded above.
+int32_t reo_get_ref_mask(reo_ctx *c, uint8_t *ref_mask, int32_t *nref)
+{
+    int32_t rc = use(c);
+    if (rc) return rc;
+    if (!ref_mask) { set_error("reo_get_ref_mask: ref_mask must not be null"); return REO_EINVAL; }
+    if (c->ref_slot < 0 || c->built_k < 0) {
+        set_error("reo_get_ref_mask: no reference set to deliver: %s", c->ref_slot < 0 ? c->ref_gone : "the class table was dropped");
+        return REO_EINVAL;
+    }
+    DrainOnExit drain(c);
+    REO_HIP_CHECK(hipMemcpyAsync(ref_mask, c->refbytes[c->ref_slot].p, static_cast<size_t>(c->G), hipMemcpyDeviceToHost, c->stream));
+    REO_HIP_CHECK(hipStreamSynchronize(c->stream));
+    drain.dismiss();
+    int32_t n = 0;
+    for (int64_t i = 0; i < c->G; ++i) { ref_mask[i] = ref_mask[i] != 0; n += ref_mask[i]; }
+    if (nref) *nref = n;
+    return REO_OK;
+}
+
+// The partners behind the tallies (include/reo_hip.h): count on the device, prefix sums on the host (the caller wants rowptr anyway), fill on
+// the device into buffers sized from the counted total.
+int32_t reo_pair_list(reo_ctx *c, const int32_t *genes, int64_t n_genes, const uint8_t *partner_mask, uint32_t class_mask, int64_t *rowptr,
+                      int32_t *partner, uint8_t *code, int64_t capacity)
+{
+    int32_t rc = no_multi(c, "reo_pair_list");
+    if (rc || (rc = use(c))) return rc;
+    if ((rc = need_complete_table(c))) return rc;
+    char msg[320];
+    if (pair_list_check_args(c->G, genes, n_genes, class_mask, rowptr, partner, code, capacity, msg, sizeof msg)) { set_error("%s", msg); return REO_EINVAL; }
+    if (!partner_mask && c->ref_slot < 0) {
+        set_error("reo_pair_list: partner_mask is null and there is no reference set to take its place: %s", c->ref_gone);
+        return REO_EINVAL;
+    }
+    const size_t n = static_cast<size_t>(n_genes);
+    DevBuf<int32_t> d_genes, d_count, d_partner, d_flag;
+    DevBuf<int64_t> d_rowptr;
+    DevBuf<uint8_t> d_code, d_maskbytes;
+    DevBuf<uint32_t> d_maskbits;
+    if ((rc = d_genes.ensure(n)) || (rc = d_count.ensure(n))) return rc;
+    const uint32_t *maskbits = nullptr;
+    if (partner_mask) {
+        if ((rc = d_maskbytes.ensure(c->Gp)) || (rc = d_maskbits.ensure(c->Wp))) return rc;
+        maskbits = d_maskbits.p;
+    } else {
+        maskbits = c->refbits[c->ref_slot].p;
+    }
+    std::vector<int32_t> count(n);
+    int32_t flag = 0;
+    DrainOnExit drain(c);   // genes and partner_mask in, partner and code out (declared after the buffers: the wait comes before their release)
+    REO_HIP_CHECK(hipMemcpyAsync(d_genes.p, genes, n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    if (partner_mask) {
+        REO_HIP_CHECK(hipMemsetAsync(d_maskbytes.p, 0, c->Gp, c->stream));
+        REO_HIP_CHECK(hipMemcpyAsync(d_maskbytes.p, partner_mask, static_cast<size_t>(c->G), hipMemcpyHostToDevice, c->stream));
+        if ((rc = launch_pack_ref(c, d_maskbytes.p, d_maskbits.p))) return rc;
+    }
+    if ((rc = launch_pair_count(c, d_genes.p, n_genes, maskbits, class_mask, d_count.p))) return rc;
+    REO_HIP_CHECK(hipMemcpyAsync(count.data(), d_count.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = wait_or_drop_table(c))) return rc;
+    for (size_t q = 0; q < n; ++q)
+        if (count[q] < 0 || count[q] >= c->G) { set_error("reo_pair_list: the count of query %zu reads %d with %lld genes", q, count[q], (long long)c->G); return REO_EHIP; }
+    const int64_t total = pair_list_rowptr(count.data(), n_genes, rowptr);
+    if (!partner || total == 0) { drain.dismiss(); return REO_OK; }
+    if (total > capacity) {
+        set_error("reo_pair_list: the lists hold %lld entries, capacity is %lld (rowptr has been filled: allocate rowptr[n_genes] entries)",
+                  (long long)total, (long long)capacity);
+        return REO_EINVAL;
+    }
+    if ((rc = d_rowptr.ensure(n + 1)) || (rc = d_partner.ensure(static_cast<size_t>(total))) || (rc = d_code.ensure(static_cast<size_t>(total))) ||
+        (rc = d_flag.ensure(1)))
+        return rc;
+    REO_HIP_CHECK(hipMemcpyAsync(d_rowptr.p, rowptr, (n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    REO_HIP_CHECK(hipMemsetAsync(d_flag.p, 0, sizeof(int32_t), c->stream));
+    if ((rc = launch_pair_fill(c, d_genes.p, n_genes, maskbits, class_mask, d_rowptr.p, d_partner.p, d_code.p, total, d_flag.p))) return rc;
+    REO_HIP_CHECK(hipMemcpyAsync(partner, d_partner.p, static_cast<size_t>(total) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    REO_HIP_CHECK(hipMemcpyAsync(code, d_code.p, static_cast<size_t>(total), hipMemcpyDeviceToHost, c->stream));
+    REO_HIP_CHECK(hipMemcpyAsync(&flag, d_flag.p, sizeof flag, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = wait_or_drop_table(c))) return rc;
+    drain.dismiss();
+    if (flag) {
+        set_error("reo_pair_list: the fill pass found another number of pairs in a row than the count pass (the class table changed between them?); "
+                  "the lists are not valid");
+        return REO_EHIP;
+    }
+    return REO_OK;
 }
 
 int32_t reo_mccullagh(reo_ctx *c, const int32_t *cont, int64_t n, double *out)

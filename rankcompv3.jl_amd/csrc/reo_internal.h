@@ -299,6 +299,10 @@ struct reo_ctx {
     // iteration state
     reo::DevBuf<uint32_t> refbits[2];   // [Wp]
     reo::DevBuf<uint8_t> refbytes[2];   // [Gp]
+    // reo_get_ref_mask / reo_pair_list: which of the two slots holds the reference set that the last reo_identify_degs counted its returned
+    // tallies over -- the mask of its last executed pass t, slot t & 1 (pass t writes the NEXT set into the other slot) -- or -1 and why not
+    int ref_slot = -1;
+    const char *ref_gone = "reo_identify_degs has not run on this context";
     reo::DevBuf<int32_t> raw;           // [G][8]
     reo::DevBuf<uint32_t> delta_list;   // [2][Gp] changed genes (gene << 1 | added) per pass parity
     reo::DevBuf<int32_t> cont;          // [G][9]
@@ -395,6 +399,12 @@ int32_t xcc_selftest(reo_ctx *c, int *ok);
 int32_t light_min_genes();
 int32_t light_window();
 int32_t launch_mccullagh(reo_ctx *c, const int32_t *d_cont, int64_t n, double *d_out);
+
+// pairlist.hip: the kernels of reo_pair_list (shared arithmetic and host checks: pair_list.h).  d_maskbits: [Wp] the partner mask as bits
+// (k_pack_ref's layout, a refbits slot); d_genes: [n_genes] query rows, checked by the caller to lie in [0, G)
+int32_t launch_pair_count(reo_ctx *c, const int32_t *d_genes, int64_t n_genes, const uint32_t *d_maskbits, uint32_t class_mask, int32_t *d_count);
+int32_t launch_pair_fill(reo_ctx *c, const int32_t *d_genes, int64_t n_genes, const uint32_t *d_maskbits, uint32_t class_mask, const int64_t *d_rowptr,
+                         int32_t *d_partner, uint8_t *d_code, int64_t capacity, int32_t *d_flag);
 
 // pseudobulk.hip: the checks, upload and kernels of reo_pseudobulk_*, the G x n_out sums left in c->dX_owned (ld = G) instead of a host array
 int32_t pseudobulk_resident_dense(reo_ctx *c, const void *X, bool is_int, int64_t G, int64_t C, int64_t ld, const int32_t *order,

@@ -15,6 +15,7 @@ from typing import NamedTuple
 import numpy as np
 
 from . import _ffi, synth
+from ._ffi import PairList, class_mask  # noqa: F401
 
 HEADER = ["pval", "padj", "n11", "n12", "n13", "n21", "n22", "n23", "n31", "n32", "n33",
           "Δ1", "Δ2", "se", "z1", "up_down"]  # src/RankCompV3.jl:665
@@ -73,8 +74,35 @@ class DegRun:
         return self._res
 
 
+def deg_pairs(ctx, labels, pairs) -> dict:
+    """{"ref_mask", "pairs"} of the comparison whose identify_degs has just returned on `ctx`: the reference set of its tallies and the
+    pair list (class selection `pairs`) of its DEGs against that set.  No DEGs: an empty PairList, no library call for it."""
+    mask = class_mask(pairs)
+    ref = ctx.ref_mask()
+    degs = np.flatnonzero(np.asarray(labels) != "no change").astype(np.int32)
+    if degs.size == 0:
+        pl = PairList(degs, np.zeros(1, dtype=np.int64), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.uint8))
+    else:
+        pl = ctx.pair_list(degs, mask)
+    return {"ref_mask": ref, "pairs": pl}
+
+
+def write_pairs_tsv(path, gene_names, pair_list) -> None:
+    """gene<TAB>partner<TAB>class, one line per listed pair in the list's own order, names from gene_names and the class as its tally's
+    header name (n13, ...); a header line, "\n" line ends, like the result writers of reoa."""
+    names = _ffi.CLASS_NAMES
+    with open(path, "w") as f:
+        f.write("gene\tpartner\tclass\n")
+        for q, g in enumerate(pair_list.genes):
+            partner, code = pair_list.row(q)
+            gname = gene_names[int(g)]
+            for j, c in zip(partner, code):
+                f.write(f"{gname}\t{gene_names[int(j)]}\t{names[int(c)]}\n")
+
+
 def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref_gene, n_iter, n_conv, *,
-                      seed: int = 0, device: int = -1, shard=(0, 1), allreduce=None, allgather=None, profile: bool = False) -> DegRun:
+                      seed: int = 0, device: int = -1, shard=(0, 1), allreduce=None, allgather=None, profile: bool = False,
+                      pairs=None) -> DegRun:
     """identify_degs with the extras (trace, timings) kept.  `data` is a host matrix (numpy, anything np.asarray takes) or a torch
     tensor on a ROCm device, which is used in place (_ffi.device_matrix).  A column-major host matrix is read in place; a row-major one
     (numpy's default C order, column slices of a wider C-ordered array) is copied column-major on the host first, or, with REO_ROWMAJOR=1
@@ -87,7 +115,11 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
     reo_set_matrix_csc_dev_*).  The mirror does not canonicalise: unsorted or repeated row indices inside a column are refused.
     Two groups: one comparison, group 1 vs
     group 2 (the reference's `gnum == 2` path, :387-389,431-434).  More groups: one comparison per
-    group, that group vs every other sample (:375-390,396-436), 16 more columns each."""
+    group, that group vs every other sample (:375-390,396-436), 16 more columns each.
+    `pairs` (not in the reference): a class selection (_ffi.class_mask: "reversed", names "n11" .. "n33", codes, a mask).  Every comparison
+    dict then gains "ref_mask", the reference set its returned tallies were counted over (Context.ref_mask), and "pairs", the PairList of its
+    DEGs (label != "no change", ascending gene index) against that set -- taken right after its identify_degs, while its class table is
+    still the current one.  None (the default): no further call is made and the dicts have the keys they always had."""
     # a torch tensor on a ROCm device: a strided one is used where it is, a sparse one is made dense there (its device is the context's)
     on_device = _ffi.is_device_sparse(data) or _ffi.is_device_tensor(data)
     if on_device:
@@ -127,6 +159,8 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
             result, iters, trace = ctx.identify_degs(np.asarray(ref_gene, dtype=bool), pval_deg, padj_deg, n_iter, n_conv)
             comps.append({"k": k, "result": result, "labels": label_genes(result, pval_deg, padj_deg),
                           "iters_run": iters, "trace": trace})
+            if pairs is not None:
+                comps[-1].update(deg_pairs(ctx, comps[-1]["labels"], pairs))
         timings = ctx.timings() if profile else {}
         info = ctx.info()
     first = comps[0]
@@ -165,14 +199,15 @@ class CellsDegRun(NamedTuple):
 
 def identify_degs_cells(cells, cell_group, gene_names, n_pseudo, pval_reo, pval_deg, padj_deg, ref_gene, n_iter, n_conv, *,
                         min_profiles: int = 0, min_features: int = 0, ref_gene_max: int = 3000, seed: int = 0, device: int = 0,
-                        profile: bool = False) -> CellsDegRun:
+                        profile: bool = False, pairs=None) -> CellsDegRun:
     """Cells to DEGs without a host trip for the profiles: `cells` is a genes x cells matrix (scipy.sparse, anything np.asarray takes, or
     a torch tensor on a ROCm device -- sparse or strided -- which is read where it is: reo_set_matrix_pseudobulk_*_dev_*),
     cell_group one label per cell.  cells_partition -> the pseudo-bulk sums written into the context's matrix (set_matrix_pseudobulk) ->
     the reference's two low-expression filters on the device (filter_matrix, :618 / :626) -> groups of the kept profiles, thresholds,
     pair table and iteration as in run_identify_degs.  ref_gene is a bool mask over the INPUT genes (subset by gene_kept here), or None for
     synth.ref_mask(G', min(G', ref_gene_max), seed), the draw reoa makes.  Bit-identical to Context.pseudobulk -> numpy filters ->
-    run_identify_degs on the same seed.  (reoa() keeps its host route: its writers want the profile matrix on the host.)"""
+    run_identify_degs on the same seed.  (reoa() keeps its host route: its writers want the profile matrix on the host.)
+    `pairs`: as in run_identify_degs; gene indices are those of the KEPT genes (run.gene_names)."""
     on_device = _ffi.is_device_sparse(cells) or _ffi.is_device_tensor(cells)
     if on_device:   # a torch tensor on a ROCm device, sparse or strided: summed where it is, on its own device
         device = cells.device.index if cells.device.index is not None else -1
@@ -207,6 +242,8 @@ def identify_degs_cells(cells, cell_group, gene_names, n_pseudo, pval_reo, pval_
             ctx.build_pairs(k)
             result, iters, trace = ctx.identify_degs(ref, pval_deg, padj_deg, n_iter, n_conv)
             comps.append({"k": k, "result": result, "labels": label_genes(result, pval_deg, padj_deg), "iters_run": iters, "trace": trace})
+            if pairs is not None:
+                comps[-1].update(deg_pairs(ctx, comps[-1]["labels"], pairs))
         timings = ctx.timings() if profile else {}
         info = ctx.info()
     first = comps[0]
