@@ -305,6 +305,35 @@ int32_t reo_pair_list(reo_ctx *ctx, const int32_t *genes, int64_t n_genes,
                       uint32_t class_mask /* bit c selects class code c = 3*(ic-1)+(it-1), c in 0..8; 1..0x1FF */,
                       int64_t *rowptr /* n_genes + 1 */, int32_t *partner, uint8_t *code, int64_t capacity);
 
+/* Sample counts: IN WHICH SAMPLES a gene's selected pairs put it above its partner.  The tallies say that gene i's order against the
+ * reference genes reversed between the groups, the pair lists say against which genes; this call says in which samples.  The reference has
+ * no such output (its R BitArray dies inside identify_degs, src/RankCompV3.jl:363-392).
+ * For query q, gene i = genes[q] (any order, repeats allowed, each entry is its own row), J is exactly the partner set that reo_pair_list
+ * lists for the same partner_mask / class_mask: j != i, partner_mask[j] != 0 (NULL = the mask of reo_get_ref_mask, read where it lies), the
+ * class of the ordered pair (i, j) selected.  n_sel[q] = |J|, and for every sample s in the CALLER's column order -- both groups, every
+ * group of a multi-group problem --
+ *     n_gt[q * S + s] = #{j in J : x_i > x_j and not tied in sample s}        n_eq[q * S + s] = #{j in J : tied in sample s}
+ * by the comparator of the resident matrix's element type as the rank/band transform encodes it: Float64 the 0.1 band, Float32 the Float32
+ * rule above, Int64 and Int32 equality; of two equal infinities the gene with the larger index is the greater one and nothing is tied.
+ * n_lt = n_sel - n_gt - n_eq is not delivered.  No tie coin is drawn: like reo_pair_counts, the call reports ties as ties.
+ * n_eq == NULL: the tied counts are not computed (half of the compare work).
+ * Needs the class table (reo_build_pairs) and the transform; reads the reference mask and changes nothing: reo_get_ref_mask and a following
+ * reo_identify_degs behave as if the call had not happened.  Both plane layouts (up to and above 65 535 genes), every S.
+ * One kernel (csrc/samplecounts.hip): a workgroup per (query, 8 blocks of 32 sample slots) compacts the selected columns of the query's
+ * table row tile by tile, runs the borrow chain of the pair kernel against every listed partner and adds the 32-sample result words into
+ * bit-sliced counters.  Device temporaries are bounded: the queries go in batches whose two count buffers, each batch x padded sample slots
+ * x 4 bytes, stay under 32 MiB each (at least one query per batch); REO_SAMPLE_COUNTS_BATCH in the environment, read per call, lowers the
+ * batch to that many queries (tests of the batch seam).
+ * Host arrays only; no stage timer of its own.
+ * REO_EINVAL, each with its own message: no class table; a NULL genes or n_gt; n_genes < 1 or above 2^30; a gene outside [0, G); a
+ * class_mask of 0 or with bits above 8; a NULL partner_mask while reo_get_ref_mask would refuse (its reason is passed on); a
+ * reo_create_multi context.  An incomplete sharded table: REO_ECOMM, as reo_tally. */
+int32_t reo_sample_counts(reo_ctx *ctx, const int32_t *genes, int64_t n_genes,
+                          const uint8_t *partner_mask /* G bytes; NULL = the mask of reo_get_ref_mask */,
+                          uint32_t class_mask /* as reo_pair_list: 1 .. 0x1FF */,
+                          int32_t *n_sel /* n_genes; may be NULL */,
+                          int32_t *n_gt, int32_t *n_eq /* n_genes x S row-major, ld = S; n_eq may be NULL */);
+
 /* McCullagh test on 3x3 tables given as 9 tallies each (n x 9 row-major),
  * evaluated by the device routine the iteration uses; out is n x 5 row-major
  * (pval, delta1, delta2, se, z1) -- src/RankCompV3.jl:225-259. */

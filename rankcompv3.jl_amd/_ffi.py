@@ -32,7 +32,7 @@ SYMBOLS = [
     "reo_set_profiling", "reo_reset_timings", "reo_get_timings", "reo_get_info",
     "reo_pseudobulk_dense_f64", "reo_pseudobulk_dense_i64", "reo_pseudobulk_csc_f64", "reo_pseudobulk_csc_i64",
     "reo_set_matrix_pseudobulk_dense_f64", "reo_set_matrix_pseudobulk_dense_i64", "reo_set_matrix_pseudobulk_csc_f64", "reo_set_matrix_pseudobulk_csc_i64",
-    "reo_filter_matrix", "reo_get_matrix", "reo_get_ref_mask", "reo_pair_list",
+    "reo_filter_matrix", "reo_get_matrix", "reo_get_ref_mask", "reo_pair_list", "reo_sample_counts",
 ] + [f"reo_set_matrix_{form}_{t}" for form in ("csc_dev", "pseudobulk_csc_dev", "pseudobulk_dense_dev") for t in ("f64", "i64", "f32", "i32")]
 
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p)
@@ -137,6 +137,7 @@ def lib() -> ctypes.CDLL:
         "reo_get_matrix": (i32, [vp, vp, i64]),
         "reo_get_ref_mask": (i32, [vp, vp, vp]),
         "reo_pair_list": (i32, [vp, vp, i64, vp, ctypes.c_uint32, vp, vp, vp, i64]),
+        "reo_sample_counts": (i32, [vp, vp, i64, vp, ctypes.c_uint32, vp, vp, vp]),
     }
     for t in ("f64", "i64", "f32", "i32"):   # SPARSE ON THE DEVICE
         sig["reo_set_matrix_csc_dev_" + t] = (i32, [vp, i64, i64, i64, vp, vp, i32, vp])
@@ -312,6 +313,43 @@ class PairList(NamedTuple):
     def row(self, q: int):
         a, b = int(self.rowptr[q]), int(self.rowptr[q + 1])
         return self.partner[a:b], self.code[a:b]
+
+
+class SampleCounts(NamedTuple):
+    """reo_sample_counts: per query gene (row) and sample (column, the caller's order), among the n_sel selected partners, in how many pairs
+    the gene lies above its partner (n_gt), level with it (n_eq; None when the call was made with ties=False) or below it (n_lt)."""
+    genes: np.ndarray      # int32, the queries as given
+    n_sel: np.ndarray      # int32, len(genes): selected partners per query
+    n_gt: np.ndarray       # int32, len(genes) x S
+    n_eq: np.ndarray | None
+
+    @property
+    def n_lt(self) -> np.ndarray:
+        """n_sel - n_gt - n_eq; needs the tied counts (ties=True)."""
+        if self.n_eq is None:
+            raise DimensionMismatch(REO_EINVAL, "n_lt needs the tied counts: call sample_counts with ties=True")
+        return (self.n_sel[:, None] - self.n_gt - self.n_eq).astype(np.int32)
+
+
+class SampleScores(NamedTuple):
+    """Per DEG (row) and sample (column): of the gene's n_pairs reversed pairs (n13 and n31 against the partner set), how many show the
+    order of the non-control side in that sample (treat_like), how many the control's (ctrl_like), how many are tied."""
+    genes: np.ndarray      # int32
+    n_pairs: np.ndarray    # int32, len(genes): n13 + n31 partners
+    treat_like: np.ndarray  # int32, len(genes) x S: gt(n13) + lt(n31)
+    ctrl_like: np.ndarray   # int32: lt(n13) + gt(n31)
+    tied: np.ndarray        # int32
+
+    @property
+    def net(self) -> np.ndarray:
+        return (self.treat_like - self.ctrl_like).astype(np.int32)
+
+
+def sample_scores_from(c13: SampleCounts, c31: SampleCounts) -> SampleScores:
+    """The scores from the counts of the two reversed classes.  Pure: no library, no GPU.  n13 is "control i < j, the rest i > j"
+    (src/RankCompV3.jl:369-384), so `gt` is the treatment-like outcome there and `lt` for n31."""
+    return SampleScores(c13.genes, (c13.n_sel + c31.n_sel).astype(np.int32), (c13.n_gt + c31.n_lt).astype(np.int32),
+                        (c13.n_lt + c31.n_gt).astype(np.int32), (c13.n_eq + c31.n_eq).astype(np.int32))
 
 
 UNIQUE_ID_BYTES = 128
@@ -601,6 +639,34 @@ class Context:
         if total:
             self.pair_list_raw(g, mask, pm, rowptr, partner, code, total)
         return PairList(g, rowptr, partner, code)
+
+    def sample_counts_raw(self, genes, mask: int, partner_mask, n_sel, n_gt, n_eq) -> None:
+        """reo_sample_counts on caller-made arrays (n_sel and n_eq may be None); sample_counts is the convenient form."""
+        check(self._L.reo_sample_counts(self._h, _ptr(genes) if genes is not None and genes.size else None, 0 if genes is None else genes.size,
+                                        None if partner_mask is None else _ptr(partner_mask), ctypes.c_uint32(mask & 0xFFFFFFFF),
+                                        None if n_sel is None else _ptr(n_sel), None if n_gt is None else _ptr(n_gt),
+                                        None if n_eq is None else _ptr(n_eq)))
+
+    def sample_counts(self, genes, classes, partner_mask=None, ties=True) -> SampleCounts:
+        """In which samples (reo_sample_counts): for every query gene and every sample, in how many of its selected pairs -- partners j with
+        partner_mask[j] set (None: the reference set of the last identify_degs, ref_mask()) whose pair with it has one of `classes`
+        (class_mask) -- the gene lies above its partner, and in how many the two are tied.  ties=False: no tied counts (n_eq None)."""
+        mask = class_mask(classes)
+        g = np.ascontiguousarray(genes, dtype=np.int32).reshape(-1)
+        pm = None
+        if partner_mask is not None:
+            pm = np.ascontiguousarray(np.asarray(partner_mask) != 0, dtype=np.uint8)
+            if pm.size != self.G:
+                raise DimensionMismatch(REO_EINVAL, "partner mask length != number of genes")
+        n_sel = np.zeros(g.size, dtype=np.int32)
+        n_gt = np.zeros((g.size, max(self.S, 1)), dtype=np.int32)
+        n_eq = np.zeros_like(n_gt) if ties else None
+        self.sample_counts_raw(g, mask, pm, n_sel, n_gt, n_eq)
+        return SampleCounts(g, n_sel, n_gt[:, : self.S], None if n_eq is None else n_eq[:, : self.S])
+
+    def sample_scores(self, genes, partner_mask=None) -> SampleScores:
+        """Per sample, how far every query gene's reversed pairs (n13, n31) show the non-control order: two sample_counts calls."""
+        return sample_scores_from(self.sample_counts(genes, "n13", partner_mask), self.sample_counts(genes, "n31", partner_mask))
 
     def mccullagh(self, cont) -> np.ndarray:
         cont = np.ascontiguousarray(cont, dtype=np.int32).reshape(-1, 9)

@@ -15,6 +15,7 @@
 
 #include "pair_list.h"
 #include "reo_internal.h"
+#include "sample_counts.h"
 #include "upload_csc.h"
 
 #include <mutex>
@@ -593,7 +594,7 @@ using namespace reo;
 
 extern "C" {
 
-int32_t reo_version(void) { return 600; }
+int32_t reo_version(void) { return 700; }
 
 int32_t reo_trim_memory(void)
 {
@@ -1482,6 +1483,70 @@ int32_t reo_pair_list(reo_ctx *c, const int32_t *genes, int64_t n_genes, const u
                   "the lists are not valid");
         return REO_EHIP;
     }
+    return REO_OK;
+}
+
+// In which samples (include/reo_hip.h): the queries in batches whose two count buffers stay under the budget of sample_counts.h; per batch one
+// launch and the copies of its rows into the caller's arrays.  Reads the class table, the bit planes and a reference mask slot; writes none of them.
+int32_t reo_sample_counts(reo_ctx *c, const int32_t *genes, int64_t n_genes, const uint8_t *partner_mask, uint32_t class_mask, int32_t *n_sel,
+                          int32_t *n_gt, int32_t *n_eq)
+{
+    int32_t rc = no_multi(c, "reo_sample_counts");
+    if (rc || (rc = use(c))) return rc;
+    if ((rc = need_complete_table(c))) return rc;
+    char msg[320];
+    if (sample_counts_check_args(c->G, genes, n_genes, class_mask, n_gt, msg, sizeof msg)) { set_error("%s", msg); return REO_EINVAL; }
+    if (!partner_mask && c->ref_slot < 0) {
+        set_error("reo_sample_counts: partner_mask is null and there is no reference set to take its place: %s", c->ref_gone);
+        return REO_EINVAL;
+    }
+    if ((rc = ensure_transform(c))) return rc;   // (in place whenever there is a class table: nothing runs)
+    // the caller's column of every sample slot, from the group labels the transform laid the slots out by
+    std::vector<int32_t> map;
+    if (!sc_slot_map(c->group_id.data(), c->S, c->ngroups, map) || c->goff32.empty() || static_cast<int64_t>(map.size()) != c->goff32.back()) {
+        set_error("reo_sample_counts: the sample slots of the bit planes do not match the group labels");
+        return REO_EHIP;
+    }
+    const int64_t S = c->S, slots = static_cast<int64_t>(map.size());
+    const char *env = getenv("REO_SAMPLE_COUNTS_BATCH");
+    const int64_t batch = sc_batch_rows(n_genes, slots, env ? atoll(env) : 0);
+    const size_t nb = static_cast<size_t>(batch);
+    DevBuf<int32_t> d_genes, d_sel, d_gt, d_eq;
+    DevBuf<uint8_t> d_maskbytes;
+    DevBuf<uint32_t> d_maskbits;
+    if ((rc = d_genes.ensure(nb)) || (rc = d_sel.ensure(nb)) || (rc = d_gt.ensure(nb * slots)) || (n_eq && (rc = d_eq.ensure(nb * slots))) ||
+        (rc = c->sc_slot2col.ensure(map.size())))
+        return rc;
+    const uint32_t *maskbits = nullptr;
+    if (partner_mask) {
+        if ((rc = d_maskbytes.ensure(c->Gp)) || (rc = d_maskbits.ensure(c->Wp))) return rc;
+        maskbits = d_maskbits.p;
+    } else {
+        maskbits = c->refbits[c->ref_slot].p;
+    }
+    DrainOnExit drain(c);   // genes and partner_mask in, the counts out (declared after the buffers: the wait comes before their release)
+    if (map != c->sc_slot2col_host || c->sc_slot2col.p != c->sc_slot2col_uploaded) {   // once per change of the groups
+        c->sc_slot2col_host = map;
+        c->sc_slot2col_uploaded = nullptr;
+        REO_HIP_CHECK(hipMemcpyAsync(c->sc_slot2col.p, c->sc_slot2col_host.data(), map.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        c->sc_slot2col_uploaded = c->sc_slot2col.p;
+    }
+    if (partner_mask) {
+        REO_HIP_CHECK(hipMemsetAsync(d_maskbytes.p, 0, c->Gp, c->stream));
+        REO_HIP_CHECK(hipMemcpyAsync(d_maskbytes.p, partner_mask, static_cast<size_t>(c->G), hipMemcpyHostToDevice, c->stream));
+        if ((rc = launch_pack_ref(c, d_maskbytes.p, d_maskbits.p))) return rc;
+    }
+    for (int64_t q0 = 0; q0 < n_genes; q0 += batch) {
+        const int64_t nq = std::min(batch, n_genes - q0);
+        const size_t rows = static_cast<size_t>(nq) * static_cast<size_t>(S);
+        REO_HIP_CHECK(hipMemcpyAsync(d_genes.p, genes + q0, static_cast<size_t>(nq) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        if ((rc = launch_sample_counts(c, d_genes.p, nq, maskbits, class_mask, c->sc_slot2col.p, d_sel.p, d_gt.p, n_eq ? d_eq.p : nullptr))) return rc;
+        REO_HIP_CHECK(hipMemcpyAsync(n_gt + static_cast<size_t>(q0) * S, d_gt.p, rows * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        if (n_eq) REO_HIP_CHECK(hipMemcpyAsync(n_eq + static_cast<size_t>(q0) * S, d_eq.p, rows * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        if (n_sel) REO_HIP_CHECK(hipMemcpyAsync(n_sel + q0, d_sel.p, static_cast<size_t>(nq) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        if ((rc = wait_or_drop_table(c))) return rc;   // the next batch reuses the buffers
+    }
+    drain.dismiss();
     return REO_OK;
 }
 

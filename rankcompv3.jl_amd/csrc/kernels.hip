@@ -3899,7 +3899,7 @@ __global__ __launch_bounds__(256) void x_expand_mirror(XArgs a, const uint32_t *
 static_assert(kItemTileI == kTileI && kItemUnitH == kUnitH, "k1_items.h carries its own copy of the tile geometry");
 
 // bits needed for every number the pair kernel compares: positions 0..G-1 and band ends up to G
-static int plane_bits(int64_t G) { return G <= 4095 ? 12 : (G <= 32767 ? 15 : (G <= 65535 ? 16 : (G <= 131071 ? 17 : 18))); }
+int plane_bits(int64_t G) { return G <= 4095 ? 12 : (G <= 32767 ? 15 : (G <= 65535 ? 16 : (G <= 131071 ? 17 : 18))); }
 
 // What launch_k1 decides before it launches anything: which form of the pair kernel runs, the geometry of its work units
 // and which units this shard owns.

@@ -303,6 +303,10 @@ struct reo_ctx {
     // tallies over -- the mask of its last executed pass t, slot t & 1 (pass t writes the NEXT set into the other slot) -- or -1 and why not
     int ref_slot = -1;
     const char *ref_gone = "reo_identify_degs has not run on this context";
+    // reo_sample_counts: the caller's column of every sample slot (-1: padding), uploaded when the groups have changed
+    reo::DevBuf<int32_t> sc_slot2col;   // [32 * sample blocks]
+    std::vector<int32_t> sc_slot2col_host;      // what it holds ...
+    const int32_t *sc_slot2col_uploaded = nullptr;   // ... and in which allocation
     reo::DevBuf<int32_t> raw;           // [G][8]
     reo::DevBuf<uint32_t> delta_list;   // [2][Gp] changed genes (gene << 1 | added) per pass parity
     reo::DevBuf<int32_t> cont;          // [G][9]
@@ -405,6 +409,13 @@ int32_t launch_mccullagh(reo_ctx *c, const int32_t *d_cont, int64_t n, double *d
 int32_t launch_pair_count(reo_ctx *c, const int32_t *d_genes, int64_t n_genes, const uint32_t *d_maskbits, uint32_t class_mask, int32_t *d_count);
 int32_t launch_pair_fill(reo_ctx *c, const int32_t *d_genes, int64_t n_genes, const uint32_t *d_maskbits, uint32_t class_mask, const int64_t *d_rowptr,
                          int32_t *d_partner, uint8_t *d_code, int64_t capacity, int32_t *d_flag);
+
+// samplecounts.hip: the kernel of reo_sample_counts (shared arithmetic and host checks: sample_counts.h).  d_genes: [n_queries] query rows,
+// checked by the caller to lie in [0, G); d_maskbits as above; d_slot2col: [32 * sample blocks] the caller's column of every sample slot, -1
+// for padding; d_gt / d_eq: [n_queries][S] (d_eq null: the tied counts are not computed); d_sel: [n_queries]
+int plane_bits(int64_t G);   // kernels.hip: position planes that the count loops read
+int32_t launch_sample_counts(reo_ctx *c, const int32_t *d_genes, int64_t n_queries, const uint32_t *d_maskbits, uint32_t class_mask,
+                             const int32_t *d_slot2col, int32_t *d_sel, int32_t *d_gt, int32_t *d_eq);
 
 // pseudobulk.hip: the checks, upload and kernels of reo_pseudobulk_*, the G x n_out sums left in c->dX_owned (ld = G) instead of a host array
 int32_t pseudobulk_resident_dense(reo_ctx *c, const void *X, bool is_int, int64_t G, int64_t C, int64_t ld, const int32_t *order,

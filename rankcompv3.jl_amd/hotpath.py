@@ -15,7 +15,7 @@ from typing import NamedTuple
 import numpy as np
 
 from . import _ffi, synth
-from ._ffi import PairList, class_mask  # noqa: F401
+from ._ffi import PairList, SampleCounts, SampleScores, class_mask  # noqa: F401
 
 HEADER = ["pval", "padj", "n11", "n12", "n13", "n21", "n22", "n23", "n31", "n32", "n33",
           "Δ1", "Δ2", "se", "z1", "up_down"]  # src/RankCompV3.jl:665
@@ -87,6 +87,25 @@ def deg_pairs(ctx, labels, pairs) -> dict:
     return {"ref_mask": ref, "pairs": pl}
 
 
+def deg_sample_scores(ctx, labels) -> dict:
+    """{"sample_scores"} of the comparison whose identify_degs has just returned on `ctx`: the SampleScores of its DEGs against the reference
+    set of its tallies.  No DEGs: an empty object, no library call for it."""
+    degs = np.flatnonzero(np.asarray(labels) != "no change").astype(np.int32)
+    if degs.size == 0:
+        z = np.zeros((0, ctx.S), dtype=np.int32)
+        return {"sample_scores": SampleScores(degs, np.zeros(0, dtype=np.int32), z, z.copy(), z.copy())}
+    return {"sample_scores": ctx.sample_scores(degs)}
+
+
+def write_sample_scores_tsv(path, gene_names, sample_names, scores) -> None:
+    """gene<TAB>n_pairs<TAB>one column per sample, one row per scored gene, cells = scores.net; "\n" line ends, like the result writers."""
+    net = scores.net
+    with open(path, "w") as f:
+        f.write("\t".join(["gene", "n_pairs"] + [str(n) for n in sample_names]) + "\n")
+        for q, g in enumerate(scores.genes):
+            f.write("\t".join([str(gene_names[int(g)]), str(int(scores.n_pairs[q]))] + [str(int(v)) for v in net[q]]) + "\n")
+
+
 def write_pairs_tsv(path, gene_names, pair_list) -> None:
     """gene<TAB>partner<TAB>class, one line per listed pair in the list's own order, names from gene_names and the class as its tally's
     header name (n13, ...); a header line, "\n" line ends, like the result writers of reoa."""
@@ -102,7 +121,7 @@ def write_pairs_tsv(path, gene_names, pair_list) -> None:
 
 def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref_gene, n_iter, n_conv, *,
                       seed: int = 0, device: int = -1, shard=(0, 1), allreduce=None, allgather=None, profile: bool = False,
-                      pairs=None) -> DegRun:
+                      pairs=None, sample_scores: bool = False) -> DegRun:
     """identify_degs with the extras (trace, timings) kept.  `data` is a host matrix (numpy, anything np.asarray takes) or a torch
     tensor on a ROCm device, which is used in place (_ffi.device_matrix).  A column-major host matrix is read in place; a row-major one
     (numpy's default C order, column slices of a wider C-ordered array) is copied column-major on the host first, or, with REO_ROWMAJOR=1
@@ -119,7 +138,10 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
     `pairs` (not in the reference): a class selection (_ffi.class_mask: "reversed", names "n11" .. "n33", codes, a mask).  Every comparison
     dict then gains "ref_mask", the reference set its returned tallies were counted over (Context.ref_mask), and "pairs", the PairList of its
     DEGs (label != "no change", ascending gene index) against that set -- taken right after its identify_degs, while its class table is
-    still the current one.  None (the default): no further call is made and the dicts have the keys they always had."""
+    still the current one.  None (the default): no further call is made and the dicts have the keys they always had.
+    `sample_scores` (not in the reference): True adds "sample_scores" to every comparison dict, the SampleScores of its DEGs against the
+    reference set of its tallies (Context.sample_scores; rows = DEGs ascending, columns = the samples as given), taken at the same moment.
+    False (the default): no further call, no new key."""
     # a torch tensor on a ROCm device: a strided one is used where it is, a sparse one is made dense there (its device is the context's)
     on_device = _ffi.is_device_sparse(data) or _ffi.is_device_tensor(data)
     if on_device:
@@ -161,6 +183,8 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
                           "iters_run": iters, "trace": trace})
             if pairs is not None:
                 comps[-1].update(deg_pairs(ctx, comps[-1]["labels"], pairs))
+            if sample_scores:
+                comps[-1].update(deg_sample_scores(ctx, comps[-1]["labels"]))
         timings = ctx.timings() if profile else {}
         info = ctx.info()
     first = comps[0]
@@ -199,7 +223,7 @@ class CellsDegRun(NamedTuple):
 
 def identify_degs_cells(cells, cell_group, gene_names, n_pseudo, pval_reo, pval_deg, padj_deg, ref_gene, n_iter, n_conv, *,
                         min_profiles: int = 0, min_features: int = 0, ref_gene_max: int = 3000, seed: int = 0, device: int = 0,
-                        profile: bool = False, pairs=None) -> CellsDegRun:
+                        profile: bool = False, pairs=None, sample_scores: bool = False) -> CellsDegRun:
     """Cells to DEGs without a host trip for the profiles: `cells` is a genes x cells matrix (scipy.sparse, anything np.asarray takes, or
     a torch tensor on a ROCm device -- sparse or strided -- which is read where it is: reo_set_matrix_pseudobulk_*_dev_*),
     cell_group one label per cell.  cells_partition -> the pseudo-bulk sums written into the context's matrix (set_matrix_pseudobulk) ->
@@ -207,7 +231,7 @@ def identify_degs_cells(cells, cell_group, gene_names, n_pseudo, pval_reo, pval_
     pair table and iteration as in run_identify_degs.  ref_gene is a bool mask over the INPUT genes (subset by gene_kept here), or None for
     synth.ref_mask(G', min(G', ref_gene_max), seed), the draw reoa makes.  Bit-identical to Context.pseudobulk -> numpy filters ->
     run_identify_degs on the same seed.  (reoa() keeps its host route: its writers want the profile matrix on the host.)
-    `pairs`: as in run_identify_degs; gene indices are those of the KEPT genes (run.gene_names)."""
+    `pairs`, `sample_scores`: as in run_identify_degs; gene indices are those of the KEPT genes (run.gene_names), columns the kept profiles."""
     on_device = _ffi.is_device_sparse(cells) or _ffi.is_device_tensor(cells)
     if on_device:   # a torch tensor on a ROCm device, sparse or strided: summed where it is, on its own device
         device = cells.device.index if cells.device.index is not None else -1
@@ -244,6 +268,8 @@ def identify_degs_cells(cells, cell_group, gene_names, n_pseudo, pval_reo, pval_
             comps.append({"k": k, "result": result, "labels": label_genes(result, pval_deg, padj_deg), "iters_run": iters, "trace": trace})
             if pairs is not None:
                 comps[-1].update(deg_pairs(ctx, comps[-1]["labels"], pairs))
+            if sample_scores:
+                comps[-1].update(deg_sample_scores(ctx, comps[-1]["labels"]))
         timings = ctx.timings() if profile else {}
         info = ctx.info()
     first = comps[0]
