@@ -6,40 +6,10 @@ info()["k1_half_tiles_separated"] (a full item counts 2, a half-height item 1)."
 import numpy as np
 import pytest
 
+from slot_cases import model as _model, model_count as _model_count   # the rule in numpy: side = group id for comparison 0
 from test_gpu_parity import _eager_ctx, _expected_block_codes, _setup
 
 pytestmark = pytest.mark.gpu
-
-
-def _model(X, gid):
-    """Separated items by the rule: positions (ranks inside a sample; tie-free data) -> per-side extremes over the side's samples ->
-    key = their sum -> slots by (key, gene) -> ranges of the 32-slot tiles and 256-slot chunks -> live (tile, chunk, side) triples
-    with cmax < rmin (every sample counts) or rmax < cmin (none).  Returns (live, {side: [separated with count n_side, with count 0]})."""
-    G = X.shape[0]
-    pos = np.argsort(np.argsort(X, axis=0, kind="stable"), axis=0, kind="stable")
-    ext = []
-    for side in (0, 1):
-        p = pos[:, np.asarray(gid) == side]
-        ext.append((p.min(axis=1), p.max(axis=1)))
-    key = ext[0][0] + ext[0][1] + ext[1][0] + ext[1][1]
-    s2g = np.lexsort((np.arange(G), key))
-    NT, NQ = (G + 31) // 32, (G + 255) // 256
-    t, q = np.meshgrid(np.arange(NT), np.arange(NQ), indexing="ij")
-    is_live = 256 * q + 255 >= (32 * t // 64) * 64
-    out = {}
-    for side in (0, 1):
-        mn, mx = ext[side][0][s2g], ext[side][1][s2g]
-        rmin = np.array([mn[32 * a:32 * a + 32].min() for a in range(NT)]); rmax = np.array([mx[32 * a:32 * a + 32].max() for a in range(NT)])
-        cmin = np.array([mn[256 * a:256 * a + 256].min() for a in range(NQ)]); cmax = np.array([mx[256 * a:256 * a + 256].max() for a in range(NQ)])
-        full = (cmax[None, :] < rmin[:, None]) & is_live
-        none = (rmax[:, None] < cmin[None, :]) & is_live
-        assert not (full & none).any()
-        out[side] = [int(full.sum()), int(none.sum())]
-    return 2 * int(is_live.sum()), out
-
-
-def _model_count(X, gid):
-    return sum(sum(v) for v in _model(X, gid)[1].values())
 
 
 def _identity_codes(pkg, X, group, seed, monkeypatch, blocks=None):

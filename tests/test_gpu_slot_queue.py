@@ -7,35 +7,13 @@ slots, with one worker that steals everything, with a worker count that is no mu
 import numpy as np
 import pytest
 
+from slot_cases import masks as _masks   # the rule in numpy with the places kept: side = group id for comparison 0
 from test_gpu_parity import _expected_block_codes, _setup
 from test_gpu_slot_order import _identity_codes, _model
 
 pytestmark = pytest.mark.gpu
 
 WAVE_SLOTS = 256 * 4 * 3   # MI355X: 256 CUs x 4 SIMDs x 3 waves of the pair kernel
-
-
-def _masks(X, gid):
-    """The rule of test_gpu_slot_order._model once more, but with the places kept: is_live[tile, chunk] and, per side, the separated
-    (tile, chunk) pairs whose count is the side's size (`full`) and 0 (`none`)."""
-    G = X.shape[0]
-    pos = np.argsort(np.argsort(X, axis=0, kind="stable"), axis=0, kind="stable")
-    ext = []
-    for side in (0, 1):
-        p = pos[:, np.asarray(gid) == side]
-        ext.append((p.min(axis=1), p.max(axis=1)))
-    key = ext[0][0] + ext[0][1] + ext[1][0] + ext[1][1]
-    s2g = np.lexsort((np.arange(G), key))
-    NT, NQ = (G + 31) // 32, (G + 255) // 256
-    t, q = np.meshgrid(np.arange(NT), np.arange(NQ), indexing="ij")
-    is_live = 256 * q + 255 >= (32 * t // 64) * 64
-    out = {}
-    for side in (0, 1):
-        mn, mx = ext[side][0][s2g], ext[side][1][s2g]
-        rmin = np.array([mn[32 * a:32 * a + 32].min() for a in range(NT)]); rmax = np.array([mx[32 * a:32 * a + 32].max() for a in range(NT)])
-        cmin = np.array([mn[256 * a:256 * a + 256].min() for a in range(NQ)]); cmax = np.array([mx[256 * a:256 * a + 256].max() for a in range(NQ)])
-        out[side] = ((cmax[None, :] < rmin[:, None]) & is_live, (rmax[:, None] < cmin[None, :]) & is_live)
-    return is_live, out
 
 
 def _queue_env(monkeypatch, workers=None, queue=None):
