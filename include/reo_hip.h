@@ -488,7 +488,10 @@ int32_t reo_get_timings(reo_ctx *ctx, double *ms, int32_t n);
  * resident matrix (0 none, 1 Float64, 2 Int64 -- Int32 input is widened --, 3 Float32), 25 the last class table was built with the genes
  * in slot order (tie-free data of two groups on one shard; REO_K1_SLOTS=0 switches it off; the table is the same bit for bit), 26 the
  * half-height tiles of that build whose count loop was skipped (counted when asked for, n > 26: one small kernel and a wait), 27 the matrix
- * was made dense from CSC arrays on the device (reo_set_matrix_csc_dev_*: 1, and 23 then reports its nnz; every other reo_set_matrix_*: 0). */
+ * was made dense from CSC arrays on the device (reo_set_matrix_csc_dev_*: 1, and 23 then reports its nnz; every other reo_set_matrix_*: 0), 28 how that build put the table's columns back
+ * into gene order (0: no slot build; 8 or 4: a word at a time, 8 or 4 table rows per 32- or 16-bit entry -- the default, by the LDS the
+ * gene count needs; 1: a bit at a time, REO_K1_UNSLOT=0 in the environment; REO_K1_UNSLOT=8 or 4 asks for that word form wherever its
+ * LDS fits; the table is the same bit for bit under all of them). */
 int32_t reo_get_info(reo_ctx *ctx, int64_t *info, int32_t n);
 
 #ifdef __cplusplus

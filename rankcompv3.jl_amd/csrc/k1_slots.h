@@ -73,13 +73,144 @@ inline void slot_invert(const uint32_t *g2s_G, int G, int Gp, uint32_t *g2s, uin
 }
 
 // One bit row of the class table (W words) from slot-order columns into gene-order columns: out bit j = in bit g2s[j] for j < G, columns
-// from G on are zero.  (k1_unslot_columns does this for every row and plane.)
+// from G on are zero.  (k1_unslot_words and k1_unslot_columns do this for every row and plane.)
 inline void slot_unpermute_row(const uint32_t *in, uint32_t *out, int W, const uint32_t *g2s, int G)
 {
     for (int w = 0; w < W; ++w) out[w] = 0;
     for (int j = 0; j < G; ++j) {
         const uint32_t k = g2s[j];
         out[j >> 5] |= ((in[k >> 5] >> (k & 31)) & 1u) << (j & 31);
+    }
+}
+
+// ---- the WORD forms of the column un-permute (kernels.hip, k1_unslot_words): the permutation is the same for every row and plane, so
+// the bits of a group of R consecutive table rows (whole rows: four planes of Wp words) travel together.  A 4R x 32 bit block -- the
+// words (row r, plane p, slot word w) -- is transposed so that ONE entry holds one slot column of all R rows and four planes; the
+// entries of all slots of the group wait in LDS (T); gene word wo takes the entries of its 32 genes' slots, T[g2s[32 wo + c]], and a
+// second transpose makes the group's words (row r, plane p, gene word wo) of them.
+//   wide form   R = 8: 32-bit entries, one word of T per slot
+//   narrow form R = 4: 16-bit entries, two per word of T (the gene counts whose wide T no longer fits a workgroup's LDS)
+constexpr int kUnslotWide = 8, kUnslotNarrow = 4;   // a form is named by its rows per group
+constexpr size_t kUnslotLdsLimit = 160 * 1024;       // LDS a workgroup may have
+constexpr int kUnslotThreadsMax = 1024;              // threads of a workgroup at most (k1_unslot_words is compiled for this bound)
+
+// which bit of an entry is (row r of the group, plane p)
+REO_SLOTS_HD int unslot_bit(int row, int plane) { return 4 * row + plane; }
+
+// Where slot k's entry lies in T: the WORD index (wide) or the HALFWORD index (narrow).  The 32 entries of slot word w are stored by one
+// thread, neighbouring threads hold neighbouring w: 33 words per 32 entries (wide), 17 words per 32 entries with the entries of slots
+// b and b + 16 sharing a word (narrow: what the 16 x 32 transpose leaves in one register), keep a wave's stores off each other's banks.
+REO_SLOTS_HD uint32_t unslot_lds_index(int form, uint32_t k)
+{
+    const uint32_t w = k >> 5, b = k & 31u;
+    return form == kUnslotWide ? 33u * w + b : 2u * (17u * w + (b & 15u)) + (b >> 4);
+}
+
+// bytes of T for Gp slots
+REO_SLOTS_HD size_t unslot_lds_bytes(int form, int Gp) { return static_cast<size_t>(Gp / 32) * (form == kUnslotWide ? 33u * 4u : 17u * 4u); }
+
+// The word form for Gp slots, from the LDS it needs: narrow while THREE of its workgroups share a CU's LDS (up to 25 600 slots: measured
+// faster than wide at 5 120 and 20 480, equal within the spread at 10 240; profiles/unslot_words_forms_sweep.txt), else wide while its T fits at all (up to 38 912: one workgroup per CU, yet
+// faster than two narrow ones at 30 720 and 38 912 -- half the groups, twice the bytes in flight per thread), else narrow (fits 65 536).
+REO_SLOTS_HD int unslot_form(int Gp)
+{
+    if (3 * unslot_lds_bytes(kUnslotNarrow, Gp) <= kUnslotLdsLimit) return kUnslotNarrow;
+    return unslot_lds_bytes(kUnslotWide, Gp) <= kUnslotLdsLimit ? kUnslotWide : kUnslotNarrow;
+}
+
+// threads of a workgroup whose threads each take every blockDim-th of Wp words: as few trips as the bound allows, then as few threads
+REO_SLOTS_HD int unslot_threads(int Wp)
+{
+    const int trips = (Wp + kUnslotThreadsMax - 1) / kUnslotThreadsMax;
+    return ((Wp + trips - 1) / trips + 63) / 64 * 64;
+}
+
+#if defined(__clang__)
+#define REO_SLOTS_UNROLL _Pragma("unroll")
+#else
+#define REO_SLOTS_UNROLL
+#endif
+
+// N x N bit blocks of N words transposed in place by masked swaps (N = 32: one block; N = 16: the blocks of columns 0-15 and 16-31 side
+// by side): afterwards bit q of w[i] is what bit i of w[q] was (N = 16: and bit 16 + q of w[i] what bit 16 + i of w[q] was).  Its own inverse.
+template <int N>
+REO_SLOTS_HD void unslot_transpose(uint32_t (&w)[N])
+{
+    static_assert(N == 32 || N == 16, "4 R words");
+    uint32_t m = N == 32 ? 0x0000FFFFu : 0x00FF00FFu;
+    REO_SLOTS_UNROLL
+    for (int j = N / 2; j != 0; j >>= 1, m ^= (m << j)) {
+        REO_SLOTS_UNROLL
+        for (int k = 0; k < N; k = (k + j + 1) & ~j) {
+            const uint32_t t = ((w[k] >> j) ^ w[k + j]) & m;
+            w[k] ^= t << j;
+            w[k + j] ^= t;
+        }
+    }
+}
+
+// The steps of k1_unslot_words for one (slot or gene) word, shared by the kernel and the host model below.  T: the LDS image as words.
+// in: the 4R words (row r, plane p, slot word w) at m[unslot_bit(r, p)] (rows the group does not have: 0) -> their entries into T
+template <int R>
+REO_SLOTS_HD void unslot_in_word(uint32_t (&m)[4 * R], int w, uint32_t *T)
+{
+    unslot_transpose<4 * R>(m);
+    if (R == kUnslotWide) {
+        REO_SLOTS_UNROLL
+        for (int b = 0; b < 4 * R; ++b) T[unslot_lds_index(R, 32u * w + b)] = m[b];
+    } else {
+        REO_SLOTS_UNROLL
+        for (int i = 0; i < 4 * R; ++i) T[unslot_lds_index(R, 32u * w + i) >> 1] = m[i];   // (the entries of slots 32 w + i and 32 w + 16 + i)
+    }
+}
+
+// out: the entries of gene word wo's 32 slots (ks[c] = g2s[32 wo + c], clamped into the table) out of T -> the 4R words (row r, plane p,
+// gene word wo) in u[unslot_bit(r, p)], columns from G on zero
+template <int R>
+REO_SLOTS_HD void unslot_out_word(uint32_t (&u)[4 * R], const uint32_t (&ks)[32], int wo, const uint32_t *T, int G, int Gp)
+{
+    if (R == kUnslotWide) {
+        REO_SLOTS_UNROLL
+        for (int c = 0; c < 32; ++c) {
+            const uint32_t k = ks[c] < static_cast<uint32_t>(Gp) ? ks[c] : static_cast<uint32_t>(Gp - 1);
+            u[c % (4 * R)] = T[unslot_lds_index(R, k)];
+        }
+    } else {
+        const uint16_t *T16 = reinterpret_cast<const uint16_t *>(T);
+        REO_SLOTS_UNROLL
+        for (int c = 0; c < 32; ++c) {
+            const uint32_t k = ks[c] < static_cast<uint32_t>(Gp) ? ks[c] : static_cast<uint32_t>(Gp - 1);
+            const uint32_t e = T16[unslot_lds_index(R, k)];
+            if (c < 16) u[c % (4 * R)] = e;
+            else u[c % (4 * R)] |= e << 16;
+        }
+    }
+    unslot_transpose<4 * R>(u);
+    const int left = G - 32 * wo;   // columns of this word that are genes
+    const uint32_t valid = left >= 32 ? 0xFFFFFFFFu : (left <= 0 ? 0u : (1u << left) - 1u);
+    REO_SLOTS_UNROLL
+    for (int q = 0; q < 4 * R; ++q) u[q] &= valid;
+}
+
+// The serial host model of one workgroup of k1_unslot_words<R>: rows r0 .. r0 + R - 1 of a table of n_rows rows (whole rows, Wp words
+// per plane; the class table has n_rows = G) from slot-order columns into gene-order columns, in place; rows from n_rows on are neither
+// read nor written.  T: unslot_lds_bytes(R, 32 Wp).
+template <int R>
+inline void unslot_group_model(uint32_t *table, int r0, int n_rows, int G, int Wp, const uint32_t *g2s, uint32_t *T)
+{
+    const int nr = n_rows - r0 < R ? n_rows - r0 : R;
+    if (nr <= 0) return;
+    uint32_t *rows = table + static_cast<size_t>(r0) * 4 * Wp;
+    for (int w = 0; w < Wp; ++w) {
+        uint32_t m[4 * R];
+        for (int q = 0; q < 4 * R; ++q) m[q] = q < 4 * nr ? rows[static_cast<size_t>(q) * Wp + w] : 0u;
+        unslot_in_word<R>(m, w, T);
+    }
+    for (int wo = 0; wo < Wp; ++wo) {   // (behind the barrier)
+        uint32_t u[4 * R], ks[32];
+        for (int c = 0; c < 32; ++c) ks[c] = g2s[32 * wo + c];
+        unslot_out_word<R>(u, ks, wo, T, G, 32 * Wp);
+        for (int q = 0; q < 4 * nr; ++q) rows[static_cast<size_t>(q) * Wp + wo] = u[q];
     }
 }
 

@@ -274,7 +274,7 @@ struct K1Args {
     int32_t *park_ge;            // [items]: the slot's n_ge half is valid (the tie form stored it; else n_ge = n_gt: no tie in those samples)
     int park_mode;               // bit 0: add the parked counts of the blocks before this range; bit 1: park the sums instead of classifying
     // SLOT ORDER (k1w_pairs_slots; k1_slots.h): P and AL are then the planes in slot order, every index of the kernel is a slot, and
-    // only the table's ROW is looked up (s2g); the columns come back in gene order afterwards (k1_unslot_columns).  Else null.
+    // only the table's ROW is looked up (s2g); the columns come back in gene order afterwards (k1_unslot_words).  Else null.
     const uint32_t *s2g;         // [Gp] slot -> gene
     const uint32_t *trng, *crng; // [2 sides][Gp / 32], [2 sides][Gp / 256]: position ranges (min | max << 16) of the i-tiles and wave chunks
     // ITEM QUEUES (k1w_pairs_slots; k1_queue.h): the launch has one workgroup per wave slot of the device, and each takes items of the
@@ -844,7 +844,8 @@ __global__ __launch_bounds__(256) void k1_slot_gather(const uint4 *__restrict__ 
 // once for all R rows), and per row one 16-byte LDS read gives the four planes' words, out of which a shift and a funnel shift move
 // the bit into each plane's new word; the words of a bit row leave as coalesced 4-byte stores.  (The first form made 64 bits per
 // ballot, one lane per column: 25 instructions per row and 64 columns, 0.95 ms at config 3,
-// profiles/slots_kernel_stats_ballot_unslot.csv; this one 0.46 ms.)  Dynamic LDS = R x Wp x 16 bytes.
+// profiles/slots_kernel_stats_ballot_unslot.csv; this one 0.46 ms.)  Dynamic LDS = R x Wp x 16 bytes.  This is the BIT form: since the
+// word forms below (0.11 ms) it runs under REO_K1_UNSLOT=0 only, as their A/B partner and the second opinion of the tests.
 template <int R>
 __global__ __launch_bounds__(256) void k1_unslot_columns(uint32_t *__restrict__ table, const uint32_t *__restrict__ g2s, int G, int Wp)
 {
@@ -888,6 +889,44 @@ __global__ __launch_bounds__(256) void k1_unslot_columns(uint32_t *__restrict__ 
 #pragma unroll
                 for (int pl = 0; pl < 4; ++pl) rows[(static_cast<size_t>(r) * kPlanes + pl) * Wp + wo] = acc[r][pl] & valid;
             }
+    }
+}
+
+// The same, a WORD at a time (k1_slots.h, "the word forms": the index rules, the steps of a word and a serial host model of this
+// kernel, pinned by tests/k1_unslot_driver.cpp).  A workgroup takes R consecutive table rows.  IN: a thread loads the 4R words (row,
+// plane) of slot word w (coalesced over the threads' w), transposes the 4R x 32 bits in registers and stores one entry per slot --
+// the slot's column of all R rows and four planes -- into T in LDS.  Behind the barrier, OUT: for gene word wo a thread takes the 32
+// slots g2s[32 wo ..] (eight 16-byte loads), reads their entries (one 4- or 2-byte LDS read per 4R bits; the bit form reads 16 bytes
+// per 4), transposes back and stores the 4R words (coalesced over wo).  In place: every word of the rows is in T before the barrier and
+// no other workgroup touches them.  Dynamic LDS = unslot_lds_bytes(R, Gp); R = 8: 32-bit entries, R = 4: 16-bit entries.
+template <int R>
+__global__ __launch_bounds__(kUnslotThreadsMax) void k1_unslot_words(uint32_t *__restrict__ table, const uint32_t *__restrict__ g2s, int G, int Wp)
+{
+    constexpr int NQ = 4 * R;
+    extern __shared__ uint32_t unslot_t[];
+    const int r0 = blockIdx.x * R, nr = min(R, G - r0);
+    if (nr <= 0) return;
+    const int nq = nr * kPlanes;   // (the last group's missing rows are neither loaded nor stored)
+    uint32_t *rows = table + static_cast<size_t>(r0) * kPlanes * Wp;
+    for (int w = threadIdx.x; w < Wp; w += blockDim.x) {
+        uint32_t m[NQ];
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) m[q] = q < nq ? rows[static_cast<size_t>(q) * Wp + w] : 0u;   // (wave-uniform)
+        unslot_in_word<R>(m, w, unslot_t);
+    }
+    __syncthreads();   // every word of these rows is in T: from here on they are only written
+    for (int wo = threadIdx.x; wo < Wp; wo += blockDim.x) {
+        const uint4 *kq = reinterpret_cast<const uint4 *>(g2s) + static_cast<size_t>(wo) * 8;   // (g2s holds Gp = 32 Wp slots)
+        uint32_t ks[32], u[NQ];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const uint4 k4 = kq[i];
+            ks[4 * i] = k4.x; ks[4 * i + 1] = k4.y; ks[4 * i + 2] = k4.z; ks[4 * i + 3] = k4.w;
+        }
+        unslot_out_word<R>(u, ks, wo, unslot_t, G, 32 * Wp);
+#pragma unroll
+        for (int q = 0; q < NQ; ++q)
+            if (q < nq) rows[static_cast<size_t>(q) * Wp + wo] = u[q];
     }
 }
 
@@ -4341,6 +4380,31 @@ static int32_t k1_slots_front(reo_ctx *c, K1Args &a)
 // behind it: the table's columns back into gene order (its rows were written in gene order)
 static int32_t k1_slots_back(reo_ctx *c, const K1Args &a)
 {
+    // the word forms (k1_unslot_words; REO_K1_UNSLOT unset: the form of unslot_form; 8 or 4: that form wherever its LDS fits)
+    if (c->k1_unslot != 0) {
+        int form = unslot_form(a.Gp);
+        if ((c->k1_unslot == kUnslotWide || c->k1_unslot == kUnslotNarrow) && unslot_lds_bytes(c->k1_unslot, a.Gp) <= kUnslotLdsLimit) form = c->k1_unslot;
+        const size_t lds = unslot_lds_bytes(form, a.Gp);
+        if (lds <= kUnslotLdsLimit) {   // (a slot build has at most 65 535 genes: the narrow form always fits)
+            auto go = [&](auto rtag) -> int32_t {
+                constexpr int R = decltype(rtag)::value;
+                const int bit = R == kUnslotWide ? 1 : 2;
+                if (!(c->k1_unslot_attr & bit)) {   // more than 64 KB of dynamic LDS: once per context and form
+                    REO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k1_unslot_words<R>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kUnslotLdsLimit)));
+                    c->k1_unslot_attr |= bit;
+                }
+                k1_unslot_words<R><<<static_cast<unsigned>((a.G + R - 1) / R), static_cast<unsigned>(unslot_threads(a.Wp)), lds, c->stream>>>(a.table, slot_maps(c).g2s, a.G, a.Wp);
+                return REO_OK;
+            };
+            const int32_t rc = form == kUnslotWide ? go(std::integral_constant<int, kUnslotWide>{}) : go(std::integral_constant<int, kUnslotNarrow>{});
+            if (rc) return rc;
+            REO_HIP_CHECK(hipGetLastError());
+            c->last_k1_unslot = form;
+            return REO_OK;
+        }
+    }
+    // the bit form (REO_K1_UNSLOT=0: the A/B partner of the word forms and the second opinion of the tests)
+    c->last_k1_unslot = 1;
     // rows per workgroup: as many as fit 60 KB of LDS (six up to 20 480 genes, four up to 30 720, two up to 61 440, else one).  60 and not
     // the 64 KB that a launch may ask for without a function attribute: 16 bytes x Gp / 32 per row and Gp a multiple of 1 024 make a row a
     // multiple of 512 bytes, six rows of 20 480 genes and four of 30 720 are 60 KB exactly, and two such workgroups (120 KB) still share a

@@ -262,6 +262,10 @@ struct reo_ctx {
     // with the genes ordered by level, and the table's rows and columns come back in gene order before launch_k1 returns
     int k1_slots = 1;                   // REO_K1_SLOTS=0: the identity order for everything (A/B, tests)
     int last_k1_slots = 0;              // reo_get_info 25: the last build of the class table used the slot order
+    int k1_unslot = -1;                 // REO_K1_UNSLOT: the column un-permute behind a slot build -- unset: the word form of unslot_form (k1_slots.h); 0: the bit form
+                                        // (k1_unslot_columns; A/B, tests); 8 or 4: that word form wherever its LDS fits (tests)
+    int last_k1_unslot = 0;             // reo_get_info 28: the un-permute of the last build (0: no slot build; 1: the bit form; 8 or 4: the word forms)
+    int k1_unslot_attr = 0;             // word forms whose kernel has been given its LDS size (bit 0: wide, bit 1: narrow)
     const uint32_t *k1_slot_items = nullptr;   // ... and its item list (one of k1_wave_items), for the count of separated items (reo_get_info 26)
     size_t k1_slot_items_n = 0;
     int k1_slot_gp = 0;                 // ... and the padded gene count its maps and ranges are laid out for
