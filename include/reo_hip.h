@@ -334,6 +334,39 @@ int32_t reo_sample_counts(reo_ctx *ctx, const int32_t *genes, int64_t n_genes,
                           int32_t *n_sel /* n_genes; may be NULL */,
                           int32_t *n_gt, int32_t *n_eq /* n_genes x S row-major, ld = S; n_eq may be NULL */);
 
+/* Pair support: HOW STRONGLY a listed pair supports a call.  The tallies say that gene i's order against the reference genes reversed, the
+ * pair lists say against which genes, the sample counts in which samples summed over the partners; this call says, for every single listed
+ * pair, in how many samples of each group gene i lies above its partner -- "above it in 498 of 500 control samples and in 3 of 500 treated
+ * ones" -- and, on request, the outcome in every sample.  The reference has no such output.
+ * The pairs come as a CSR, exactly what reo_pair_list delivers (a caller may as well hand in pairs of its own, a published signature):
+ * for entry e of row q, i = genes[q] (any order, repeats allowed), j = partner[e] (any order, repeats allowed, never i), rowptr[0] = 0,
+ * rowptr[n_genes] entries in all; empty rows are fine, and a list without entries returns REO_OK without a launch.  For every group g of
+ * reo_set_groups
+ *     n_gt[e * ngroups + g] = #{samples of g : x_i > x_j and not tied}        n_eq[e * ngroups + g] = #{samples of g : tied}
+ * the values and the per-pair layout of reo_pair_counts widened to int32 (no limit of 65 535 samples), by the comparator of the resident
+ * matrix's element type as the rank/band transform encodes it: Float64 the 0.1 band, Float32 the Float32 rule above, Int64 and Int32
+ * equality; of two equal infinities the gene with the larger index is the greater one and nothing is tied.  No tie coin is drawn: ties are
+ * reported as ties.  n_eq == NULL: the tied counts are not computed (without `outcome`, half of the compare work).
+ * outcome (may be NULL): outcome[e * S + s] = 0 (x_i < x_j), 1 (tied), 2 (x_i > x_j) for sample s in the CALLER's column order.
+ * Needs the matrix, the groups and the transform (run here if need be, as by reo_pair_counts); needs no class table, no thresholds and no
+ * reference mask, reads none of the iteration's buffers and writes none: reo_get_ref_mask and a following reo_identify_degs behave as if
+ * the call had not happened.  Both plane layouts (up to and above 65 535 genes), every S.
+ * One kernel (csrc/pairsupport.hip): the host cuts every row into work items of at most 64 consecutive entries, one wave per item and one
+ * lane per entry; the wave walks the groups' blocks of 32 sample slots with the band edges of gene i wave-uniform, every lane runs the borrow
+ * chain of the pair kernel against its own partner and adds the popcounts.  The outcome bytes are stored lane by lane, not coalesced:
+ * meant for signatures of hundreds of pairs.  Device temporaries are bounded and sized from the list: the entries go in batches whose two
+ * count buffers (batch x ngroups x 4 bytes) and outcome buffer (batch x S bytes) stay under 32 MiB each (at least one entry per batch);
+ * REO_PAIR_SUPPORT_BATCH in the environment, read per call, lowers the batch to that many entries (tests of the batch seam).
+ * Host arrays only; no stage timer of its own.
+ * REO_EINVAL, each with its own message that names reo_pair_support, all checked on the host before anything is uploaded, and a refused
+ * call writes nothing: a NULL genes, rowptr or n_gt; n_genes < 1 or above 2^30; a gene outside [0, G); rowptr[0] != 0 or a decreasing
+ * rowptr; a NULL partner with rowptr[n_genes] > 0; a partner outside [0, G); a partner that equals its row's gene (the diagonal is no
+ * pair, reo_pair_list never lists it); a reo_create_multi context. */
+int32_t reo_pair_support(reo_ctx *ctx, const int32_t *genes, int64_t n_genes,
+                         const int64_t *rowptr /* n_genes + 1 */, const int32_t *partner /* rowptr[n_genes] */,
+                         int32_t *n_gt, int32_t *n_eq /* entries x ngroups, row-major; n_eq may be NULL */,
+                         uint8_t *outcome /* entries x S, row-major, caller's column order; may be NULL */);
+
 /* McCullagh test on 3x3 tables given as 9 tallies each (n x 9 row-major),
  * evaluated by the device routine the iteration uses; out is n x 5 row-major
  * (pval, delta1, delta2, se, z1) -- src/RankCompV3.jl:225-259. */

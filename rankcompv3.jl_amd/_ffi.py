@@ -32,7 +32,7 @@ SYMBOLS = [
     "reo_set_profiling", "reo_reset_timings", "reo_get_timings", "reo_get_info",
     "reo_pseudobulk_dense_f64", "reo_pseudobulk_dense_i64", "reo_pseudobulk_csc_f64", "reo_pseudobulk_csc_i64",
     "reo_set_matrix_pseudobulk_dense_f64", "reo_set_matrix_pseudobulk_dense_i64", "reo_set_matrix_pseudobulk_csc_f64", "reo_set_matrix_pseudobulk_csc_i64",
-    "reo_filter_matrix", "reo_get_matrix", "reo_get_ref_mask", "reo_pair_list", "reo_sample_counts",
+    "reo_filter_matrix", "reo_get_matrix", "reo_get_ref_mask", "reo_pair_list", "reo_sample_counts", "reo_pair_support",
 ] + [f"reo_set_matrix_{form}_{t}" for form in ("csc_dev", "pseudobulk_csc_dev", "pseudobulk_dense_dev") for t in ("f64", "i64", "f32", "i32")]
 
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p)
@@ -138,6 +138,7 @@ def lib() -> ctypes.CDLL:
         "reo_get_ref_mask": (i32, [vp, vp, vp]),
         "reo_pair_list": (i32, [vp, vp, i64, vp, ctypes.c_uint32, vp, vp, vp, i64]),
         "reo_sample_counts": (i32, [vp, vp, i64, vp, ctypes.c_uint32, vp, vp, vp]),
+        "reo_pair_support": (i32, [vp, vp, i64, vp, vp, vp, vp, vp]),
     }
     for t in ("f64", "i64", "f32", "i32"):   # SPARSE ON THE DEVICE
         sig["reo_set_matrix_csc_dev_" + t] = (i32, [vp, i64, i64, i64, vp, vp, i32, vp])
@@ -331,6 +332,58 @@ class SampleCounts(NamedTuple):
         return (self.n_sel[:, None] - self.n_gt - self.n_eq).astype(np.int32)
 
 
+class PairSupport(NamedTuple):
+    """reo_pair_support: how strongly every listed pair supports a call.  The CSR is the one that was handed in (entry e of row q: gene
+    genes[q] against partner[e]); per entry and group, in how many of the group's samples the gene lies above its partner (n_gt) or level
+    with it (n_eq; None when the call was made with ties=False), and optionally the outcome in every sample."""
+    genes: np.ndarray        # int32, the rows as given
+    rowptr: np.ndarray       # int64, len(genes) + 1
+    partner: np.ndarray      # int32
+    code: np.ndarray | None  # uint8, the list's class codes; None for pairs that came without
+    n_gt: np.ndarray         # int32, entries x ngroups
+    n_eq: np.ndarray | None  # int32, entries x ngroups
+    outcome: np.ndarray | None   # uint8, entries x S in the caller's column order: 0 below, 1 tied, 2 above
+    group_sizes: np.ndarray  # int64, ngroups: the samples of every group
+
+    def row(self, q: int):
+        """(partner, n_gt, n_eq) of row q."""
+        a, b = int(self.rowptr[q]), int(self.rowptr[q + 1])
+        return self.partner[a:b], self.n_gt[a:b], None if self.n_eq is None else self.n_eq[a:b]
+
+    @property
+    def entry_genes(self) -> np.ndarray:
+        """The gene of every entry (genes[q] repeated over row q), int32."""
+        return np.repeat(self.genes, np.diff(self.rowptr)).astype(np.int32)
+
+    @property
+    def n_lt(self) -> np.ndarray:
+        """group size - n_gt - n_eq; needs the tied counts (ties=True)."""
+        if self.n_eq is None:
+            raise DimensionMismatch(REO_EINVAL, "n_lt needs the tied counts: call pair_support with ties=True")
+        return (np.asarray(self.group_sizes, dtype=np.int64)[None, :] - self.n_gt - self.n_eq).astype(np.int32)
+
+    @property
+    def frac_gt(self) -> np.ndarray:
+        """n_gt / group size, float64, entries x ngroups."""
+        return self.n_gt.astype(np.float64) / np.asarray(self.group_sizes, dtype=np.float64)[None, :]
+
+    def delta(self, k: int = 0) -> np.ndarray:
+        """Per entry: the fraction of group k's samples with the gene above its partner minus that fraction over all other samples -- the
+        two sides that reo_build_pairs(k) compares.  float64."""
+        sizes = np.asarray(self.group_sizes, dtype=np.int64)
+        if not 0 <= int(k) < sizes.size:
+            raise DimensionMismatch(REO_EINVAL, f"delta: group {k} is outside [0, {sizes.size})")
+        k = int(k)
+        rest = self.n_gt.sum(axis=1, dtype=np.int64) - self.n_gt[:, k]
+        return self.n_gt[:, k].astype(np.float64) / float(sizes[k]) - rest.astype(np.float64) / float(sizes.sum() - sizes[k])
+
+    def top(self, n: int, k: int = 0) -> np.ndarray:
+        """The indices of the n entries with the largest |delta(k)|, largest first; equal |delta| in ascending (gene, partner) order."""
+        d = np.abs(self.delta(k))
+        order = np.lexsort((self.partner, self.entry_genes, -d))   # (the last key is the primary one)
+        return order[: max(int(n), 0)]
+
+
 class SampleScores(NamedTuple):
     """Per DEG (row) and sample (column): of the gene's n_pairs reversed pairs (n13 and n31 against the partner set), how many show the
     order of the non-control side in that sample (treat_like), how many the control's (ctrl_like), how many are tied."""
@@ -448,6 +501,7 @@ class Context:
         self._keep = []  # keeps callbacks / device tensors alive
         self.G = self.S = 0
         self.ngroups = 0
+        self._group_id = np.zeros(0, dtype=np.int32)
 
     def close(self) -> None:
         if self._h:
@@ -507,6 +561,7 @@ class Context:
         gid = np.ascontiguousarray(group_id, dtype=np.int32)
         check(self._L.reo_set_groups(self._h, _ptr(gid), gid.size, int(ngroups)))
         self.ngroups = int(ngroups)
+        self._group_id = gid.copy()   # (pair_support: the group sizes)
 
     def compute_thresholds(self, pval_reo: float) -> np.ndarray:
         check(self._L.reo_compute_thresholds(self._h, float(pval_reo)))
@@ -667,6 +722,43 @@ class Context:
     def sample_scores(self, genes, partner_mask=None) -> SampleScores:
         """Per sample, how far every query gene's reversed pairs (n13, n31) show the non-control order: two sample_counts calls."""
         return sample_scores_from(self.sample_counts(genes, "n13", partner_mask), self.sample_counts(genes, "n31", partner_mask))
+
+    def pair_support_raw(self, genes, rowptr, partner, n_gt, n_eq, outcome) -> None:
+        """reo_pair_support on caller-made arrays (any may be None); pair_support is the convenient form."""
+        check(self._L.reo_pair_support(self._h, _ptr(genes) if genes is not None and genes.size else None, 0 if genes is None else genes.size,
+                                       None if rowptr is None else _ptr(rowptr), _ptr(partner) if partner is not None and partner.size else None,
+                                       None if n_gt is None else _ptr(n_gt), None if n_eq is None else _ptr(n_eq),
+                                       None if outcome is None else _ptr(outcome)))
+
+    def pair_support(self, pairs, ties=True, outcomes=False) -> PairSupport:
+        """How strongly (reo_pair_support): for every pair of `pairs` -- a PairList, or a (genes, rowptr, partner) triple of the caller's
+        own -- and every group, in how many samples the row's gene lies above the partner, and in how many the two are tied.  ties=False:
+        no tied counts (n_eq None).  outcomes=True: also the outcome of every sample, entries x S bytes (0 below, 1 tied, 2 above) in the
+        caller's column order -- meant for signatures of hundreds of pairs.  Needs the matrix and the groups, no class table."""
+        code = None
+        if isinstance(pairs, PairList):
+            genes, rowptr, partner, code = pairs
+        else:
+            genes, rowptr, partner = pairs
+        g = np.ascontiguousarray(genes, dtype=np.int32).reshape(-1)
+        rp = np.ascontiguousarray(rowptr, dtype=np.int64).reshape(-1)
+        pa = np.ascontiguousarray(partner, dtype=np.int32).reshape(-1)
+        if rp.size != g.size + 1:
+            raise DimensionMismatch(REO_EINVAL, f"pair_support: rowptr has {rp.size} entries for {g.size} rows (one more is needed)")
+        if rp.size and int(rp[-1]) != pa.size:
+            raise DimensionMismatch(REO_EINVAL, f"pair_support: rowptr lists {int(rp[-1])} entries, partner has {pa.size}")
+        if code is not None:
+            code = np.asarray(code)
+            if code.size != pa.size:
+                raise DimensionMismatch(REO_EINVAL, f"pair_support: code has {code.size} entries, partner has {pa.size}")
+        n, ng, S = pa.size, max(self.ngroups, 1), max(self.S, 1)
+        n_gt = np.zeros((n, ng), dtype=np.int32)
+        n_eq = np.zeros_like(n_gt) if ties else None
+        outcome = np.zeros((n, S), dtype=np.uint8) if outcomes else None
+        if g.size:   # (no rows: nothing to ask; the library refuses n_genes < 1)
+            self.pair_support_raw(g, rp, pa, n_gt, n_eq, outcome)
+        sizes = np.bincount(np.asarray(self._group_id, dtype=np.int64), minlength=ng)[:ng].astype(np.int64)
+        return PairSupport(g, rp, pa, code, n_gt, n_eq, None if outcome is None else outcome[:, : self.S], sizes)
 
     def mccullagh(self, cont) -> np.ndarray:
         cont = np.ascontiguousarray(cont, dtype=np.int32).reshape(-1, 9)

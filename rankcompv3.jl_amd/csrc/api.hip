@@ -16,6 +16,7 @@
 #include "pair_list.h"
 #include "reo_internal.h"
 #include "sample_counts.h"
+#include "pair_support.h"
 #include "upload_csc.h"
 
 #include <mutex>
@@ -594,7 +595,7 @@ using namespace reo;
 
 extern "C" {
 
-int32_t reo_version(void) { return 700; }
+int32_t reo_version(void) { return 800; }
 
 int32_t reo_trim_memory(void)
 {
@@ -1546,6 +1547,63 @@ int32_t reo_sample_counts(reo_ctx *c, const int32_t *genes, int64_t n_genes, con
         if (n_eq) REO_HIP_CHECK(hipMemcpyAsync(n_eq + static_cast<size_t>(q0) * S, d_eq.p, rows * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
         if (n_sel) REO_HIP_CHECK(hipMemcpyAsync(n_sel + q0, d_sel.p, static_cast<size_t>(nq) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
         if ((rc = wait_or_drop_table(c))) return rc;   // the next batch reuses the buffers
+    }
+    drain.dismiss();
+    return REO_OK;
+}
+
+// How strongly (include/reo_hip.h): every check on the host first (pair_support.h), then the entries in batches whose count buffers and
+// outcome buffer stay under the budget; per batch the work items and the partners go up, one launch, and the batch's rows come back into
+// the caller's arrays.  Reads the bit planes of the transform and nothing of the class table or the iteration; writes none of them.
+int32_t reo_pair_support(reo_ctx *c, const int32_t *genes, int64_t n_genes, const int64_t *rowptr, const int32_t *partner, int32_t *n_gt,
+                         int32_t *n_eq, uint8_t *outcome)
+{
+    int32_t rc = no_multi(c, "reo_pair_support");
+    if (rc || (rc = use(c))) return rc;
+    if (c->dtype == 0 || c->group_id.empty() || static_cast<int64_t>(c->group_id.size()) != c->S) return ensure_transform(c);   // (its refusals: nothing runs)
+    char msg[320];
+    if (pair_support_check_args(c->G, genes, n_genes, rowptr, partner, n_gt, msg, sizeof msg)) { set_error("%s", msg); return REO_EINVAL; }
+    const int64_t total = rowptr[n_genes];
+    if (total == 0) return REO_OK;   // nothing listed: no transform, no launch
+    if ((rc = ensure_transform(c))) return rc;
+    const int64_t S = c->S, ng = c->ngroups;
+    std::vector<int32_t> map;
+    if (outcome && (!sc_slot_map(c->group_id.data(), S, c->ngroups, map) || c->goff32.empty() || static_cast<int64_t>(map.size()) != c->goff32.back())) {
+        set_error("reo_pair_support: the sample slots of the bit planes do not match the group labels");
+        return REO_EHIP;
+    }
+    const char *env = getenv("REO_PAIR_SUPPORT_BATCH");
+    const int64_t batch = ps_batch_entries(total, ng, S, outcome != nullptr, env ? atoll(env) : 0);
+    const size_t nb = static_cast<size_t>(batch);
+    DevBuf<PsItem> d_items;
+    DevBuf<int32_t> d_partner, d_gt, d_eq;
+    DevBuf<uint8_t> d_out;
+    if ((rc = d_items.ensure(nb)) || (rc = d_partner.ensure(nb)) || (rc = d_gt.ensure(nb * ng)) || (n_eq && (rc = d_eq.ensure(nb * ng))) ||
+        (outcome && ((rc = d_out.ensure(nb * static_cast<size_t>(S))) || (rc = c->sc_slot2col.ensure(map.size())))))
+        return rc;
+    std::vector<PsItem> items;
+    DrainOnExit drain(c);   // items and partners in, counts and outcomes out (declared after the buffers: the wait comes before their release)
+    if (outcome && (map != c->sc_slot2col_host || c->sc_slot2col.p != c->sc_slot2col_uploaded)) {   // once per change of the groups (shared with reo_sample_counts)
+        c->sc_slot2col_host = map;
+        c->sc_slot2col_uploaded = nullptr;
+        REO_HIP_CHECK(hipMemcpyAsync(c->sc_slot2col.p, c->sc_slot2col_host.data(), map.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        c->sc_slot2col_uploaded = c->sc_slot2col.p;
+    }
+    int64_t row = 0;
+    for (int64_t e0 = 0; e0 < total; e0 += batch) {
+        const int64_t ne = std::min(batch, total - e0);
+        ps_build_items(genes, rowptr, n_genes, e0, e0 + ne, &row, items);
+        if (items.empty() || static_cast<int64_t>(items.size()) > ne) { set_error("reo_pair_support: %zu work items for %lld entries", items.size(), (long long)ne); return REO_EHIP; }
+        const size_t n = static_cast<size_t>(ne);
+        REO_HIP_CHECK(hipMemcpyAsync(d_items.p, items.data(), items.size() * sizeof(PsItem), hipMemcpyHostToDevice, c->stream));
+        REO_HIP_CHECK(hipMemcpyAsync(d_partner.p, partner + e0, n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        if ((rc = launch_pair_support(c, d_items.p, static_cast<int64_t>(items.size()), d_partner.p, outcome ? c->sc_slot2col.p : nullptr, d_gt.p,
+                                      n_eq ? d_eq.p : nullptr, outcome ? d_out.p : nullptr)))
+            return rc;
+        REO_HIP_CHECK(hipMemcpyAsync(n_gt + static_cast<size_t>(e0) * ng, d_gt.p, n * ng * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        if (n_eq) REO_HIP_CHECK(hipMemcpyAsync(n_eq + static_cast<size_t>(e0) * ng, d_eq.p, n * ng * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        if (outcome) REO_HIP_CHECK(hipMemcpyAsync(outcome + static_cast<size_t>(e0) * S, d_out.p, n * static_cast<size_t>(S), hipMemcpyDeviceToHost, c->stream));
+        if ((rc = wait_or_drop_table(c))) return rc;   // the next batch reuses the buffers and the item list
     }
     drain.dismiss();
     return REO_OK;

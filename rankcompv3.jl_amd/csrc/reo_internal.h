@@ -421,6 +421,13 @@ int plane_bits(int64_t G);   // kernels.hip: position planes that the count loop
 int32_t launch_sample_counts(reo_ctx *c, const int32_t *d_genes, int64_t n_queries, const uint32_t *d_maskbits, uint32_t class_mask,
                              const int32_t *d_slot2col, int32_t *d_sel, int32_t *d_gt, int32_t *d_eq);
 
+// pairsupport.hip: the kernel of reo_pair_support (work items, batches and host checks: pair_support.h).  d_items: [n_items] work items of the
+// batch; d_partner: [entries of the batch] partners, checked by the caller to lie in [0, G) and off the diagonal; d_slot2col as above (read
+// only with d_outcome); d_gt / d_eq: [entries][ngroups] (d_eq null: no tied counts); d_outcome: [entries][S] bytes or null
+struct PsItem;
+int32_t launch_pair_support(reo_ctx *c, const PsItem *d_items, int64_t n_items, const int32_t *d_partner, const int32_t *d_slot2col,
+                            int32_t *d_gt, int32_t *d_eq, uint8_t *d_outcome);
+
 // pseudobulk.hip: the checks, upload and kernels of reo_pseudobulk_*, the G x n_out sums left in c->dX_owned (ld = G) instead of a host array
 int32_t pseudobulk_resident_dense(reo_ctx *c, const void *X, bool is_int, int64_t G, int64_t C, int64_t ld, const int32_t *order,
                                   int64_t n_order, const int32_t *chunk_ptr, int32_t n_out);

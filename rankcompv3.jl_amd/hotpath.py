@@ -15,7 +15,7 @@ from typing import NamedTuple
 import numpy as np
 
 from . import _ffi, synth
-from ._ffi import PairList, SampleCounts, SampleScores, class_mask  # noqa: F401
+from ._ffi import PairList, PairSupport, SampleCounts, SampleScores, class_mask  # noqa: F401
 
 HEADER = ["pval", "padj", "n11", "n12", "n13", "n21", "n22", "n23", "n31", "n32", "n33",
           "Δ1", "Δ2", "se", "z1", "up_down"]  # src/RankCompV3.jl:665
@@ -97,6 +97,37 @@ def deg_sample_scores(ctx, labels) -> dict:
     return {"sample_scores": ctx.sample_scores(degs)}
 
 
+def need_pairs_for_support(pairs, pair_support) -> None:
+    """pair_support=True asks for the support of the comparison's pair list: without `pairs` there is no list.  Raised before any context is
+    opened."""
+    if pair_support and pairs is None:
+        raise _ffi.DimensionMismatch(_ffi.REO_EINVAL, "pair_support=True needs `pairs`: it is the support of the comparison's pair list "
+                                                      "(pass pairs=\"reversed\" or another class selection)")
+
+
+def deg_pair_support(ctx, pair_list) -> dict:
+    """{"pair_support"} of the comparison whose pair list has just been taken on `ctx`: the PairSupport of that list (tied counts, no
+    outcomes).  An empty list: an empty object, no library call for it."""
+    return {"pair_support": ctx.pair_support(pair_list)}
+
+
+def write_pair_support_tsv(path, gene_names, levels, support) -> None:
+    """gene<TAB>partner<TAB>class, then <level>_gt and <level>_eq per group level, one line per listed pair in the list's own order; names
+    from gene_names, the class as its tally's header name (n13, ...; empty for pairs that came without class codes); a header line, "\n"
+    line ends, like the result writers of reoa.  Needs the tied counts."""
+    if support.n_eq is None:
+        raise _ffi.DimensionMismatch(_ffi.REO_EINVAL, "write_pair_support_tsv needs the tied counts: call pair_support with ties=True")
+    names = _ffi.CLASS_NAMES
+    with open(path, "w") as f:
+        f.write("\t".join(["gene", "partner", "class"] + [f"{lv}_{w}" for lv in levels for w in ("gt", "eq")]) + "\n")
+        for q, g in enumerate(support.genes):
+            gname = gene_names[int(g)]
+            for e in range(int(support.rowptr[q]), int(support.rowptr[q + 1])):
+                cls = "" if support.code is None else names[int(support.code[e])]
+                cells = [str(int(v)) for pair in zip(support.n_gt[e], support.n_eq[e]) for v in pair]
+                f.write("\t".join([str(gname), str(gene_names[int(support.partner[e])]), cls] + cells) + "\n")
+
+
 def write_sample_scores_tsv(path, gene_names, sample_names, scores) -> None:
     """gene<TAB>n_pairs<TAB>one column per sample, one row per scored gene, cells = scores.net; "\n" line ends, like the result writers."""
     net = scores.net
@@ -121,7 +152,7 @@ def write_pairs_tsv(path, gene_names, pair_list) -> None:
 
 def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref_gene, n_iter, n_conv, *,
                       seed: int = 0, device: int = -1, shard=(0, 1), allreduce=None, allgather=None, profile: bool = False,
-                      pairs=None, sample_scores: bool = False) -> DegRun:
+                      pairs=None, sample_scores: bool = False, pair_support: bool = False) -> DegRun:
     """identify_degs with the extras (trace, timings) kept.  `data` is a host matrix (numpy, anything np.asarray takes) or a torch
     tensor on a ROCm device, which is used in place (_ffi.device_matrix).  A column-major host matrix is read in place; a row-major one
     (numpy's default C order, column slices of a wider C-ordered array) is copied column-major on the host first, or, with REO_ROWMAJOR=1
@@ -141,7 +172,12 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
     still the current one.  None (the default): no further call is made and the dicts have the keys they always had.
     `sample_scores` (not in the reference): True adds "sample_scores" to every comparison dict, the SampleScores of its DEGs against the
     reference set of its tallies (Context.sample_scores; rows = DEGs ascending, columns = the samples as given), taken at the same moment.
-    False (the default): no further call, no new key."""
+    False (the default): no further call, no new key.
+    `pair_support` (not in the reference): True needs `pairs` (DimensionMismatch otherwise) and adds "pair_support" to every comparison
+    dict, the PairSupport of that comparison's pair list (Context.pair_support: per listed pair and group, in how many samples the DEG lies
+    above its partner, and in how many the two are tied), taken at the same moment as "pairs".  False (the default): no further call, no new
+    key."""
+    need_pairs_for_support(pairs, pair_support)
     # a torch tensor on a ROCm device: a strided one is used where it is, a sparse one is made dense there (its device is the context's)
     on_device = _ffi.is_device_sparse(data) or _ffi.is_device_tensor(data)
     if on_device:
@@ -183,6 +219,8 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
                           "iters_run": iters, "trace": trace})
             if pairs is not None:
                 comps[-1].update(deg_pairs(ctx, comps[-1]["labels"], pairs))
+                if pair_support:
+                    comps[-1].update(deg_pair_support(ctx, comps[-1]["pairs"]))
             if sample_scores:
                 comps[-1].update(deg_sample_scores(ctx, comps[-1]["labels"]))
         timings = ctx.timings() if profile else {}
@@ -223,7 +261,7 @@ class CellsDegRun(NamedTuple):
 
 def identify_degs_cells(cells, cell_group, gene_names, n_pseudo, pval_reo, pval_deg, padj_deg, ref_gene, n_iter, n_conv, *,
                         min_profiles: int = 0, min_features: int = 0, ref_gene_max: int = 3000, seed: int = 0, device: int = 0,
-                        profile: bool = False, pairs=None, sample_scores: bool = False) -> CellsDegRun:
+                        profile: bool = False, pairs=None, sample_scores: bool = False, pair_support: bool = False) -> CellsDegRun:
     """Cells to DEGs without a host trip for the profiles: `cells` is a genes x cells matrix (scipy.sparse, anything np.asarray takes, or
     a torch tensor on a ROCm device -- sparse or strided -- which is read where it is: reo_set_matrix_pseudobulk_*_dev_*),
     cell_group one label per cell.  cells_partition -> the pseudo-bulk sums written into the context's matrix (set_matrix_pseudobulk) ->
@@ -231,7 +269,9 @@ def identify_degs_cells(cells, cell_group, gene_names, n_pseudo, pval_reo, pval_
     pair table and iteration as in run_identify_degs.  ref_gene is a bool mask over the INPUT genes (subset by gene_kept here), or None for
     synth.ref_mask(G', min(G', ref_gene_max), seed), the draw reoa makes.  Bit-identical to Context.pseudobulk -> numpy filters ->
     run_identify_degs on the same seed.  (reoa() keeps its host route: its writers want the profile matrix on the host.)
-    `pairs`, `sample_scores`: as in run_identify_degs; gene indices are those of the KEPT genes (run.gene_names), columns the kept profiles."""
+    `pairs`, `sample_scores`, `pair_support`: as in run_identify_degs; gene indices are those of the KEPT genes (run.gene_names), columns
+    the kept profiles."""
+    need_pairs_for_support(pairs, pair_support)
     on_device = _ffi.is_device_sparse(cells) or _ffi.is_device_tensor(cells)
     if on_device:   # a torch tensor on a ROCm device, sparse or strided: summed where it is, on its own device
         device = cells.device.index if cells.device.index is not None else -1
@@ -268,6 +308,8 @@ def identify_degs_cells(cells, cell_group, gene_names, n_pseudo, pval_reo, pval_
             comps.append({"k": k, "result": result, "labels": label_genes(result, pval_deg, padj_deg), "iters_run": iters, "trace": trace})
             if pairs is not None:
                 comps[-1].update(deg_pairs(ctx, comps[-1]["labels"], pairs))
+                if pair_support:
+                    comps[-1].update(deg_pair_support(ctx, comps[-1]["pairs"]))
             if sample_scores:
                 comps[-1].update(deg_sample_scores(ctx, comps[-1]["labels"]))
         timings = ctx.timings() if profile else {}

@@ -18,7 +18,7 @@ import os
 import numpy as np
 
 from . import _ffi, synth
-from .hotpath import HEADER, run_identify_degs, write_pairs_tsv, write_sample_scores_tsv
+from .hotpath import HEADER, need_pairs_for_support, run_identify_degs, write_pair_support_tsv, write_pairs_tsv, write_sample_scores_tsv
 
 log = logging.getLogger("reo_hip")
 
@@ -275,7 +275,7 @@ def reoa(fn_expr: str = "fn_expr.txt", fn_meta: str = "fn_meta.txt", *, expr_thr
          n_pseudo: int = 0, use_hk_genes: str = "yes", hk_file: str | None = None, gene_name_type: str = "ENSEMBL",
          ref_gene_max: int = 3000, ref_gene_min: int = 100, n_iter: int = 128, n_conv: int = 5, work_dir: str = "./",
          use_testdata: str = "no", seed: int = 0, device: int = -1, testdata_dir: str | None = None, align_meta: bool | None = None,
-         pairs=None, sample_scores: bool = False):
+         pairs=None, sample_scores: bool = False, pair_support: bool = False):
     """reoa(fn_expr, fn_meta; kwargs...) -- src/RankCompV3.jl:536-555.  `expr_threshold` is accepted and
     unused, as in the reference (:539).  Extra keywords: `seed` (the reference's RNG is unseeded),
     `device`, `testdata_dir` (where fn_expr.txt / fn_meta.txt of the reference's test/ directory live), `align_meta`
@@ -283,7 +283,10 @@ def reoa(fn_expr: str = "fn_expr.txt", fn_meta: str = "fn_meta.txt", *, expr_thr
     selection as in run_identify_degs, e.g. "reversed": additionally writes `<stem>_<fg_name>_pairs.tsv` per comparison, the partner genes
     of every DEG among the comparison's final reference set; the reference has no such file), `sample_scores` (True: additionally
     writes `<stem>_<fg_name>_sample_scores.tsv` per comparison, one row per DEG and one column per sample: in how many more of the DEG's
-    reversed pairs the sample shows the non-control order than the control's -- SampleScores.net)."""
+    reversed pairs the sample shows the non-control order than the control's -- SampleScores.net), `pair_support` (True, which needs
+    `pairs`: additionally writes `<stem>_<fg_name>_pair_support.tsv` per comparison, one line per listed pair: gene, partner, class, and
+    per group level in how many of its samples the DEG lies above the partner, `<level>_gt`, and level with it, `<level>_eq`)."""
+    need_pairs_for_support(pairs, pair_support)
     work_dir = os.path.abspath(work_dir)
     if use_testdata == "yes":  # :559-562
         d = testdata_dir or os.environ.get("REO_TESTDATA_DIR") or os.path.join(
@@ -302,7 +305,7 @@ def reoa(fn_expr: str = "fn_expr.txt", fn_meta: str = "fn_meta.txt", *, expr_thr
                    ref_gene_max=ref_gene_max, ref_gene_min=ref_gene_min, seed=seed, sums=gpu_sums, align_meta=align_meta)
     run = run_identify_degs(prep["data"], prep["sample_groups"], prep["gene_names"], pval_reo, pval_deg, padj_deg,
                             prep["ref"], n_iter, n_conv, seed=seed, device=device, pairs=pairs,
-                            sample_scores=sample_scores)  # :652-662
+                            sample_scores=sample_scores, pair_support=pair_support)  # :652-662
     for p, (d, n) in enumerate(run.trace):
         log.info("INFO: iteration %d,  # DEGs %d, # non-DEGs %d", p, d, n)  # :418
     df = write_outputs(stem, prep, run, work_dir)
@@ -312,6 +315,8 @@ def reoa(fn_expr: str = "fn_expr.txt", fn_meta: str = "fn_meta.txt", *, expr_thr
             fg = "_".join([g_name[0], g_name[1]]) if len(g_name) == 2 else g_name[cm["k"]]   # (write_outputs' fg_name)
             if pairs is not None:
                 write_pairs_tsv(os.path.join(work_dir, f"{stem}_{fg}_pairs.tsv"), prep["gene_names"], cm["pairs"])
+            if pair_support:
+                write_pair_support_tsv(os.path.join(work_dir, f"{stem}_{fg}_pair_support.tsv"), prep["gene_names"], run.levels, cm["pair_support"])
             if sample_scores:
                 write_sample_scores_tsv(os.path.join(work_dir, f"{stem}_{fg}_sample_scores.tsv"), prep["gene_names"], prep["sample_names"],
                                         cm["sample_scores"])
