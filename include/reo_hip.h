@@ -237,6 +237,27 @@ int32_t reo_threshold(int32_t sample_size, double pval_reo);
  * that waits (REO_EHIP).  With shards (several GPUs, hooks) the call returns after the exchange has finished. */
 int32_t reo_build_pairs(reo_ctx *ctx, int32_t k);
 
+/* Pairwise contrast: the class table of "group ctrl (c-side) against group treat (t-side)"; samples of every other group take no part.
+ * With more than two groups reo_build_pairs answers "group k against every other sample"; a design with a control and several treatments
+ * asks for treatment against control and treatment against treatment, and this call answers those from what the one-vs-rest comparisons
+ * already keep: the per-group counts nre_g(i, j) of every ordered pair (reo_get_info 12, 13), tie coins included.  Nothing is counted again
+ * -- the first build of a context counts every group once, whichever call it is, and each contrast is one table-sized classification.
+ * For the unordered pair i < j and group g: nre_g = n_gt_g(i, j) + tie_wins(seed, i, j, g, n_eq_g(i, j)), the coin keyed by the group's own
+ * id in reo_set_groups order (not by its side); ic = nre_ctrl >= m1 ? 3 : (S_ctrl - nre_ctrl >= m1 ? 1 : 2), `it` likewise from nre_treat,
+ * S_treat, m2; the code is 3 (ic - 1) + (it - 1) and the ordered pair (j, i) gets 8 - code.  m1 = thr[0, ctrl] and m2 = thr[0, treat]: row 0
+ * of reo_get_thresholds, each group's own size (row 1 is not used; values from reo_set_thresholds are read from the same places).  On
+ * tie-free data the table equals, code for code, the reo_build_pairs table of a context that holds only the two groups' columns with ctrl
+ * as its control; with ties that holds when the two group ids are 0 and 1 (the coin keys then coincide).
+ * Everything behind the table -- reo_tally, reo_identify_degs, reo_get_ref_mask, reo_pair_list, reo_sample_counts, reo_pair_support -- works
+ * on it as on any other; reo_get_info 29 reports the treat group.  Two groups: (0, 1) is reo_build_pairs(ctx, 0) and (1, 0) is
+ * reo_build_pairs(ctx, 1).  Sharded contexts (reo_set_shard with a communicator or a hook) classify their own units and exchange as
+ * reo_build_pairs does.  Returns and waits as reo_build_pairs.
+ * Refused with REO_EINVAL, before anything of the context is touched (the resident table and the reference mask survive): a null context;
+ * ctrl or treat outside [0, ngroups); ctrl == treat; thresholds not set; a reo_create_multi context; and, with more than two groups, no
+ * shared count planes -- more than 65535 samples, REO_SHARE_GROUP_COUNTS=0 in the environment, or planes that do not fit the free device
+ * memory (the message gives the bytes needed).  There is no fallback that recounts. */
+int32_t reo_build_pairs_contrast(reo_ctx *ctx, int32_t ctrl, int32_t treat);
+
 /* Parity hook: deterministic per-pair per-group counts for the ordered pairs
  * (i, j), i in [i0,i1), j in [j0,j1): n_gt = #samples with x_i > x_j and not
  * tied, n_eq = #tied samples (|x_i - x_j| < 0.1, src/RankCompV3.jl:72), each
@@ -524,7 +545,8 @@ int32_t reo_get_timings(reo_ctx *ctx, double *ms, int32_t n);
  * was made dense from CSC arrays on the device (reo_set_matrix_csc_dev_*: 1, and 23 then reports its nnz; every other reo_set_matrix_*: 0), 28 how that build put the table's columns back
  * into gene order (0: no slot build; 8 or 4: a word at a time, 8 or 4 table rows per 32- or 16-bit entry -- the default, by the LDS the
  * gene count needs; 1: a bit at a time, REO_K1_UNSLOT=0 in the environment; REO_K1_UNSLOT=8 or 4 asks for that word form wherever its
- * LDS fits; the table is the same bit for bit under all of them). */
+ * LDS fits; the table is the same bit for bit under all of them), 29 the treat group of the resident class table (reo_build_pairs_contrast;
+ * -1: every other sample, reo_build_pairs with more than two groups, and -1 while there is no table). */
 int32_t reo_get_info(reo_ctx *ctx, int64_t *info, int32_t n);
 
 #ifdef __cplusplus

@@ -28,7 +28,7 @@ SYMBOLS = [
     "reo_set_matrix_rm_f64", "reo_set_matrix_rm_i64", "reo_set_matrix_rm_f32", "reo_set_matrix_rm_i32",
     "reo_set_matrix_csc_f64", "reo_set_matrix_csc_i64", "reo_set_matrix_csc_f32", "reo_set_matrix_csc_i32",
     "reo_set_groups", "reo_compute_thresholds", "reo_set_thresholds", "reo_get_thresholds", "reo_threshold",
-    "reo_build_pairs", "reo_pair_counts", "reo_get_codes", "reo_tally", "reo_identify_degs", "reo_mccullagh",
+    "reo_build_pairs", "reo_build_pairs_contrast", "reo_pair_counts", "reo_get_codes", "reo_tally", "reo_identify_degs", "reo_mccullagh",
     "reo_set_profiling", "reo_reset_timings", "reo_get_timings", "reo_get_info",
     "reo_pseudobulk_dense_f64", "reo_pseudobulk_dense_i64", "reo_pseudobulk_csc_f64", "reo_pseudobulk_csc_i64",
     "reo_set_matrix_pseudobulk_dense_f64", "reo_set_matrix_pseudobulk_dense_i64", "reo_set_matrix_pseudobulk_csc_f64", "reo_set_matrix_pseudobulk_csc_i64",
@@ -116,6 +116,7 @@ def lib() -> ctypes.CDLL:
         "reo_get_thresholds": (i32, [vp, vp]),
         "reo_threshold": (i32, [i32, f64]),
         "reo_build_pairs": (i32, [vp, i32]),
+        "reo_build_pairs_contrast": (i32, [vp, i32, i32]),
         "reo_pair_counts": (i32, [vp, i64, i64, i64, i64, vp, vp]),
         "reo_get_codes": (i32, [vp, i64, i64, i64, i64, vp]),
         "reo_tally": (i32, [vp, vp, vp]),
@@ -367,13 +368,19 @@ class PairSupport(NamedTuple):
         """n_gt / group size, float64, entries x ngroups."""
         return self.n_gt.astype(np.float64) / np.asarray(self.group_sizes, dtype=np.float64)[None, :]
 
-    def delta(self, k: int = 0) -> np.ndarray:
+    def delta(self, k: int = 0, other=None) -> np.ndarray:
         """Per entry: the fraction of group k's samples with the gene above its partner minus that fraction over all other samples -- the
-        two sides that reo_build_pairs(k) compares.  float64."""
+        two sides that reo_build_pairs(k) compares.  With `other` (a group id): minus that fraction in group `other` alone -- the two sides
+        that reo_build_pairs_contrast(k, other) compares.  float64."""
         sizes = np.asarray(self.group_sizes, dtype=np.int64)
         if not 0 <= int(k) < sizes.size:
             raise DimensionMismatch(REO_EINVAL, f"delta: group {k} is outside [0, {sizes.size})")
         k = int(k)
+        if other is not None:
+            if not 0 <= int(other) < sizes.size or int(other) == k:
+                raise DimensionMismatch(REO_EINVAL, f"delta: other = {other} must be a group in [0, {sizes.size}) different from k = {k}")
+            o = int(other)
+            return self.n_gt[:, k].astype(np.float64) / float(sizes[k]) - self.n_gt[:, o].astype(np.float64) / float(sizes[o])
         rest = self.n_gt.sum(axis=1, dtype=np.int64) - self.n_gt[:, k]
         return self.n_gt[:, k].astype(np.float64) / float(sizes[k]) - rest.astype(np.float64) / float(sizes.sum() - sizes[k])
 
@@ -630,6 +637,12 @@ class Context:
     def build_pairs(self, k: int = 0) -> None:
         check(self._L.reo_build_pairs(self._h, int(k)))
 
+    def build_contrast(self, ctrl: int, treat: int) -> None:
+        """reo_build_pairs_contrast: the class table of group `ctrl` (c-side) against group `treat` (t-side), classified from the per-group
+        counts that the one-vs-rest comparisons of more than two groups share; samples of other groups take no part.  Two groups: (0, 1) is
+        build_pairs(0), (1, 0) is build_pairs(1).  info()["contrast_treat"] reports `treat` afterwards."""
+        check(self._L.reo_build_pairs_contrast(self._h, int(ctrl), int(treat)))
+
     def pair_counts(self, i0: int, i1: int, j0: int, j1: int):
         shape = (i1 - i0, j1 - j0, self.ngroups)
         gt = np.zeros(shape, dtype=np.uint16)
@@ -862,8 +875,8 @@ class Context:
                 "k2_full_launches": int(ms[9]), "k2_delta_ms": ms[10], "set_matrix_host_wall_ms": ms[11]}
 
     def info(self) -> dict:
-        w = np.zeros(29, dtype=np.int64)
-        check(self._L.reo_get_info(self._h, _ptr(w), 29))
+        w = np.zeros(30, dtype=np.int64)
+        check(self._L.reo_get_info(self._h, _ptr(w), 30))
         v = np.zeros(28, dtype=np.int64)   # fields 0-27 keep their places (tests/test_csc_device_cpu.py reads this line); 28 is appended
         v[:] = w[:28]
         return {"G": int(v[0]), "S": int(v[1]), "Gp": int(v[2]), "table_bytes": int(v[3]), "has_ties": int(v[4]),
@@ -874,4 +887,4 @@ class Context:
                 "eager_range_launches": int(v[20]), "rowmajor_upload": int(v[21]),
                 "csc_upload": int(v[22]), "csc_nnz": int(v[23]), "resident_dtype": int(v[24]),
                 "k1_slot_order": int(v[25]), "k1_half_tiles_separated": int(v[26]), "csc_device": int(v[27]),
-                "k1_unslot_form": int(w[28])}
+                "k1_unslot_form": int(w[28]), "contrast_treat": int(w[29])}

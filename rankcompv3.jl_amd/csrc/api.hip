@@ -17,6 +17,7 @@
 #include "reo_internal.h"
 #include "sample_counts.h"
 #include "pair_support.h"
+#include "contrast.h"
 #include "upload_csc.h"
 
 #include <mutex>
@@ -362,6 +363,7 @@ static void invalidate(reo_ctx *c)
                      "the class table it ran on is gone");
     c->transformed = false;
     c->built_k = -1;
+    c->built_treat = -1;
     c->gc_valid = false;
     c->eager_k1 = false;
     // no class table any more: nothing is left of a build in slot order either (reo_get_info 25, 26 read 0; the maps and the item list that
@@ -595,7 +597,7 @@ using namespace reo;
 
 extern "C" {
 
-int32_t reo_version(void) { return 800; }
+int32_t reo_version(void) { return 900; }
 
 int32_t reo_trim_memory(void)
 {
@@ -1063,7 +1065,7 @@ int32_t reo_get_thresholds(reo_ctx *c, int32_t *m)
 }
 
 // transform + this context's share of the pair tiles; no exchange
-static int32_t enqueue_local(reo_ctx *c, int32_t k)
+static int32_t enqueue_local(reo_ctx *c, int32_t k, int32_t treat = -1)
 {
     int32_t rc = use(c);
     if (rc) return rc;
@@ -1072,27 +1074,32 @@ static int32_t enqueue_local(reo_ctx *c, int32_t k)
     if (k < 0 || k >= c->ngroups) { set_error("comparison %d outside [0,%d)", k, c->ngroups); return REO_EINVAL; }
     if ((rc = c->table.ensure(static_cast<size_t>(c->G) * kPlanes * c->Wp))) return rc;
     c->built_k = -1;
-    return launch_k1(c, k);
+    c->built_treat = -1;
+    return launch_k1(c, k, 3, false, nullptr, nullptr, false, treat);
 }
 
 // ... finished on return (shards: the pack and the exchange follow)
-static int32_t build_local(reo_ctx *c, int32_t k)
+static int32_t build_local_of(reo_ctx *c, int32_t k, int32_t treat)
 {
-    const int32_t rc = enqueue_local(c, k);
+    const int32_t rc = enqueue_local(c, k, treat);
     if (rc) return rc;
     REO_HIP_CHECK(stream_wait(c));
     return REO_OK;
 }
 
-int32_t reo_build_pairs(reo_ctx *c, int32_t k)
+static int32_t build_local(reo_ctx *c, int32_t k) { return build_local_of(c, k, -1); }
+
+// reo_build_pairs (treat < 0: comparison k against every other sample) and, behind its checks, reo_build_pairs_contrast (group k against
+// group treat; more than two groups, never a reo_create_multi context).  why: what reo_get_ref_mask answers from now on.
+static int32_t build_pairs(reo_ctx *c, int32_t k, int32_t treat, const char *why)
 {
     int32_t rc;
-    if (c) drop_ref_mask(c, "reo_build_pairs has replaced the class table that the last reo_identify_degs ran on: no reo_identify_degs has run on the current one");
+    if (c) drop_ref_mask(c, why);
     if (c && !c->peers.empty()) {
         if ((rc = multi_build_pairs(c, k, build_local))) return rc;
     } else {
         if (c && c->comm_dead && c->world > 1) { set_error("the communicator of this context was aborted after an earlier failure: attach a new one (reo_comm_init_rank)"); return REO_ECOMM; }
-        if (c && c->eager_k1 && k == 0 && c->built_k == 0 && c->transformed && !c->comm && c->world <= 1 && !c->ag && !c->ar) {
+        if (c && c->eager_k1 && treat < 0 && k == 0 && c->built_k == 0 && c->transformed && !c->comm && c->world <= 1 && !c->ag && !c->ar) {
             // reo_set_matrix (host matrix, groups and thresholds known) has launched this comparison's pair kernel already
             c->eager_k1 = false;   // (once: a second reo_build_pairs rebuilds, as it always did)
             c->t_ms[5] += 1.0;
@@ -1103,15 +1110,16 @@ int32_t reo_build_pairs(reo_ctx *c, int32_t k)
             // reo_identify_degs queues its first passes behind it without a host round trip in between; an asynchronous
             // failure of the kernel surfaces at the next wait (REO_EHIP); the stage timers are collected by the next call
             // that reads them.
-            if ((rc = enqueue_local(c, k))) return rc;
+            if ((rc = enqueue_local(c, k, treat))) return rc;
             c->table_complete = true;
             c->t_ms[5] += 1.0;
             c->built_k = k;
+            c->built_treat = treat;
             return REO_OK;
         }
         // a rank that fails here must not leave its peers waiting inside the collective: it aborts its communicator
         // (a failing caller-supplied hook has to do the same with its own)
-        if ((rc = build_local(c, k))) { if (c && c->comm && c->world > 1) comm_abort(c); return rc; }
+        if ((rc = build_local_of(c, k, treat))) { if (c && c->comm && c->world > 1) comm_abort(c); return rc; }
         if ((rc = exchange_table(c))) { if (c->comm) comm_abort(c); return rc; }
         if ((rc = comm_wait(c))) return rc;
         if (c->table_complete && (c->ag || c->ar) && c->check_hook_table) {
@@ -1129,7 +1137,36 @@ int32_t reo_build_pairs(reo_ctx *c, int32_t k)
     c->t_ms[5] += 1.0;
     collect_timings(c);
     c->built_k = k;
+    c->built_treat = treat;
     return REO_OK;
+}
+
+int32_t reo_build_pairs(reo_ctx *c, int32_t k)
+{
+    return build_pairs(c, k, -1, "reo_build_pairs has replaced the class table that the last reo_identify_degs ran on: no reo_identify_degs has run on the current one");
+}
+
+int32_t reo_build_pairs_contrast(reo_ctx *c, int32_t ctrl, int32_t treat)
+{
+    // every refusal first, from what the context already knows: a refused call leaves the table and the reference mask as they were
+    char msg[320];
+    ContrastState st{};
+    if (c) {
+        st.ngroups = c->ngroups; st.thr_set = c->thr_set; st.multi_device = c->in_multi || !c->peers.empty();
+        st.S = c->S; st.share_counts = c->share_counts != 0; st.planes_fit = true; st.planes_bytes = 0;
+        // the planes' size follows from the padded gene count, which the matrix sets (no matrix yet: the build itself refuses, as reo_build_pairs does)
+        if (c->ngroups > 2 && ctrl >= 0 && ctrl < c->ngroups && treat >= 0 && treat < c->ngroups && ctrl != treat && c->thr_set && !st.multi_device &&
+            c->S <= 65535 && st.share_counts && c->dtype != 0) {
+            int32_t rc = use(c);
+            size_t need = 0;
+            if (rc || (rc = k1_planes_fit(c, &st.planes_fit, &need))) return rc;
+            st.planes_bytes = static_cast<int64_t>(need);
+        }
+    }
+    if (contrast_check_args(c != nullptr, st, ctrl, treat, msg, sizeof msg)) { set_error("%s", msg); return REO_EINVAL; }
+    // two groups: the other group IS every other sample
+    if (c->ngroups == 2) return reo_build_pairs(c, ctrl);
+    return build_pairs(c, ctrl, treat, "reo_build_pairs_contrast has replaced the class table that the last reo_identify_degs ran on: no reo_identify_degs has run on the current one");
 }
 
 int32_t reo_pair_counts(reo_ctx *c, int64_t i0, int64_t i1, int64_t j0, int64_t j1, uint16_t *n_gt, uint16_t *n_eq)
@@ -1663,14 +1700,14 @@ int32_t reo_get_info(reo_ctx *c, int64_t *info, int32_t n)
         int32_t rc = use(c);
         if (rc || (rc = launch_slot_separated(c, &separated))) return rc;
     }
-    const int64_t v[29] = {c->G, c->S, c->Gp, static_cast<int64_t>(c->table.n * sizeof(uint32_t)), c->has_ties,
+    const int64_t v[30] = {c->G, c->S, c->Gp, static_cast<int64_t>(c->table.n * sizeof(uint32_t)), c->has_ties,
                            c->tiles_owned, c->tiles_total, kTileI, c->k1_cj, c->k1_q, kUnitH,
                            c->goff32.empty() ? 0 : c->goff32.back(), c->last_k1_shared,
                            static_cast<int64_t>(c->gcounts.n * sizeof(uint16_t)), c->transform_in_lds, c->xcc_local,
                            c->it_cycle_period, c->it_cycle_at, c->it_cycle_skipped, c->narrowed_bytes, c->eager_range_launches, c->rowmajor_upload,
                            c->csc_upload, c->csc_nnz, c->dtype, c->last_k1_slots, separated, c->csc_device,
-                           c->last_k1_slots ? c->last_k1_unslot : 0};
-    for (int i = 0; i < n && i < 29; ++i) info[i] = v[i];
+                           c->last_k1_slots ? c->last_k1_unslot : 0, c->built_k >= 0 ? c->built_treat : -1};
+    for (int i = 0; i < n && i < 30; ++i) info[i] = v[i];
     return REO_OK;
 }
 

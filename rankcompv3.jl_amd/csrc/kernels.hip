@@ -48,6 +48,7 @@
 #include "k1_items.h"
 #include "k1_slots.h"
 #include "k1_queue.h"
+#include "contrast.h"
 
 namespace reo {
 
@@ -1183,6 +1184,41 @@ __global__ __launch_bounds__(256) void k1_classify(K1Args a, const uint16_t *__r
     auto nk_of = [&](int r, int ii) -> int { return static_cast<int>(unpack16(wk[r], ii)); };
     auto nt_of = [&](int r, int ii) -> int { return static_cast<int>(unpack16(wt[r], ii)) - nk_of(r, ii); };
     emit_side<RI, RJ>(a, i0, jl, i0 >> 6, lane, 0, a.m1, a.nc - a.m1, nk_of);
+    emit_side<RI, RJ>(a, i0, jl, i0 >> 6, lane, 2, a.m2, a.nt - a.m2, nt_of);
+}
+
+// Classify the CONTRAST of group a.gc (c-side) against group a.gt (t-side) from the stored counts (reo_build_pairs_contrast; contrast.h):
+// k1_classify with plane a.gt in the place of "the sum minus plane k".  The counts are the ones one-vs-rest stores, tie coins included (keyed
+// by the group's own id, not by the side); a.nc, a.nt are the two groups' sizes and a.m1, a.m2 their own thresholds.  The sum plane is not
+// read; samples of other groups take no part.  HBM-bound like k1_classify: 2 x 64 B read per (tile, gene j).
+template <int RJ>
+__global__ __launch_bounds__(256) void k1_classify_contrast(K1Args a, const uint16_t *__restrict__ planes, size_t plane_elems)
+{
+    constexpr int RI = kTileI;
+    int i0, jl;
+    if (!tile_of_block<RI, RJ>(a, i0, jl)) return;
+    const int lane = threadIdx.x & 63;
+    const int it = i0 / RI;
+    const uint16_t *pc = planes + static_cast<size_t>(a.gc) * plane_elems;
+    const uint16_t *pt = planes + static_cast<size_t>(a.gt) * plane_elems;
+    uint32_t wc[RJ][RI / 2], wt[RJ][RI / 2];  // two u16 counts per register
+#pragma unroll
+    for (int r = 0; r < RJ; ++r) {
+        const int j = jl + 64 * r;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            uint4 vc = {0, 0, 0, 0}, vt = {0, 0, 0, 0};
+            if (j < a.Gp) {
+                vc = *reinterpret_cast<const uint4 *>(pc + gc_index(it, q, j, a.Gp));
+                vt = *reinterpret_cast<const uint4 *>(pt + gc_index(it, q, j, a.Gp));
+            }
+            wc[r][4 * q] = vc.x; wc[r][4 * q + 1] = vc.y; wc[r][4 * q + 2] = vc.z; wc[r][4 * q + 3] = vc.w;
+            wt[r][4 * q] = vt.x; wt[r][4 * q + 1] = vt.y; wt[r][4 * q + 2] = vt.z; wt[r][4 * q + 3] = vt.w;
+        }
+    }
+    auto nc_of = [&](int r, int ii) -> int { return static_cast<int>(unpack16(wc[r], ii)); };
+    auto nt_of = [&](int r, int ii) -> int { return static_cast<int>(unpack16(wt[r], ii)); };
+    emit_side<RI, RJ>(a, i0, jl, i0 >> 6, lane, 0, a.m1, a.nc - a.m1, nc_of);
     emit_side<RI, RJ>(a, i0, jl, i0 >> 6, lane, 2, a.m2, a.nt - a.m2, nt_of);
 }
 
@@ -3945,12 +3981,27 @@ int plane_bits(int64_t G) { return G <= 4095 ? 12 : (G <= 32767 ? 15 : (G <= 655
 struct K1Plan {
     bool multi, wide, big, wave, shared, wcounts, wmulti;   // the form (k1_plan says what each means)
     bool slots = false;     // the tie-free wave form in slot order (launch_k1 decides: k1_slots_wanted)
+    bool contrast = false;  // group against group from the shared counts (launch_k1, treat >= 0): k1_classify_contrast
     int RJ, CJ, Q, NP;      // genes j per lane, per j-chunk; j-chunks per panel; panels
     unsigned grid;          // workgroups of the workgroup forms
     size_t plane_elems;     // elements of one group's count plane (shared counts)
     std::vector<uint32_t> units, units_all;   // panel << 16 | i-range: this shard's, and every unit of the build (owner = index % world)
     int64_t tiles_owned, tiles_total;
 };
+
+int32_t k1_planes_fit(reo_ctx *c, bool *fit, size_t *need_bytes)
+{
+    const size_t Gp = static_cast<size_t>((c->G + kGenePad - 1) / kGenePad) * kGenePad;   // (c->Gp, once the transform has run)
+    const size_t need = Gp * Gp * (c->ngroups + 1) * sizeof(uint16_t);
+    const size_t have = c->gcounts.n * sizeof(uint16_t);
+    *need_bytes = need;
+    *fit = true;
+    if (c->gc_valid) return REO_OK;
+    size_t free_b = 0, total_b = 0;
+    REO_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+    if (need > have && need - have + (size_t(4) << 30) > free_b) *fit = false;  // keep 4 GiB for everything else
+    return REO_OK;
+}
 
 // The plan of a launch.  Refuses what no kernel can do; decides -- by the free device
 // memory, when the planes are not there yet -- whether the groups' counts are shared, and allocates them.
@@ -3970,12 +4021,13 @@ static int32_t k1_plan(reo_ctx *c, int sides, K1Plan &pl)
     const size_t plane_elems = static_cast<size_t>(c->Gp) * c->Gp;
     bool shared = multi && c->share_counts && !wide;
     if (shared && !c->gc_valid) {
-        size_t free_b = 0, total_b = 0;
-        REO_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-        const size_t need = plane_elems * (c->ngroups + 1) * sizeof(uint16_t);
-        const size_t have = c->gcounts.n * sizeof(uint16_t);
-        if (need > have && need - have + (size_t(4) << 30) > free_b) shared = false;  // keep 4 GiB for everything else
+        size_t need = 0;
+        if ((rc = k1_planes_fit(c, &shared, &need))) return rc;
         if (shared && (rc = c->gcounts.ensure(plane_elems * (c->ngroups + 1)))) return rc;
+    }
+    if (pl.contrast && !shared) {   // (reo_build_pairs_contrast has looked before it touched anything: only a change of the free memory since then ends here)
+        set_error("reo_build_pairs_contrast: no shared per-group counts (more than 65535 samples, REO_SHARE_GROUP_COUNTS=0, or the planes do not fit)");
+        return REO_EINVAL;
     }
     const bool wcounts = shared && (c->k1_wave || big);  // the per-group counts by the wave form's loop (k1w_group_counts): kRJ genes per lane too
     const bool wmulti = multi && !shared && !wide && big;  // a comparison recounted by the wave form (k1w_pairs_multi): above 65 535 genes only --
@@ -4046,7 +4098,10 @@ static void launch_pairs(reo_ctx *c, const K1Args &a, const K1Plan &pl)
                 by_ties([&](auto t) { k1_group_counts<NB, decltype(t)::value><<<grid, 256, 0, c->stream>>>(a, c->gcounts.p, plane_elems); });
             c->gc_valid = true;
         }
-        if (c->has_ties && !wv) k1_classify<kRJTies><<<grid, 256, 0, c->stream>>>(a, c->gcounts.p, plane_elems);
+        if (pl.contrast) {  // group a.gc against group a.gt: two planes, the sum plane is not read
+            if (c->has_ties && !wv) k1_classify_contrast<kRJTies><<<grid, 256, 0, c->stream>>>(a, c->gcounts.p, plane_elems);
+            else k1_classify_contrast<kRJ><<<grid, 256, 0, c->stream>>>(a, c->gcounts.p, plane_elems);
+        } else if (c->has_ties && !wv) k1_classify<kRJTies><<<grid, 256, 0, c->stream>>>(a, c->gcounts.p, plane_elems);
         else k1_classify<kRJ><<<grid, 256, 0, c->stream>>>(a, c->gcounts.p, plane_elems);
     } else if (pl.multi) {
         if constexpr (kWg) by_ties([&](auto t) { k1_pairs<NB, decltype(t)::value, true><<<grid, 256, 0, c->stream>>>(a); });
@@ -4444,11 +4499,19 @@ int32_t launch_slot_separated(reo_ctx *c, int64_t *half_tiles)
 // sides (wave form, two groups): which sides' items are launched -- bit 0 the comparison's own group, bit 1 the rest; 3 = the whole
 // table.  keep_table: the class table has been cleared by the caller and holds other sides' planes already (the pipelined upload,
 // transform.hip eager_upload, launches a side as soon as its group's samples are ranked).
-int32_t launch_k1(reo_ctx *c, int k, int sides, bool keep_table, const int32_t *gate, const K1Range *range, bool prepare)
+int32_t launch_k1(reo_ctx *c, int k, int sides, bool keep_table, const int32_t *gate, const K1Range *range, bool prepare, int treat)
 {
     K1Args a = k1_args(c, k);
     K1Plan pl;
     int32_t rc;
+    if (treat >= 0) {   // a contrast: the c-side is group k, the t-side group `treat` alone (contrast.h)
+        if (sides != 3 || keep_table || gate || range || prepare || c->ngroups <= 2) { set_error("a contrast of two groups: more than two groups, the whole table"); return REO_EINVAL; }
+        const ContrastSides cs = contrast_sides(c->goff.data(), c->goff32.data(), c->thr.data(), k, treat);
+        a.cb = cs.cb; a.ce = cs.ce; a.tb = cs.tb; a.te = cs.te;
+        a.gc = k; a.gt = treat;
+        a.nc = cs.nc; a.nt = cs.nt; a.m1 = cs.m1; a.m2 = cs.m2;
+        pl.contrast = true;
+    }
     if ((rc = k1_plan(c, sides, pl))) return rc;
     const std::vector<uint32_t> &units = pl.units;
     c->units_all_host = pl.units_all;

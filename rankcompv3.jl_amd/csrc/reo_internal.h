@@ -244,6 +244,7 @@ struct reo_ctx {
     // class table: [G][4 planes][Wp] 32-bit words
     reo::DevBuf<uint32_t> table;
     int built_k = -1;
+    int built_treat = -1;               // reo_get_info 29: the treat group of the resident table (reo_build_pairs_contrast), -1: every other sample
     bool table_complete = false;        // world > 1: the shards' parts have been summed (api.hip, exchange_table)
     void *comm = nullptr;               // ncclComm_t of the in-library RCCL path (comm.hip), or null
     int spin_wait = 0;                  // REO_SPIN_WAIT=1: poll the stream on the hot path instead of the blocking wait (api.hip, stream_wait; measured: 0.04 ms per step)
@@ -386,8 +387,12 @@ void host_parallel(int nthreads, int ntasks, const std::function<void(int)> &fn)
 // buffer between the ranges of a side and the launch of the last range classifies (kernels.hip, K1Args::park).  prepare: only make
 // (and upload) the unit map and the item list of `sides` -- the pipelined upload does that before it queues any wait on the stream.
 struct K1Range { int b0, b1; bool first, last; };
+// treat: -1 = comparison k against every other sample; a group id = the contrast of group k against that group alone, classified from
+// the shared per-group count planes (more than two groups; contrast.h) -- whole table only.
 int32_t launch_k1(reo_ctx *c, int k, int sides = 3, bool keep_table = false, const int32_t *gate = nullptr, const K1Range *range = nullptr,
-                  bool prepare = false);  // sides: bit 0 = the comparison's own group, bit 1 = the rest (wave form; eager_upload)
+                  bool prepare = false, int treat = -1);  // sides: bit 0 = the comparison's own group, bit 1 = the rest (wave form; eager_upload)
+// whether the shared per-group count planes of the context's problem are resident or fit the free device memory, and their size
+int32_t k1_planes_fit(reo_ctx *c, bool *fit, size_t *need_bytes);
 int64_t exchange_unit_words(const reo_ctx *c);   // uint32 per packed work unit
 int32_t exchange_units_per_rank(const reo_ctx *c);
 int32_t launch_pack_units(reo_ctx *c, int m0 = 0, int mcnt = -1, uint32_t *send = nullptr, hipStream_t st = nullptr);    // this shard's units (all, or slots m0 .. m0 + mcnt - 1) -> c->xsend / send

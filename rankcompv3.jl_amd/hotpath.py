@@ -35,6 +35,56 @@ def encode_groups(group):
     return ids, levels
 
 
+def parse_contrasts(levels, contrasts) -> list:
+    """The contrasts of a run as (ctrl, treat) index pairs into `levels` (encode_groups' order).  "all": every unordered pair of levels, the
+    level that appears first as control, in level order.  Otherwise a sequence of (ctrl_level, treat_level) pairs, kept in the order given.
+    Raises DimensionMismatch -- before any context is opened -- for an unknown level, ctrl == treat, an empty list and the same ordered
+    contrast twice."""
+    n = len(levels)
+    if isinstance(contrasts, str):
+        if contrasts != "all":
+            raise _ffi.DimensionMismatch(_ffi.REO_EINVAL, f"contrasts: {contrasts!r} is not \"all\" and not a sequence of (ctrl, treat) level pairs")
+        out = [(a, b) for a in range(n) for b in range(a + 1, n)]
+    else:
+        index = {lv: q for q, lv in enumerate(levels)}
+        out = []
+        for item in contrasts:
+            pair = tuple(item)
+            if len(pair) != 2:
+                raise _ffi.DimensionMismatch(_ffi.REO_EINVAL, f"contrasts: {item!r} is not a (ctrl, treat) pair of levels")
+            ids = []
+            for lv in pair:
+                key = lv.item() if isinstance(lv, np.generic) else lv
+                if key not in index:
+                    raise _ffi.DimensionMismatch(_ffi.REO_EINVAL, f"contrasts: unknown level {key!r} (the levels of 'group' are {list(levels)!r})")
+                ids.append(index[key])
+            if ids[0] == ids[1]:
+                raise _ffi.DimensionMismatch(_ffi.REO_EINVAL, f"contrasts: ctrl == treat == {pair[0]!r}, a contrast needs two different levels")
+            if (ids[0], ids[1]) in out:
+                raise _ffi.DimensionMismatch(_ffi.REO_EINVAL, f"contrasts: ({pair[0]!r}, {pair[1]!r}) is listed twice")
+            out.append((ids[0], ids[1]))
+    if not out:
+        raise _ffi.DimensionMismatch(_ffi.REO_EINVAL, "contrasts: the list is empty (None runs the comparisons of the reference)")
+    return out
+
+
+def comparison_plan(levels, contrasts) -> list:
+    """What a run builds, in order: (k, treat) per comparison -- treat None: comparison k of the reference (one for two groups, else one per
+    group against every other sample); with `contrasts`: parse_contrasts' pairs."""
+    if contrasts is None:
+        return [(k, None) for k in range(1 if len(levels) == 2 else len(levels))]
+    return parse_contrasts(levels, contrasts)
+
+
+def build_comparison(ctx, levels, k, treat) -> dict:
+    """Builds the class table of one entry of comparison_plan on `ctx` and starts its comparison dict."""
+    if treat is None:
+        ctx.build_pairs(k)
+        return {"k": k}
+    ctx.build_contrast(k, treat)
+    return {"k": k, "ctrl": levels[k], "treat": levels[treat]}
+
+
 def label_genes(result: np.ndarray, pval_deg: float, padj_deg: float) -> np.ndarray:
     """up / down / no change, src/RankCompV3.jl:426-429."""
     sig = (result[:, 0] <= pval_deg) & (result[:, 1] <= padj_deg)
@@ -55,7 +105,7 @@ class DegRun:
     trace: list = field(default_factory=list)   # (#DEG, #non-DEG) per pass (:418), first comparison
     timings: dict = field(default_factory=dict)
     info: dict = field(default_factory=dict)
-    comparisons: list = field(default_factory=list)  # per comparison: dict(k, result, labels, iters_run, trace)
+    comparisons: list = field(default_factory=list)  # per comparison: dict(k, result, labels, iters_run, trace); contrasts: ctrl, treat too
     gene_names: object = None
     _res: object = None
 
@@ -152,7 +202,7 @@ def write_pairs_tsv(path, gene_names, pair_list) -> None:
 
 def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref_gene, n_iter, n_conv, *,
                       seed: int = 0, device: int = -1, shard=(0, 1), allreduce=None, allgather=None, profile: bool = False,
-                      pairs=None, sample_scores: bool = False, pair_support: bool = False) -> DegRun:
+                      pairs=None, sample_scores: bool = False, pair_support: bool = False, contrasts=None) -> DegRun:
     """identify_degs with the extras (trace, timings) kept.  `data` is a host matrix (numpy, anything np.asarray takes) or a torch
     tensor on a ROCm device, which is used in place (_ffi.device_matrix).  A column-major host matrix is read in place; a row-major one
     (numpy's default C order, column slices of a wider C-ordered array) is copied column-major on the host first, or, with REO_ROWMAJOR=1
@@ -176,7 +226,12 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
     `pair_support` (not in the reference): True needs `pairs` (DimensionMismatch otherwise) and adds "pair_support" to every comparison
     dict, the PairSupport of that comparison's pair list (Context.pair_support: per listed pair and group, in how many samples the DEG lies
     above its partner, and in how many the two are tied), taken at the same moment as "pairs".  False (the default): no further call, no new
-    key."""
+    key.
+    `contrasts` (not in the reference): "all" or a sequence of (ctrl_level, treat_level) pairs (parse_contrasts).  One comparison per
+    contrast, in the order given, instead of the reference's: group ctrl against group treat ALONE (Context.build_contrast; with more than two
+    groups every contrast is classified from the per-group counts of the first build, nothing is counted again).  Each comparison dict
+    carries "ctrl" and "treat" (level names) besides today's keys, "k" is the control's index, and `res` has 1 + 16 len(contrasts) columns;
+    `pairs`, `sample_scores` and `pair_support` work per contrast.  None (the default): the reference's comparisons."""
     need_pairs_for_support(pairs, pair_support)
     # a torch tensor on a ROCm device: a strided one is used where it is, a sparse one is made dense there (its device is the context's)
     on_device = _ffi.is_device_sparse(data) or _ffi.is_device_tensor(data)
@@ -194,7 +249,7 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
         raise _ffi.DimensionMismatch(_ffi.REO_EINVAL, "Only 1 level in 'group1, at least 2 levels!")
     if len(gene_names) != r or len(ref_gene) != r:
         raise _ffi.DimensionMismatch(_ffi.REO_EINVAL, "gene_names / ref_gene length != number of rows of 'data'")
-    ncomp = 1 if len(levels) == 2 else len(levels)
+    plan = comparison_plan(levels, contrasts)
     comps = []
     with _ffi.Context(device=device, seed=seed) as ctx:
         ctx.set_profiling(profile)
@@ -212,11 +267,11 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
             ctx.set_matrix_tensor(data)   # (the context keeps the tensor alive until it is closed, behind the last build_pairs)
         else:
             ctx.set_matrix(data)
-        for k in range(ncomp):  # `for k=1:gnum ... if gnum==2 break` (:396,431-434)
-            ctx.build_pairs(k)
+        for k, treat in plan:  # `for k=1:gnum ... if gnum==2 break` (:396,431-434), or the contrasts
+            cm = build_comparison(ctx, levels, k, treat)
             result, iters, trace = ctx.identify_degs(np.asarray(ref_gene, dtype=bool), pval_deg, padj_deg, n_iter, n_conv)
-            comps.append({"k": k, "result": result, "labels": label_genes(result, pval_deg, padj_deg),
-                          "iters_run": iters, "trace": trace})
+            cm.update({"result": result, "labels": label_genes(result, pval_deg, padj_deg), "iters_run": iters, "trace": trace})
+            comps.append(cm)
             if pairs is not None:
                 comps[-1].update(deg_pairs(ctx, comps[-1]["labels"], pairs))
                 if pair_support:
@@ -261,7 +316,8 @@ class CellsDegRun(NamedTuple):
 
 def identify_degs_cells(cells, cell_group, gene_names, n_pseudo, pval_reo, pval_deg, padj_deg, ref_gene, n_iter, n_conv, *,
                         min_profiles: int = 0, min_features: int = 0, ref_gene_max: int = 3000, seed: int = 0, device: int = 0,
-                        profile: bool = False, pairs=None, sample_scores: bool = False, pair_support: bool = False) -> CellsDegRun:
+                        profile: bool = False, pairs=None, sample_scores: bool = False, pair_support: bool = False,
+                        contrasts=None) -> CellsDegRun:
     """Cells to DEGs without a host trip for the profiles: `cells` is a genes x cells matrix (scipy.sparse, anything np.asarray takes, or
     a torch tensor on a ROCm device -- sparse or strided -- which is read where it is: reo_set_matrix_pseudobulk_*_dev_*),
     cell_group one label per cell.  cells_partition -> the pseudo-bulk sums written into the context's matrix (set_matrix_pseudobulk) ->
@@ -270,7 +326,8 @@ def identify_degs_cells(cells, cell_group, gene_names, n_pseudo, pval_reo, pval_
     synth.ref_mask(G', min(G', ref_gene_max), seed), the draw reoa makes.  Bit-identical to Context.pseudobulk -> numpy filters ->
     run_identify_degs on the same seed.  (reoa() keeps its host route: its writers want the profile matrix on the host.)
     `pairs`, `sample_scores`, `pair_support`: as in run_identify_degs; gene indices are those of the KEPT genes (run.gene_names), columns
-    the kept profiles."""
+    the kept profiles.  `contrasts`: as in run_identify_degs, over the group levels of the cells (checked against the levels of cell_group
+    before any context is opened, and again against those of the kept profiles)."""
     need_pairs_for_support(pairs, pair_support)
     on_device = _ffi.is_device_sparse(cells) or _ffi.is_device_tensor(cells)
     if on_device:   # a torch tensor on a ROCm device, sparse or strided: summed where it is, on its own device
@@ -287,6 +344,8 @@ def identify_degs_cells(cells, cell_group, gene_names, n_pseudo, pval_reo, pval_
     if n_pseudo < 1:
         raise _ffi.DimensionMismatch(_ffi.REO_EINVAL, "n_pseudo must be at least 1")
     order, chunk_ptr, names, groups = cells_partition(cell_group, n_pseudo, seed)
+    if contrasts is not None:
+        parse_contrasts(encode_groups(groups)[1], contrasts)
     comps = []
     with _ffi.Context(device=device, seed=seed) as ctx:
         ctx.set_profiling(profile)
@@ -302,10 +361,11 @@ def identify_degs_cells(cells, cell_group, gene_names, n_pseudo, pval_reo, pval_
         ref = synth.ref_mask(G, min(G, ref_gene_max), seed) if ref_gene is None else np.asarray(ref_gene, dtype=bool)[gene_kept]
         ctx.set_groups(gid, len(levels))
         thr = ctx.compute_thresholds(pval_reo)
-        for k in range(1 if len(levels) == 2 else len(levels)):
-            ctx.build_pairs(k)
+        for k, treat in comparison_plan(levels, contrasts):
+            cm = build_comparison(ctx, levels, k, treat)
             result, iters, trace = ctx.identify_degs(ref, pval_deg, padj_deg, n_iter, n_conv)
-            comps.append({"k": k, "result": result, "labels": label_genes(result, pval_deg, padj_deg), "iters_run": iters, "trace": trace})
+            cm.update({"result": result, "labels": label_genes(result, pval_deg, padj_deg), "iters_run": iters, "trace": trace})
+            comps.append(cm)
             if pairs is not None:
                 comps[-1].update(deg_pairs(ctx, comps[-1]["labels"], pairs))
                 if pair_support:

@@ -239,13 +239,22 @@ def prepare(fn_expr: str, fn_meta: str, *, min_profiles: int = 0, min_features: 
             "g_name": g_name, "ref": ref, "meta": meta_out}
 
 
+def fg_name(g_name, cm) -> str:
+    """The `<fg_name>` of a comparison's files (:670): `<g1>_<g2>` for two groups, the group's name for one-vs-rest, and `<ctrl>_<treat>` -- the
+    two-group naming -- for a contrast (a comparison dict with "ctrl" and "treat", run_identify_degs(contrasts=...))."""
+    if "treat" in cm:
+        return f"{cm['ctrl']}_{cm['treat']}"
+    return "_".join([g_name[0], g_name[1]]) if len(g_name) == 2 else g_name[cm["k"]]
+
+
 def write_outputs(stem: str, prep: dict, run, work_dir: str = "."):
-    """The reference's result files (:663-683) minus the plots.  Returns the gene_up_down DataFrame (:682-684)."""
+    """The reference's result files (:663-683) minus the plots.  Returns the gene_up_down DataFrame (:682-684).  The comparisons of a run
+    with contrasts are named as the reference names two groups: `<stem>_<ctrl>_<treat>_result.tsv` (:670), column `<ctrl>_vs_<treat>` (:683)."""
     import pandas as pd
     g_name, genes = prep["g_name"], prep["gene_names"]
     mg = len(g_name)
     for cm in run.comparisons:  # :666-677
-        fg = "_".join([g_name[0], g_name[1]]) if mg == 2 else g_name[cm["k"]]
+        fg = fg_name(g_name, cm)
         path = os.path.join(work_dir, f"{stem}_{fg}_result.tsv")
         with open(path, "w") as f:
             f.write("\t".join(["genename"] + HEADER) + "\n")
@@ -263,6 +272,8 @@ def write_outputs(stem: str, prep: dict, run, work_dir: str = "."):
         meta_out = pd.DataFrame({"Name": prep["sample_names"], "Group": prep["sample_groups"]})
     meta_out.to_csv(os.path.join(work_dir, f"{stem}_df_meta.tsv"), sep="\t", index=False)  # :680, every meta column
     cols = [f"{g_name[0]}_vs_{g_name[1]}"] if mg == 2 else [f"{g}_vs_other" for g in g_name]  # :683
+    if any("treat" in cm for cm in run.comparisons):
+        cols = [f"{cm['ctrl']}_vs_{cm['treat']}" for cm in run.comparisons]
     df = pd.DataFrame({"gene_name": genes})
     for cname, cm in zip(cols, run.comparisons):
         df[cname] = cm["labels"]
@@ -275,7 +286,7 @@ def reoa(fn_expr: str = "fn_expr.txt", fn_meta: str = "fn_meta.txt", *, expr_thr
          n_pseudo: int = 0, use_hk_genes: str = "yes", hk_file: str | None = None, gene_name_type: str = "ENSEMBL",
          ref_gene_max: int = 3000, ref_gene_min: int = 100, n_iter: int = 128, n_conv: int = 5, work_dir: str = "./",
          use_testdata: str = "no", seed: int = 0, device: int = -1, testdata_dir: str | None = None, align_meta: bool | None = None,
-         pairs=None, sample_scores: bool = False, pair_support: bool = False):
+         pairs=None, sample_scores: bool = False, pair_support: bool = False, contrasts=None):
     """reoa(fn_expr, fn_meta; kwargs...) -- src/RankCompV3.jl:536-555.  `expr_threshold` is accepted and
     unused, as in the reference (:539).  Extra keywords: `seed` (the reference's RNG is unseeded),
     `device`, `testdata_dir` (where fn_expr.txt / fn_meta.txt of the reference's test/ directory live), `align_meta`
@@ -285,7 +296,10 @@ def reoa(fn_expr: str = "fn_expr.txt", fn_meta: str = "fn_meta.txt", *, expr_thr
     writes `<stem>_<fg_name>_sample_scores.tsv` per comparison, one row per DEG and one column per sample: in how many more of the DEG's
     reversed pairs the sample shows the non-control order than the control's -- SampleScores.net), `pair_support` (True, which needs
     `pairs`: additionally writes `<stem>_<fg_name>_pair_support.tsv` per comparison, one line per listed pair: gene, partner, class, and
-    per group level in how many of its samples the DEG lies above the partner, `<level>_gt`, and level with it, `<level>_eq`)."""
+    per group level in how many of its samples the DEG lies above the partner, `<level>_gt`, and level with it, `<level>_eq`), `contrasts`
+    ("all" or (ctrl_level, treat_level) pairs as in run_identify_degs: one comparison per contrast, group against group, instead of the
+    reference's; the files are `<stem>_<ctrl>_<treat>_result.tsv`, the gene_up_down columns `<ctrl>_vs_<treat>` -- the reference's two-group
+    naming -- and the optional files carry the same `<ctrl>_<treat>`)."""
     need_pairs_for_support(pairs, pair_support)
     work_dir = os.path.abspath(work_dir)
     if use_testdata == "yes":  # :559-562
@@ -305,20 +319,29 @@ def reoa(fn_expr: str = "fn_expr.txt", fn_meta: str = "fn_meta.txt", *, expr_thr
                    ref_gene_max=ref_gene_max, ref_gene_min=ref_gene_min, seed=seed, sums=gpu_sums, align_meta=align_meta)
     run = run_identify_degs(prep["data"], prep["sample_groups"], prep["gene_names"], pval_reo, pval_deg, padj_deg,
                             prep["ref"], n_iter, n_conv, seed=seed, device=device, pairs=pairs,
-                            sample_scores=sample_scores, pair_support=pair_support)  # :652-662
+                            sample_scores=sample_scores, pair_support=pair_support, contrasts=contrasts)  # :652-662
     for p, (d, n) in enumerate(run.trace):
         log.info("INFO: iteration %d,  # DEGs %d, # non-DEGs %d", p, d, n)  # :418
     df = write_outputs(stem, prep, run, work_dir)
-    if pairs is not None or sample_scores:
-        g_name = prep["g_name"]
-        for cm in run.comparisons:
-            fg = "_".join([g_name[0], g_name[1]]) if len(g_name) == 2 else g_name[cm["k"]]   # (write_outputs' fg_name)
-            if pairs is not None:
-                write_pairs_tsv(os.path.join(work_dir, f"{stem}_{fg}_pairs.tsv"), prep["gene_names"], cm["pairs"])
-            if pair_support:
-                write_pair_support_tsv(os.path.join(work_dir, f"{stem}_{fg}_pair_support.tsv"), prep["gene_names"], run.levels, cm["pair_support"])
-            if sample_scores:
-                write_sample_scores_tsv(os.path.join(work_dir, f"{stem}_{fg}_sample_scores.tsv"), prep["gene_names"], prep["sample_names"],
-                                        cm["sample_scores"])
+    write_extras(stem, prep, run, work_dir)
     df.attrs["run"] = run
     return df
+
+
+def write_extras(stem: str, prep: dict, run, work_dir: str = ".") -> list:
+    """The files beyond the reference's, one per comparison and kind that the run carries ("pairs", "pair_support", "sample_scores" in its
+    comparison dicts): `<stem>_<fg_name>_pairs.tsv`, `_pair_support.tsv`, `_sample_scores.tsv`, with write_outputs' fg_name.  Returns the
+    paths written."""
+    g_name, out = prep["g_name"], []
+    for cm in run.comparisons:
+        fg = fg_name(g_name, cm)
+        if "pairs" in cm:
+            out.append(os.path.join(work_dir, f"{stem}_{fg}_pairs.tsv"))
+            write_pairs_tsv(out[-1], prep["gene_names"], cm["pairs"])
+        if "pair_support" in cm:
+            out.append(os.path.join(work_dir, f"{stem}_{fg}_pair_support.tsv"))
+            write_pair_support_tsv(out[-1], prep["gene_names"], run.levels, cm["pair_support"])
+        if "sample_scores" in cm:
+            out.append(os.path.join(work_dir, f"{stem}_{fg}_sample_scores.tsv"))
+            write_sample_scores_tsv(out[-1], prep["gene_names"], prep["sample_names"], cm["sample_scores"])
+    return out
