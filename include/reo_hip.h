@@ -248,9 +248,9 @@ int32_t reo_build_pairs(reo_ctx *ctx, int32_t k);
  * of reo_get_thresholds, each group's own size (row 1 is not used; values from reo_set_thresholds are read from the same places).  On
  * tie-free data the table equals, code for code, the reo_build_pairs table of a context that holds only the two groups' columns with ctrl
  * as its control; with ties that holds when the two group ids are 0 and 1 (the coin keys then coincide).
- * Everything behind the table -- reo_tally, reo_identify_degs, reo_get_ref_mask, reo_pair_list, reo_sample_counts, reo_pair_support -- works
- * on it as on any other; reo_get_info 29 reports the treat group.  Two groups: (0, 1) is reo_build_pairs(ctx, 0) and (1, 0) is
- * reo_build_pairs(ctx, 1).  Sharded contexts (reo_set_shard with a communicator or a hook) classify their own units and exchange as
+ * Everything behind the table -- reo_tally, reo_identify_degs, reo_get_ref_mask, reo_pair_list, reo_sample_counts, reo_pair_support,
+ * reo_sample_tests (ctrl is its control group) -- works on it as on any other; reo_get_info 29 reports the treat group.  Two groups:
+ * (0, 1) is reo_build_pairs(ctx, 0) and (1, 0) is reo_build_pairs(ctx, 1).  Sharded contexts (reo_set_shard with a communicator or a hook) classify their own units and exchange as
  * reo_build_pairs does.  Returns and waits as reo_build_pairs.
  * Refused with REO_EINVAL, before anything of the context is touched (the resident table and the reference mask survive): a null context;
  * ctrl or treat outside [0, ngroups); ctrl == treat; thresholds not set; a reo_create_multi context; and, with more than two groups, no
@@ -387,6 +387,46 @@ int32_t reo_pair_support(reo_ctx *ctx, const int32_t *genes, int64_t n_genes,
                          const int64_t *rowptr /* n_genes + 1 */, const int32_t *partner /* rowptr[n_genes] */,
                          int32_t *n_gt, int32_t *n_eq /* entries x ngroups, row-major; n_eq may be NULL */,
                          uint8_t *outcome /* entries x S, row-major, caller's column order; may be NULL */);
+
+/* Sample tests: is gene i UP OR DOWN IN ONE SAMPLE?  The tallies call a gene over the groups; this call tests one sample's orderings of
+ * the gene against the pairs that are stable in the control group, with Fisher's exact test -- the individual-level question of the
+ * RankComp family.  The reference has no such output.
+ * For query q, gene i = genes[q] (any order, repeats allowed, each entry is its own row), the background is
+ *     J = {j != i : partner_mask[j] != 0, ic(i, j) in {1, 3}}
+ * where ic is the c-side class of the resident table (class code 3*(ic-1)+(it-1)); the c-side is group k of reo_build_pairs(k), or ctrl
+ * of reo_build_pairs_contrast(ctrl, treat).  partner_mask NULL = the mask of reo_get_ref_mask, read where it lies.  J splits into
+ *     A = {ic = 3} (class mask 0x1C0: i stably above j in the control group)   n_above_ctrl[q] = |A|
+ *     B = {ic = 1} (class mask 0x007)                                          n_below_ctrl[q] = |B|
+ * and for every sample s in the CALLER's column order -- every group's samples, the control's own included -- by the comparator of the
+ * resident matrix's element type as reo_sample_counts applies it (ties are reported as ties, no tie coin is drawn):
+ *     rev_up[q * S + s]   = #{j in B : x_i > x_j}          rev_down[q * S + s] = #{j in A : x_i < x_j}
+ *     tied[q * S + s]     = #{j in J : tied}               u = #{j in J : x_i > x_j}      d = |J| - u - tied
+ * Fisher's 2 x 2 table is [[n_above_ctrl, n_below_ctrl], [u, d]]; with N its total, K = n_above_ctrl + u, n = u + d and
+ * X ~ Hypergeometric(N, K, n):
+ *     p_up[q * S + s] = P(X >= u)          p_down[q * S + s] = P(X <= u)
+ * An empty J, or n = 0 (every pair tied), gives 1 and 1.  A two-sided value, min(1, 2 min(p_up, p_down)), and any correction for multiple
+ * testing are the caller's (the Python package forms both on the host).  Samples of the control group are tested against a background
+ * that they helped to define: their p-values are not those of an independent sample.
+ * rev_up, rev_down and tied may be NULL (they are then not stored); n_above_ctrl and n_below_ctrl may be NULL as well.
+ * Arithmetic (csrc/sample_tests.h, evaluated by the kernel and by a host driver alike): pmf(u) from a table of log k!, k = 0 .. 2 (G - 1)
+ * (a running sum of logl in long double, rounded once per entry, uploaded once per context and rebuilt when G changes); the tail that points
+ * away from the mode floor((n+1)(K+1)/(N+2)) is summed by the ratio recurrence, integer products formed exactly, until the support ends
+ * or a term falls below 2^-60 of the sum; the other tail is 1 - small + pmf(u); both are clamped to [0, 1].  Relative error against the
+ * exact tails: DESIGN.md section 7 (n9).  Tails below about 2^-1022 are subnormal or 0.
+ * Per batch of queries: two launches of the kernel of reo_sample_counts into device buffers that stay on the device, one launch of
+ * k_sample_fisher (csrc/sampletests.hip), one thread per (query, sample).  Batches are sized so that every device buffer stays under
+ * 32 MiB (at least one query per batch); REO_SAMPLE_TESTS_BATCH in the environment, read per call, lowers the batch to that many queries
+ * (tests of the batch seam).  Needs the class table and the transform; reads the reference mask and changes nothing: reo_get_ref_mask and
+ * a following reo_identify_degs behave as if the call had not happened.  Both plane layouts, every S.
+ * Host arrays only; no stage timer of its own.
+ * REO_EINVAL, each with its own message, decided before anything is uploaded, and a refused call writes nothing: a NULL genes, p_up or
+ * p_down; n_genes < 1 or above 2^30; a gene outside [0, G); no class table; a NULL partner_mask while reo_get_ref_mask would refuse (its
+ * reason is passed on); a reo_create_multi context.  An incomplete sharded table: REO_ECOMM, as reo_tally. */
+int32_t reo_sample_tests(reo_ctx *ctx, const int32_t *genes, int64_t n_genes,
+                         const uint8_t *partner_mask /* G bytes; NULL = the mask of reo_get_ref_mask */,
+                         int32_t *n_above_ctrl, int32_t *n_below_ctrl /* n_genes; may be NULL */,
+                         int32_t *rev_up, int32_t *rev_down, int32_t *tied /* n_genes x S row-major, ld = S; may be NULL */,
+                         double *p_up, double *p_down /* n_genes x S row-major, ld = S */);
 
 /* McCullagh test on 3x3 tables given as 9 tallies each (n x 9 row-major),
  * evaluated by the device routine the iteration uses; out is n x 5 row-major

@@ -33,6 +33,7 @@ SYMBOLS = [
     "reo_pseudobulk_dense_f64", "reo_pseudobulk_dense_i64", "reo_pseudobulk_csc_f64", "reo_pseudobulk_csc_i64",
     "reo_set_matrix_pseudobulk_dense_f64", "reo_set_matrix_pseudobulk_dense_i64", "reo_set_matrix_pseudobulk_csc_f64", "reo_set_matrix_pseudobulk_csc_i64",
     "reo_filter_matrix", "reo_get_matrix", "reo_get_ref_mask", "reo_pair_list", "reo_sample_counts", "reo_pair_support",
+    "reo_sample_tests",
 ] + [f"reo_set_matrix_{form}_{t}" for form in ("csc_dev", "pseudobulk_csc_dev", "pseudobulk_dense_dev") for t in ("f64", "i64", "f32", "i32")]
 
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p)
@@ -140,6 +141,7 @@ def lib() -> ctypes.CDLL:
         "reo_pair_list": (i32, [vp, vp, i64, vp, ctypes.c_uint32, vp, vp, vp, i64]),
         "reo_sample_counts": (i32, [vp, vp, i64, vp, ctypes.c_uint32, vp, vp, vp]),
         "reo_pair_support": (i32, [vp, vp, i64, vp, vp, vp, vp, vp]),
+        "reo_sample_tests": (i32, [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
     }
     for t in ("f64", "i64", "f32", "i32"):   # SPARSE ON THE DEVICE
         sig["reo_set_matrix_csc_dev_" + t] = (i32, [vp, i64, i64, i64, vp, vp, i32, vp])
@@ -389,6 +391,57 @@ class PairSupport(NamedTuple):
         d = np.abs(self.delta(k))
         order = np.lexsort((self.partner, self.entry_genes, -d))   # (the last key is the primary one)
         return order[: max(int(n), 0)]
+
+
+def bh_columns(p: np.ndarray) -> np.ndarray:
+    """Benjamini-Hochberg down every column of p (rows x columns, float64): p * n / rank in ascending order (a stable sort), the reverse
+    cumulative minimum, clamped to 1 -- the rule of the reference's BenjaminiHochberg call (src/RankCompV3.jl:413), restated in numpy.
+    One row: the values as they are."""
+    p = np.asarray(p, dtype=np.float64)
+    if p.ndim != 2:
+        raise DimensionMismatch(REO_EINVAL, "bh_columns takes a rows x columns matrix")
+    n = p.shape[0]
+    if n <= 1:
+        return p.copy()
+    order = np.argsort(p, axis=0, kind="stable")
+    adj = np.take_along_axis(p, order, axis=0) * (n / np.arange(1, n + 1))[:, None]
+    adj = np.minimum.accumulate(adj[::-1], axis=0)[::-1]
+    out = np.empty_like(p)
+    np.put_along_axis(out, order, np.minimum(adj, 1.0), axis=0)
+    return out
+
+
+class SampleTests(NamedTuple):
+    """reo_sample_tests: per query gene (row) and sample (column, the caller's order), Fisher's exact test of the sample's orderings of the
+    gene against the pairs that are stable in the control group.  The 2 x 2 table of a cell is [[n_above_ctrl, n_below_ctrl], [u, d]] with
+    u = rev_up + (n_above_ctrl - rev_down - the ties of that half) partners below the gene in the sample.  The integer fields are None
+    when the call was made with counts=False.  Control samples are tested against a background they helped to define."""
+    genes: np.ndarray          # int32, the queries as given
+    n_above_ctrl: np.ndarray   # int32, len(genes): background partners the gene is stably above in the control group
+    n_below_ctrl: np.ndarray   # int32, len(genes): ... stably below
+    rev_up: np.ndarray | None    # int32, len(genes) x S: partners of n_below_ctrl that the gene lies ABOVE in the sample
+    rev_down: np.ndarray | None  # int32: partners of n_above_ctrl that the gene lies BELOW in the sample
+    tied: np.ndarray | None      # int32: background partners tied with the gene in the sample
+    p_up: np.ndarray           # float64, len(genes) x S: P(X >= u)
+    p_down: np.ndarray         # float64: P(X <= u)
+
+    @property
+    def pval(self) -> np.ndarray:
+        """The two-sided value min(1, 2 min(p_up, p_down)): the doubling rule of the reference's own two-sided tests."""
+        return np.minimum(1.0, 2.0 * np.minimum(self.p_up, self.p_down))
+
+    def padj(self) -> np.ndarray:
+        """Benjamini-Hochberg of pval per sample column, over the queried genes (bh_columns)."""
+        return bh_columns(self.pval)
+
+    def calls(self, pval_deg: float, padj_deg: float) -> np.ndarray:
+        """int8, len(genes) x S: +1 (up) where pval <= pval_deg, padj <= padj_deg and p_up < p_down; -1 (down) where both thresholds hold
+        and p_down < p_up; else 0."""
+        sig = (self.pval <= pval_deg) & (self.padj() <= padj_deg)
+        out = np.zeros(self.p_up.shape, dtype=np.int8)
+        out[sig & (self.p_up < self.p_down)] = 1
+        out[sig & (self.p_down < self.p_up)] = -1
+        return out
 
 
 class SampleScores(NamedTuple):
@@ -735,6 +788,32 @@ class Context:
     def sample_scores(self, genes, partner_mask=None) -> SampleScores:
         """Per sample, how far every query gene's reversed pairs (n13, n31) show the non-control order: two sample_counts calls."""
         return sample_scores_from(self.sample_counts(genes, "n13", partner_mask), self.sample_counts(genes, "n31", partner_mask))
+
+    def sample_tests_raw(self, genes, partner_mask, n_above_ctrl, n_below_ctrl, rev_up, rev_down, tied, p_up, p_down) -> None:
+        """reo_sample_tests on caller-made arrays (the integer arrays may be None); sample_tests is the convenient form."""
+        opt = lambda a: None if a is None else _ptr(a)   # noqa: E731
+        check(self._L.reo_sample_tests(self._h, _ptr(genes) if genes is not None and genes.size else None, 0 if genes is None else genes.size,
+                                       opt(partner_mask), opt(n_above_ctrl), opt(n_below_ctrl), opt(rev_up), opt(rev_down), opt(tied),
+                                       opt(p_up), opt(p_down)))
+
+    def sample_tests(self, genes=None, partner_mask=None, counts=True) -> SampleTests:
+        """Up or down in one sample (reo_sample_tests): for every query gene (None: all genes) and every sample, Fisher's exact test of the
+        sample's orderings of the gene against the partners -- partner_mask[j] set (None: the reference set of the last identify_degs,
+        ref_mask()) -- that it is stably above or below in the control group of the resident class table.  counts=False: the per-sample
+        integer fields are not fetched (None).  Host arrays; not available on a multi-GPU context."""
+        g = np.arange(self.G, dtype=np.int32) if genes is None else np.ascontiguousarray(genes, dtype=np.int32).reshape(-1)
+        pm = None
+        if partner_mask is not None:
+            pm = np.ascontiguousarray(np.asarray(partner_mask) != 0, dtype=np.uint8)
+            if pm.size != self.G:
+                raise DimensionMismatch(REO_EINVAL, "partner mask length != number of genes")
+        shape = (g.size, max(self.S, 1))
+        n_above, n_below = np.zeros(g.size, dtype=np.int32), np.zeros(g.size, dtype=np.int32)
+        ints = [np.zeros(shape, dtype=np.int32) for _ in range(3)] if counts else [None] * 3
+        p_up, p_down = np.ones(shape, dtype=np.float64), np.ones(shape, dtype=np.float64)
+        self.sample_tests_raw(g, pm, n_above, n_below, ints[0], ints[1], ints[2], p_up, p_down)
+        cut = lambda a: None if a is None else a[:, : self.S]   # noqa: E731
+        return SampleTests(g, n_above, n_below, cut(ints[0]), cut(ints[1]), cut(ints[2]), cut(p_up), cut(p_down))
 
     def pair_support_raw(self, genes, rowptr, partner, n_gt, n_eq, outcome) -> None:
         """reo_pair_support on caller-made arrays (any may be None); pair_support is the convenient form."""

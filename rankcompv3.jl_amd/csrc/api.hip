@@ -16,6 +16,7 @@
 #include "pair_list.h"
 #include "reo_internal.h"
 #include "sample_counts.h"
+#include "sample_tests.h"
 #include "pair_support.h"
 #include "contrast.h"
 #include "upload_csc.h"
@@ -580,6 +581,18 @@ static int32_t pass_fault(reo_ctx *c)
     return REO_EHIP;
 }
 
+// The slot -> column map of sc_slot_map into c->sc_slot2col (already sized by the caller), on the stream: uploaded once per change of the
+// groups, shared by reo_sample_counts, reo_sample_tests and reo_pair_support.
+static int32_t upload_slot2col(reo_ctx *c, const std::vector<int32_t> &map)
+{
+    if (map == c->sc_slot2col_host && c->sc_slot2col.p == c->sc_slot2col_uploaded) return REO_OK;
+    c->sc_slot2col_host = map;
+    c->sc_slot2col_uploaded = nullptr;
+    REO_HIP_CHECK(hipMemcpyAsync(c->sc_slot2col.p, c->sc_slot2col_host.data(), map.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    c->sc_slot2col_uploaded = c->sc_slot2col.p;
+    return REO_OK;
+}
+
 static int32_t need_complete_table(reo_ctx *c)
 {
     if (c->built_k < 0) { set_error("no class table: call reo_build_pairs first"); return REO_EINVAL; }
@@ -597,7 +610,7 @@ using namespace reo;
 
 extern "C" {
 
-int32_t reo_version(void) { return 900; }
+int32_t reo_version(void) { return 1000; }
 
 int32_t reo_trim_memory(void)
 {
@@ -1564,12 +1577,7 @@ int32_t reo_sample_counts(reo_ctx *c, const int32_t *genes, int64_t n_genes, con
         maskbits = c->refbits[c->ref_slot].p;
     }
     DrainOnExit drain(c);   // genes and partner_mask in, the counts out (declared after the buffers: the wait comes before their release)
-    if (map != c->sc_slot2col_host || c->sc_slot2col.p != c->sc_slot2col_uploaded) {   // once per change of the groups
-        c->sc_slot2col_host = map;
-        c->sc_slot2col_uploaded = nullptr;
-        REO_HIP_CHECK(hipMemcpyAsync(c->sc_slot2col.p, c->sc_slot2col_host.data(), map.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        c->sc_slot2col_uploaded = c->sc_slot2col.p;
-    }
+    if ((rc = upload_slot2col(c, map))) return rc;
     if (partner_mask) {
         REO_HIP_CHECK(hipMemsetAsync(d_maskbytes.p, 0, c->Gp, c->stream));
         REO_HIP_CHECK(hipMemcpyAsync(d_maskbytes.p, partner_mask, static_cast<size_t>(c->G), hipMemcpyHostToDevice, c->stream));
@@ -1584,6 +1592,95 @@ int32_t reo_sample_counts(reo_ctx *c, const int32_t *genes, int64_t n_genes, con
         if (n_eq) REO_HIP_CHECK(hipMemcpyAsync(n_eq + static_cast<size_t>(q0) * S, d_eq.p, rows * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
         if (n_sel) REO_HIP_CHECK(hipMemcpyAsync(n_sel + q0, d_sel.p, static_cast<size_t>(nq) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
         if ((rc = wait_or_drop_table(c))) return rc;   // the next batch reuses the buffers
+    }
+    drain.dismiss();
+    return REO_OK;
+}
+
+// Up or down in one sample (include/reo_hip.h): the queries in batches; per batch two launches of the counting kernel of reo_sample_counts
+// (class masks 0x1C0 and 0x007, with tied counts) into device buffers that stay there, one launch of k_sample_fisher (sampletests.hip)
+// over them, and the copies of the batch's rows into the caller's arrays.  Reads the class table, the bit planes and a reference mask
+// slot; writes none of them.
+int32_t reo_sample_tests(reo_ctx *c, const int32_t *genes, int64_t n_genes, const uint8_t *partner_mask, int32_t *n_above_ctrl,
+                         int32_t *n_below_ctrl, int32_t *rev_up, int32_t *rev_down, int32_t *tied, double *p_up, double *p_down)
+{
+    int32_t rc = no_multi(c, "reo_sample_tests");
+    if (rc || (rc = use(c))) return rc;
+    if ((rc = need_complete_table(c))) return rc;
+    char msg[320];
+    if (sample_tests_check_args(c->G, genes, n_genes, p_up, p_down, msg, sizeof msg)) { set_error("%s", msg); return REO_EINVAL; }
+    if (!partner_mask && c->ref_slot < 0) {
+        set_error("reo_sample_tests: partner_mask is null and there is no reference set to take its place: %s", c->ref_gone);
+        return REO_EINVAL;
+    }
+    if ((rc = ensure_transform(c))) return rc;   // (in place whenever there is a class table: nothing runs)
+    std::vector<int32_t> map;
+    if (!sc_slot_map(c->group_id.data(), c->S, c->ngroups, map) || c->goff32.empty() || static_cast<int64_t>(map.size()) != c->goff32.back()) {
+        set_error("reo_sample_tests: the sample slots of the bit planes do not match the group labels");
+        return REO_EHIP;
+    }
+    const int64_t S = c->S, slots = static_cast<int64_t>(map.size());
+    const char *env = getenv("REO_SAMPLE_TESTS_BATCH");
+    const int64_t batch = st_batch_rows(n_genes, slots, env ? atoll(env) : 0);
+    const size_t nb = static_cast<size_t>(batch), cells = nb * static_cast<size_t>(S);
+    const int64_t lf_entries = st_lf_entries(c->G);
+    DevBuf<int32_t> d_genes, d_sel_a, d_sel_b, d_gt_a, d_eq_a, d_gt_b, d_eq_b, d_rev_up, d_rev_down, d_tied, d_flag;
+    DevBuf<double> d_p_up, d_p_down;
+    DevBuf<uint8_t> d_maskbytes;
+    DevBuf<uint32_t> d_maskbits;
+    if ((rc = d_genes.ensure(nb)) || (rc = d_sel_a.ensure(nb)) || (rc = d_sel_b.ensure(nb)) || (rc = d_gt_a.ensure(nb * slots)) ||
+        (rc = d_eq_a.ensure(nb * slots)) || (rc = d_gt_b.ensure(nb * slots)) || (rc = d_eq_b.ensure(nb * slots)) ||
+        (rev_up && (rc = d_rev_up.ensure(cells))) || (rev_down && (rc = d_rev_down.ensure(cells))) || (tied && (rc = d_tied.ensure(cells))) ||
+        (rc = d_p_up.ensure(cells)) || (rc = d_p_down.ensure(cells)) || (rc = d_flag.ensure(1)) || (rc = c->sc_slot2col.ensure(map.size())) ||
+        (rc = c->st_lf.ensure(static_cast<size_t>(lf_entries))))
+        return rc;
+    const uint32_t *maskbits = nullptr;
+    if (partner_mask) {
+        if ((rc = d_maskbytes.ensure(c->Gp)) || (rc = d_maskbits.ensure(c->Wp))) return rc;
+        maskbits = d_maskbits.p;
+    } else {
+        maskbits = c->refbits[c->ref_slot].p;
+    }
+    std::vector<double> lf;
+    int32_t flag = 0;
+    DrainOnExit drain(c);   // genes, partner_mask and lf in, the results out (declared after the buffers: the wait comes before their release)
+    if (c->st_lf_G != c->G) {   // once per context and gene count
+        st_build_lf(c->G, lf);
+        c->st_lf_G = -1;
+        REO_HIP_CHECK(hipMemcpyAsync(c->st_lf.p, lf.data(), lf.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        REO_HIP_CHECK(hipStreamSynchronize(c->stream));   // (lf is a local)
+        c->st_lf_G = c->G;
+    }
+    if ((rc = upload_slot2col(c, map))) return rc;
+    if (partner_mask) {
+        REO_HIP_CHECK(hipMemsetAsync(d_maskbytes.p, 0, c->Gp, c->stream));
+        REO_HIP_CHECK(hipMemcpyAsync(d_maskbytes.p, partner_mask, static_cast<size_t>(c->G), hipMemcpyHostToDevice, c->stream));
+        if ((rc = launch_pack_ref(c, d_maskbytes.p, d_maskbits.p))) return rc;
+    }
+    REO_HIP_CHECK(hipMemsetAsync(d_flag.p, 0, sizeof(int32_t), c->stream));
+    for (int64_t q0 = 0; q0 < n_genes; q0 += batch) {
+        const int64_t nq = std::min(batch, n_genes - q0);
+        const size_t rows = static_cast<size_t>(nq) * static_cast<size_t>(S), at = static_cast<size_t>(q0) * S;
+        REO_HIP_CHECK(hipMemcpyAsync(d_genes.p, genes + q0, static_cast<size_t>(nq) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        if ((rc = launch_sample_counts(c, d_genes.p, nq, maskbits, kStMaskAbove, c->sc_slot2col.p, d_sel_a.p, d_gt_a.p, d_eq_a.p)) ||
+            (rc = launch_sample_counts(c, d_genes.p, nq, maskbits, kStMaskBelow, c->sc_slot2col.p, d_sel_b.p, d_gt_b.p, d_eq_b.p)) ||
+            (rc = launch_sample_fisher(c, nq, d_sel_a.p, d_sel_b.p, d_gt_a.p, d_eq_a.p, d_gt_b.p, d_eq_b.p, c->st_lf.p, lf_entries,
+                                       rev_up ? d_rev_up.p : nullptr, rev_down ? d_rev_down.p : nullptr, tied ? d_tied.p : nullptr, d_p_up.p,
+                                       d_p_down.p, d_flag.p)))
+            return rc;
+        if (n_above_ctrl) REO_HIP_CHECK(hipMemcpyAsync(n_above_ctrl + q0, d_sel_a.p, static_cast<size_t>(nq) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        if (n_below_ctrl) REO_HIP_CHECK(hipMemcpyAsync(n_below_ctrl + q0, d_sel_b.p, static_cast<size_t>(nq) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        if (rev_up) REO_HIP_CHECK(hipMemcpyAsync(rev_up + at, d_rev_up.p, rows * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        if (rev_down) REO_HIP_CHECK(hipMemcpyAsync(rev_down + at, d_rev_down.p, rows * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        if (tied) REO_HIP_CHECK(hipMemcpyAsync(tied + at, d_tied.p, rows * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        REO_HIP_CHECK(hipMemcpyAsync(p_up + at, d_p_up.p, rows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        REO_HIP_CHECK(hipMemcpyAsync(p_down + at, d_p_down.p, rows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        REO_HIP_CHECK(hipMemcpyAsync(&flag, d_flag.p, sizeof flag, hipMemcpyDeviceToHost, c->stream));
+        if ((rc = wait_or_drop_table(c))) return rc;   // the next batch reuses the buffers
+        if (flag) {
+            set_error("reo_sample_tests: the counting kernel delivered counts that %lld genes cannot produce; the results are not valid", (long long)c->G);
+            return REO_EHIP;
+        }
     }
     drain.dismiss();
     return REO_OK;
@@ -1620,12 +1717,7 @@ int32_t reo_pair_support(reo_ctx *c, const int32_t *genes, int64_t n_genes, cons
         return rc;
     std::vector<PsItem> items;
     DrainOnExit drain(c);   // items and partners in, counts and outcomes out (declared after the buffers: the wait comes before their release)
-    if (outcome && (map != c->sc_slot2col_host || c->sc_slot2col.p != c->sc_slot2col_uploaded)) {   // once per change of the groups (shared with reo_sample_counts)
-        c->sc_slot2col_host = map;
-        c->sc_slot2col_uploaded = nullptr;
-        REO_HIP_CHECK(hipMemcpyAsync(c->sc_slot2col.p, c->sc_slot2col_host.data(), map.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        c->sc_slot2col_uploaded = c->sc_slot2col.p;
-    }
+    if (outcome && (rc = upload_slot2col(c, map))) return rc;
     int64_t row = 0;
     for (int64_t e0 = 0; e0 < total; e0 += batch) {
         const int64_t ne = std::min(batch, total - e0);

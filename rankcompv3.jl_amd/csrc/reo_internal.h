@@ -312,6 +312,9 @@ struct reo_ctx {
     reo::DevBuf<int32_t> sc_slot2col;   // [32 * sample blocks]
     std::vector<int32_t> sc_slot2col_host;      // what it holds ...
     const int32_t *sc_slot2col_uploaded = nullptr;   // ... and in which allocation
+    // reo_sample_tests: the log-factorial table lf[0 .. 2 (G - 1)] (sample_tests.h), uploaded once and rebuilt when G changes
+    reo::DevBuf<double> st_lf;
+    int64_t st_lf_G = -1;               // the G it was built for (-1: none)
     reo::DevBuf<int32_t> raw;           // [G][8]
     reo::DevBuf<uint32_t> delta_list;   // [2][Gp] changed genes (gene << 1 | added) per pass parity
     reo::DevBuf<int32_t> cont;          // [G][9]
@@ -425,6 +428,14 @@ int32_t launch_pair_fill(reo_ctx *c, const int32_t *d_genes, int64_t n_genes, co
 int plane_bits(int64_t G);   // kernels.hip: position planes that the count loops read
 int32_t launch_sample_counts(reo_ctx *c, const int32_t *d_genes, int64_t n_queries, const uint32_t *d_maskbits, uint32_t class_mask,
                              const int32_t *d_slot2col, int32_t *d_sel, int32_t *d_gt, int32_t *d_eq);
+
+// sampletests.hip: the kernel of reo_sample_tests (shared arithmetic and host checks: sample_tests.h).  The six counts are what two
+// launch_sample_counts calls (class masks 0x1C0 and 0x007, tied counts included) left on the device: d_sel_*: [n_queries], the rest
+// [n_queries][S]; d_lf: the log-factorial table of lf_entries >= 2 (G - 1) + 1 doubles; d_rev_up / d_rev_down / d_tied: [n_queries][S] or
+// null; d_p_up / d_p_down: [n_queries][S]; d_flag: [1], set when a thread met counts that G genes cannot produce
+int32_t launch_sample_fisher(reo_ctx *c, int64_t n_queries, const int32_t *d_sel_a, const int32_t *d_sel_b, const int32_t *d_gt_a,
+                             const int32_t *d_eq_a, const int32_t *d_gt_b, const int32_t *d_eq_b, const double *d_lf, int64_t lf_entries,
+                             int32_t *d_rev_up, int32_t *d_rev_down, int32_t *d_tied, double *d_p_up, double *d_p_down, int32_t *d_flag);
 
 // pairsupport.hip: the kernel of reo_pair_support (work items, batches and host checks: pair_support.h).  d_items: [n_items] work items of the
 // batch; d_partner: [entries of the batch] partners, checked by the caller to lie in [0, G) and off the diagonal; d_slot2col as above (read

@@ -18,7 +18,8 @@ import os
 import numpy as np
 
 from . import _ffi, synth
-from .hotpath import HEADER, need_pairs_for_support, run_identify_degs, write_pair_support_tsv, write_pairs_tsv, write_sample_scores_tsv
+from .hotpath import (HEADER, need_pairs_for_support, run_identify_degs, write_pair_support_tsv, write_pairs_tsv, write_sample_calls_tsv,
+                      write_sample_scores_tsv)
 
 log = logging.getLogger("reo_hip")
 
@@ -286,7 +287,7 @@ def reoa(fn_expr: str = "fn_expr.txt", fn_meta: str = "fn_meta.txt", *, expr_thr
          n_pseudo: int = 0, use_hk_genes: str = "yes", hk_file: str | None = None, gene_name_type: str = "ENSEMBL",
          ref_gene_max: int = 3000, ref_gene_min: int = 100, n_iter: int = 128, n_conv: int = 5, work_dir: str = "./",
          use_testdata: str = "no", seed: int = 0, device: int = -1, testdata_dir: str | None = None, align_meta: bool | None = None,
-         pairs=None, sample_scores: bool = False, pair_support: bool = False, contrasts=None):
+         pairs=None, sample_scores: bool = False, pair_support: bool = False, contrasts=None, sample_tests: bool = False):
     """reoa(fn_expr, fn_meta; kwargs...) -- src/RankCompV3.jl:536-555.  `expr_threshold` is accepted and
     unused, as in the reference (:539).  Extra keywords: `seed` (the reference's RNG is unseeded),
     `device`, `testdata_dir` (where fn_expr.txt / fn_meta.txt of the reference's test/ directory live), `align_meta`
@@ -296,7 +297,9 @@ def reoa(fn_expr: str = "fn_expr.txt", fn_meta: str = "fn_meta.txt", *, expr_thr
     writes `<stem>_<fg_name>_sample_scores.tsv` per comparison, one row per DEG and one column per sample: in how many more of the DEG's
     reversed pairs the sample shows the non-control order than the control's -- SampleScores.net), `pair_support` (True, which needs
     `pairs`: additionally writes `<stem>_<fg_name>_pair_support.tsv` per comparison, one line per listed pair: gene, partner, class, and
-    per group level in how many of its samples the DEG lies above the partner, `<level>_gt`, and level with it, `<level>_eq`), `contrasts`
+    per group level in how many of its samples the DEG lies above the partner, `<level>_gt`, and level with it, `<level>_eq`),
+    `sample_tests` (True: additionally writes `<stem>_<fg_name>_sample_calls.tsv` per comparison, one row per gene that is called up (1)
+    or down (-1) in at least one sample and one column per sample -- SampleTests.calls(pval_deg, padj_deg) of all genes), `contrasts`
     ("all" or (ctrl_level, treat_level) pairs as in run_identify_degs: one comparison per contrast, group against group, instead of the
     reference's; the files are `<stem>_<ctrl>_<treat>_result.tsv`, the gene_up_down columns `<ctrl>_vs_<treat>` -- the reference's two-group
     naming -- and the optional files carry the same `<ctrl>_<treat>`)."""
@@ -319,19 +322,20 @@ def reoa(fn_expr: str = "fn_expr.txt", fn_meta: str = "fn_meta.txt", *, expr_thr
                    ref_gene_max=ref_gene_max, ref_gene_min=ref_gene_min, seed=seed, sums=gpu_sums, align_meta=align_meta)
     run = run_identify_degs(prep["data"], prep["sample_groups"], prep["gene_names"], pval_reo, pval_deg, padj_deg,
                             prep["ref"], n_iter, n_conv, seed=seed, device=device, pairs=pairs,
-                            sample_scores=sample_scores, pair_support=pair_support, contrasts=contrasts)  # :652-662
+                            sample_scores=sample_scores, pair_support=pair_support, contrasts=contrasts,
+                            sample_tests=sample_tests)  # :652-662
     for p, (d, n) in enumerate(run.trace):
         log.info("INFO: iteration %d,  # DEGs %d, # non-DEGs %d", p, d, n)  # :418
     df = write_outputs(stem, prep, run, work_dir)
-    write_extras(stem, prep, run, work_dir)
+    write_extras(stem, prep, run, work_dir, pval_deg, padj_deg)
     df.attrs["run"] = run
     return df
 
 
-def write_extras(stem: str, prep: dict, run, work_dir: str = ".") -> list:
-    """The files beyond the reference's, one per comparison and kind that the run carries ("pairs", "pair_support", "sample_scores" in its
-    comparison dicts): `<stem>_<fg_name>_pairs.tsv`, `_pair_support.tsv`, `_sample_scores.tsv`, with write_outputs' fg_name.  Returns the
-    paths written."""
+def write_extras(stem: str, prep: dict, run, work_dir: str = ".", pval_deg: float = 1.0, padj_deg: float = 0.05) -> list:
+    """The files beyond the reference's, one per comparison and kind that the run carries ("pairs", "pair_support", "sample_scores",
+    "sample_tests" in its comparison dicts): `<stem>_<fg_name>_pairs.tsv`, `_pair_support.tsv`, `_sample_scores.tsv`, `_sample_calls.tsv`
+    (the calls at pval_deg / padj_deg), with write_outputs' fg_name.  Returns the paths written."""
     g_name, out = prep["g_name"], []
     for cm in run.comparisons:
         fg = fg_name(g_name, cm)
@@ -344,4 +348,8 @@ def write_extras(stem: str, prep: dict, run, work_dir: str = ".") -> list:
         if "sample_scores" in cm:
             out.append(os.path.join(work_dir, f"{stem}_{fg}_sample_scores.tsv"))
             write_sample_scores_tsv(out[-1], prep["gene_names"], prep["sample_names"], cm["sample_scores"])
+        if "sample_tests" in cm:
+            out.append(os.path.join(work_dir, f"{stem}_{fg}_sample_calls.tsv"))
+            st = cm["sample_tests"]
+            write_sample_calls_tsv(out[-1], prep["gene_names"], prep["sample_names"], st.genes, st.calls(pval_deg, padj_deg))
     return out
