@@ -181,6 +181,15 @@ def _ptr(a: np.ndarray) -> int:
     return a.ctypes.data
 
 
+def _opt(a):
+    return None if a is None else _ptr(a)
+
+
+def _genes(genes):
+    """(pointer, count) of a query's gene (or partner) array: null for None or an empty one."""
+    return (_ptr(genes) if genes is not None and genes.size else None, 0 if genes is None else genes.size)
+
+
 # element types with an entry point of their own; every other integer type (and bool) goes to Int64, every other float type to Float64
 _NATIVE = {np.dtype(np.float64): "f64", np.dtype(np.int64): "i64", np.dtype(np.float32): "f32", np.dtype(np.int32): "i32"}
 
@@ -734,12 +743,19 @@ class Context:
         check(self._L.reo_get_ref_mask(self._h, _ptr(m), None))
         return m[: self.G].astype(bool)
 
+    def _partner_mask(self, partner_mask):
+        """A caller's partner mask as the uint8 array (0 / 1 per gene) that the library reads, or None."""
+        if partner_mask is None:
+            return None
+        pm = np.ascontiguousarray(np.asarray(partner_mask) != 0, dtype=np.uint8)
+        if pm.size != self.G:
+            raise DimensionMismatch(REO_EINVAL, "partner mask length != number of genes")
+        return pm
+
     def pair_list_raw(self, genes, mask: int, partner_mask, rowptr, partner, code, capacity: int) -> None:
         """reo_pair_list on caller-made arrays (partner and code None: count only); pair_list is the convenient form."""
-        check(self._L.reo_pair_list(self._h, _ptr(genes) if genes is not None and genes.size else None, 0 if genes is None else genes.size,
-                                    None if partner_mask is None else _ptr(partner_mask), ctypes.c_uint32(mask & 0xFFFFFFFF),
-                                    None if rowptr is None else _ptr(rowptr), None if partner is None else _ptr(partner),
-                                    None if code is None else _ptr(code), int(capacity)))
+        check(self._L.reo_pair_list(self._h, *_genes(genes), _opt(partner_mask), ctypes.c_uint32(mask & 0xFFFFFFFF), _opt(rowptr), _opt(partner),
+                                    _opt(code), int(capacity)))
 
     def pair_list(self, genes, classes, partner_mask=None) -> PairList:
         """The partner genes behind the tallies of `genes` (reo_pair_list): for every query gene the partners j, ascending, with
@@ -747,11 +763,7 @@ class Context:
         int mask, names "n11" .. "n33", codes 0 .. 8 or "reversed" (class_mask).  Counts first, allocates, then fills."""
         mask = class_mask(classes)
         g = np.ascontiguousarray(genes, dtype=np.int32).reshape(-1)
-        pm = None
-        if partner_mask is not None:
-            pm = np.ascontiguousarray(np.asarray(partner_mask) != 0, dtype=np.uint8)
-            if pm.size != self.G:
-                raise DimensionMismatch(REO_EINVAL, "partner mask length != number of genes")
+        pm = self._partner_mask(partner_mask)
         rowptr = np.zeros(g.size + 1, dtype=np.int64)
         self.pair_list_raw(g, mask, pm, rowptr, None, None, 0)
         total = int(rowptr[-1])
@@ -763,10 +775,8 @@ class Context:
 
     def sample_counts_raw(self, genes, mask: int, partner_mask, n_sel, n_gt, n_eq) -> None:
         """reo_sample_counts on caller-made arrays (n_sel and n_eq may be None); sample_counts is the convenient form."""
-        check(self._L.reo_sample_counts(self._h, _ptr(genes) if genes is not None and genes.size else None, 0 if genes is None else genes.size,
-                                        None if partner_mask is None else _ptr(partner_mask), ctypes.c_uint32(mask & 0xFFFFFFFF),
-                                        None if n_sel is None else _ptr(n_sel), None if n_gt is None else _ptr(n_gt),
-                                        None if n_eq is None else _ptr(n_eq)))
+        check(self._L.reo_sample_counts(self._h, *_genes(genes), _opt(partner_mask), ctypes.c_uint32(mask & 0xFFFFFFFF), _opt(n_sel), _opt(n_gt),
+                                        _opt(n_eq)))
 
     def sample_counts(self, genes, classes, partner_mask=None, ties=True) -> SampleCounts:
         """In which samples (reo_sample_counts): for every query gene and every sample, in how many of its selected pairs -- partners j with
@@ -774,11 +784,7 @@ class Context:
         (class_mask) -- the gene lies above its partner, and in how many the two are tied.  ties=False: no tied counts (n_eq None)."""
         mask = class_mask(classes)
         g = np.ascontiguousarray(genes, dtype=np.int32).reshape(-1)
-        pm = None
-        if partner_mask is not None:
-            pm = np.ascontiguousarray(np.asarray(partner_mask) != 0, dtype=np.uint8)
-            if pm.size != self.G:
-                raise DimensionMismatch(REO_EINVAL, "partner mask length != number of genes")
+        pm = self._partner_mask(partner_mask)
         n_sel = np.zeros(g.size, dtype=np.int32)
         n_gt = np.zeros((g.size, max(self.S, 1)), dtype=np.int32)
         n_eq = np.zeros_like(n_gt) if ties else None
@@ -791,10 +797,8 @@ class Context:
 
     def sample_tests_raw(self, genes, partner_mask, n_above_ctrl, n_below_ctrl, rev_up, rev_down, tied, p_up, p_down) -> None:
         """reo_sample_tests on caller-made arrays (the integer arrays may be None); sample_tests is the convenient form."""
-        opt = lambda a: None if a is None else _ptr(a)   # noqa: E731
-        check(self._L.reo_sample_tests(self._h, _ptr(genes) if genes is not None and genes.size else None, 0 if genes is None else genes.size,
-                                       opt(partner_mask), opt(n_above_ctrl), opt(n_below_ctrl), opt(rev_up), opt(rev_down), opt(tied),
-                                       opt(p_up), opt(p_down)))
+        check(self._L.reo_sample_tests(self._h, *_genes(genes), _opt(partner_mask), _opt(n_above_ctrl), _opt(n_below_ctrl), _opt(rev_up),
+                                       _opt(rev_down), _opt(tied), _opt(p_up), _opt(p_down)))
 
     def sample_tests(self, genes=None, partner_mask=None, counts=True) -> SampleTests:
         """Up or down in one sample (reo_sample_tests): for every query gene (None: all genes) and every sample, Fisher's exact test of the
@@ -802,11 +806,7 @@ class Context:
         ref_mask()) -- that it is stably above or below in the control group of the resident class table.  counts=False: the per-sample
         integer fields are not fetched (None).  Host arrays; not available on a multi-GPU context."""
         g = np.arange(self.G, dtype=np.int32) if genes is None else np.ascontiguousarray(genes, dtype=np.int32).reshape(-1)
-        pm = None
-        if partner_mask is not None:
-            pm = np.ascontiguousarray(np.asarray(partner_mask) != 0, dtype=np.uint8)
-            if pm.size != self.G:
-                raise DimensionMismatch(REO_EINVAL, "partner mask length != number of genes")
+        pm = self._partner_mask(partner_mask)
         shape = (g.size, max(self.S, 1))
         n_above, n_below = np.zeros(g.size, dtype=np.int32), np.zeros(g.size, dtype=np.int32)
         ints = [np.zeros(shape, dtype=np.int32) for _ in range(3)] if counts else [None] * 3
@@ -817,10 +817,8 @@ class Context:
 
     def pair_support_raw(self, genes, rowptr, partner, n_gt, n_eq, outcome) -> None:
         """reo_pair_support on caller-made arrays (any may be None); pair_support is the convenient form."""
-        check(self._L.reo_pair_support(self._h, _ptr(genes) if genes is not None and genes.size else None, 0 if genes is None else genes.size,
-                                       None if rowptr is None else _ptr(rowptr), _ptr(partner) if partner is not None and partner.size else None,
-                                       None if n_gt is None else _ptr(n_gt), None if n_eq is None else _ptr(n_eq),
-                                       None if outcome is None else _ptr(outcome)))
+        check(self._L.reo_pair_support(self._h, *_genes(genes), _opt(rowptr), _genes(partner)[0],
+                                       _opt(n_gt), _opt(n_eq), _opt(outcome)))
 
     def pair_support(self, pairs, ties=True, outcomes=False) -> PairSupport:
         """How strongly (reo_pair_support): for every pair of `pairs` -- a PairList, or a (genes, rowptr, partner) triple of the caller's

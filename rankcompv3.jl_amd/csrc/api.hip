@@ -13,11 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "pair_list.h"
 #include "reo_internal.h"
-#include "sample_counts.h"
-#include "sample_tests.h"
-#include "pair_support.h"
 #include "contrast.h"
 #include "upload_csc.h"
 
@@ -322,7 +318,7 @@ static void drop_ref_mask(reo_ctx *c, const char *why)
 
 // The wait of a call that may be the first to see an asynchronous failure of the pair kernel (reo_build_pairs returns with
 // it in flight on one GPU): the table cannot be trusted then, and a retry must rebuild it.
-static int32_t wait_or_drop_table(reo_ctx *c)
+int32_t wait_or_drop_table(reo_ctx *c)
 {
     const hipError_t e = stream_wait(c);
     if (e == hipSuccess) return REO_OK;
@@ -333,28 +329,20 @@ static int32_t wait_or_drop_table(reo_ctx *c)
     return REO_EHIP;
 }
 
-// Every call that enqueues an asynchronous copy from or into CALLER memory (or a local) holds one of these: whatever way the call
-// ends -- a failing REO_HIP_CHECK between the enqueue and the wait included -- the stream has been waited for before the caller
-// gets its arrays back (include/reo_hip.h: "no host pointer is retained after return").  A call that has done its own wait
-// dismisses the guard; the extra wait of an error path costs nothing that matters.
-struct DrainOnExit {
-    reo_ctx *c;
-    bool armed = true;
-    explicit DrainOnExit(reo_ctx *ctx) : c(ctx) {}
-    DrainOnExit(const DrainOnExit &) = delete;
-    DrainOnExit &operator=(const DrainOnExit &) = delete;
-    void dismiss() { armed = false; }
-    ~DrainOnExit()
-    {
-        if (!armed || !c || !c->stream) return;
-        (void)hipStreamSynchronize(c->stream);
-    }
-};
-
-static int32_t use(reo_ctx *c)
+int32_t use(reo_ctx *c)
 {
     if (!c) { set_error("null context"); return REO_EINVAL; }
     REO_HIP_CHECK(hipSetDevice(c->device));
+    return REO_OK;
+}
+
+int32_t no_multi(reo_ctx *c, const char *what)
+{
+    if (!c) { set_error("null context"); return REO_EINVAL; }
+    if (c->in_multi) {
+        set_error("%s is not available on a reo_create_multi context (every device would need the matrix: use one process per GPU, each with its own context)", what);
+        return REO_EINVAL;
+    }
     return REO_OK;
 }
 
@@ -457,7 +445,7 @@ static int32_t set_matrix(reo_ctx *c, const void *X, int64_t G, int64_t S, int64
     return REO_OK;
 }
 
-static int32_t ensure_transform(reo_ctx *c)
+int32_t ensure_transform(reo_ctx *c)
 {
     if (c->dtype == 0) { set_error("no expression matrix set"); return REO_EINVAL; }
     if (c->group_id.empty()) { set_error("no groups set"); return REO_EINVAL; }
@@ -583,7 +571,7 @@ static int32_t pass_fault(reo_ctx *c)
 
 // The slot -> column map of sc_slot_map into c->sc_slot2col (already sized by the caller), on the stream: uploaded once per change of the
 // groups, shared by reo_sample_counts, reo_sample_tests and reo_pair_support.
-static int32_t upload_slot2col(reo_ctx *c, const std::vector<int32_t> &map)
+int32_t upload_slot2col(reo_ctx *c, const std::vector<int32_t> &map)
 {
     if (map == c->sc_slot2col_host && c->sc_slot2col.p == c->sc_slot2col_uploaded) return REO_OK;
     c->sc_slot2col_host = map;
@@ -593,7 +581,7 @@ static int32_t upload_slot2col(reo_ctx *c, const std::vector<int32_t> &map)
     return REO_OK;
 }
 
-static int32_t need_complete_table(reo_ctx *c)
+int32_t need_complete_table(reo_ctx *c)
 {
     if (c->built_k < 0) { set_error("no class table: call reo_build_pairs first"); return REO_EINVAL; }
     if (!c->table_complete) {
@@ -864,16 +852,6 @@ int32_t reo_set_matrix_csc_i32(reo_ctx *c, int64_t G, int64_t S, const int64_t *
 
 // Pseudo-bulk profiles as the expression matrix (include/reo_hip.h, CELLS): reo_pseudobulk_*'s sums stay in the context's own matrix.
 // Whatever fails, the context holds no matrix afterwards (the old one may already have given its buffer to the new one).
-static int32_t no_multi(reo_ctx *c, const char *what)
-{
-    if (!c) { set_error("null context"); return REO_EINVAL; }
-    if (c->in_multi) {
-        set_error("%s is not available on a reo_create_multi context (every device would need the matrix: use one process per GPU, each with its own context)", what);
-        return REO_EINVAL;
-    }
-    return REO_OK;
-}
-
 static int32_t set_matrix_pseudobulk(reo_ctx *c, bool csc, bool is_int, const void *X, int64_t G, int64_t C, int64_t ld, const int64_t *colptr,
                                      const int32_t *rowidx, const void *val, const int32_t *order, int64_t n_order, const int32_t *chunk_ptr,
                                      int32_t n_out)
@@ -1468,273 +1446,6 @@ int32_t reo_get_ref_mask(reo_ctx *c, uint8_t *ref_mask, int32_t *nref)
     int32_t n = 0;
     for (int64_t i = 0; i < c->G; ++i) { ref_mask[i] = ref_mask[i] != 0; n += ref_mask[i]; }
     if (nref) *nref = n;
-    return REO_OK;
-}
-
-// The partners behind the tallies (include/reo_hip.h): count on the device, prefix sums on the host (the caller wants rowptr anyway), fill on
-// the device into buffers sized from the counted total.
-int32_t reo_pair_list(reo_ctx *c, const int32_t *genes, int64_t n_genes, const uint8_t *partner_mask, uint32_t class_mask, int64_t *rowptr,
-                      int32_t *partner, uint8_t *code, int64_t capacity)
-{
-    int32_t rc = no_multi(c, "reo_pair_list");
-    if (rc || (rc = use(c))) return rc;
-    if ((rc = need_complete_table(c))) return rc;
-    char msg[320];
-    if (pair_list_check_args(c->G, genes, n_genes, class_mask, rowptr, partner, code, capacity, msg, sizeof msg)) { set_error("%s", msg); return REO_EINVAL; }
-    if (!partner_mask && c->ref_slot < 0) {
-        set_error("reo_pair_list: partner_mask is null and there is no reference set to take its place: %s", c->ref_gone);
-        return REO_EINVAL;
-    }
-    const size_t n = static_cast<size_t>(n_genes);
-    DevBuf<int32_t> d_genes, d_count, d_partner, d_flag;
-    DevBuf<int64_t> d_rowptr;
-    DevBuf<uint8_t> d_code, d_maskbytes;
-    DevBuf<uint32_t> d_maskbits;
-    if ((rc = d_genes.ensure(n)) || (rc = d_count.ensure(n))) return rc;
-    const uint32_t *maskbits = nullptr;
-    if (partner_mask) {
-        if ((rc = d_maskbytes.ensure(c->Gp)) || (rc = d_maskbits.ensure(c->Wp))) return rc;
-        maskbits = d_maskbits.p;
-    } else {
-        maskbits = c->refbits[c->ref_slot].p;
-    }
-    std::vector<int32_t> count(n);
-    int32_t flag = 0;
-    DrainOnExit drain(c);   // genes and partner_mask in, partner and code out (declared after the buffers: the wait comes before their release)
-    REO_HIP_CHECK(hipMemcpyAsync(d_genes.p, genes, n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    if (partner_mask) {
-        REO_HIP_CHECK(hipMemsetAsync(d_maskbytes.p, 0, c->Gp, c->stream));
-        REO_HIP_CHECK(hipMemcpyAsync(d_maskbytes.p, partner_mask, static_cast<size_t>(c->G), hipMemcpyHostToDevice, c->stream));
-        if ((rc = launch_pack_ref(c, d_maskbytes.p, d_maskbits.p))) return rc;
-    }
-    if ((rc = launch_pair_count(c, d_genes.p, n_genes, maskbits, class_mask, d_count.p))) return rc;
-    REO_HIP_CHECK(hipMemcpyAsync(count.data(), d_count.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    if ((rc = wait_or_drop_table(c))) return rc;
-    for (size_t q = 0; q < n; ++q)
-        if (count[q] < 0 || count[q] >= c->G) { set_error("reo_pair_list: the count of query %zu reads %d with %lld genes", q, count[q], (long long)c->G); return REO_EHIP; }
-    const int64_t total = pair_list_rowptr(count.data(), n_genes, rowptr);
-    if (!partner || total == 0) { drain.dismiss(); return REO_OK; }
-    if (total > capacity) {
-        set_error("reo_pair_list: the lists hold %lld entries, capacity is %lld (rowptr has been filled: allocate rowptr[n_genes] entries)",
-                  (long long)total, (long long)capacity);
-        return REO_EINVAL;
-    }
-    if ((rc = d_rowptr.ensure(n + 1)) || (rc = d_partner.ensure(static_cast<size_t>(total))) || (rc = d_code.ensure(static_cast<size_t>(total))) ||
-        (rc = d_flag.ensure(1)))
-        return rc;
-    REO_HIP_CHECK(hipMemcpyAsync(d_rowptr.p, rowptr, (n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-    REO_HIP_CHECK(hipMemsetAsync(d_flag.p, 0, sizeof(int32_t), c->stream));
-    if ((rc = launch_pair_fill(c, d_genes.p, n_genes, maskbits, class_mask, d_rowptr.p, d_partner.p, d_code.p, total, d_flag.p))) return rc;
-    REO_HIP_CHECK(hipMemcpyAsync(partner, d_partner.p, static_cast<size_t>(total) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    REO_HIP_CHECK(hipMemcpyAsync(code, d_code.p, static_cast<size_t>(total), hipMemcpyDeviceToHost, c->stream));
-    REO_HIP_CHECK(hipMemcpyAsync(&flag, d_flag.p, sizeof flag, hipMemcpyDeviceToHost, c->stream));
-    if ((rc = wait_or_drop_table(c))) return rc;
-    drain.dismiss();
-    if (flag) {
-        set_error("reo_pair_list: the fill pass found another number of pairs in a row than the count pass (the class table changed between them?); "
-                  "the lists are not valid");
-        return REO_EHIP;
-    }
-    return REO_OK;
-}
-
-// In which samples (include/reo_hip.h): the queries in batches whose two count buffers stay under the budget of sample_counts.h; per batch one
-// launch and the copies of its rows into the caller's arrays.  Reads the class table, the bit planes and a reference mask slot; writes none of them.
-int32_t reo_sample_counts(reo_ctx *c, const int32_t *genes, int64_t n_genes, const uint8_t *partner_mask, uint32_t class_mask, int32_t *n_sel,
-                          int32_t *n_gt, int32_t *n_eq)
-{
-    int32_t rc = no_multi(c, "reo_sample_counts");
-    if (rc || (rc = use(c))) return rc;
-    if ((rc = need_complete_table(c))) return rc;
-    char msg[320];
-    if (sample_counts_check_args(c->G, genes, n_genes, class_mask, n_gt, msg, sizeof msg)) { set_error("%s", msg); return REO_EINVAL; }
-    if (!partner_mask && c->ref_slot < 0) {
-        set_error("reo_sample_counts: partner_mask is null and there is no reference set to take its place: %s", c->ref_gone);
-        return REO_EINVAL;
-    }
-    if ((rc = ensure_transform(c))) return rc;   // (in place whenever there is a class table: nothing runs)
-    // the caller's column of every sample slot, from the group labels the transform laid the slots out by
-    std::vector<int32_t> map;
-    if (!sc_slot_map(c->group_id.data(), c->S, c->ngroups, map) || c->goff32.empty() || static_cast<int64_t>(map.size()) != c->goff32.back()) {
-        set_error("reo_sample_counts: the sample slots of the bit planes do not match the group labels");
-        return REO_EHIP;
-    }
-    const int64_t S = c->S, slots = static_cast<int64_t>(map.size());
-    const char *env = getenv("REO_SAMPLE_COUNTS_BATCH");
-    const int64_t batch = sc_batch_rows(n_genes, slots, env ? atoll(env) : 0);
-    const size_t nb = static_cast<size_t>(batch);
-    DevBuf<int32_t> d_genes, d_sel, d_gt, d_eq;
-    DevBuf<uint8_t> d_maskbytes;
-    DevBuf<uint32_t> d_maskbits;
-    if ((rc = d_genes.ensure(nb)) || (rc = d_sel.ensure(nb)) || (rc = d_gt.ensure(nb * slots)) || (n_eq && (rc = d_eq.ensure(nb * slots))) ||
-        (rc = c->sc_slot2col.ensure(map.size())))
-        return rc;
-    const uint32_t *maskbits = nullptr;
-    if (partner_mask) {
-        if ((rc = d_maskbytes.ensure(c->Gp)) || (rc = d_maskbits.ensure(c->Wp))) return rc;
-        maskbits = d_maskbits.p;
-    } else {
-        maskbits = c->refbits[c->ref_slot].p;
-    }
-    DrainOnExit drain(c);   // genes and partner_mask in, the counts out (declared after the buffers: the wait comes before their release)
-    if ((rc = upload_slot2col(c, map))) return rc;
-    if (partner_mask) {
-        REO_HIP_CHECK(hipMemsetAsync(d_maskbytes.p, 0, c->Gp, c->stream));
-        REO_HIP_CHECK(hipMemcpyAsync(d_maskbytes.p, partner_mask, static_cast<size_t>(c->G), hipMemcpyHostToDevice, c->stream));
-        if ((rc = launch_pack_ref(c, d_maskbytes.p, d_maskbits.p))) return rc;
-    }
-    for (int64_t q0 = 0; q0 < n_genes; q0 += batch) {
-        const int64_t nq = std::min(batch, n_genes - q0);
-        const size_t rows = static_cast<size_t>(nq) * static_cast<size_t>(S);
-        REO_HIP_CHECK(hipMemcpyAsync(d_genes.p, genes + q0, static_cast<size_t>(nq) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        if ((rc = launch_sample_counts(c, d_genes.p, nq, maskbits, class_mask, c->sc_slot2col.p, d_sel.p, d_gt.p, n_eq ? d_eq.p : nullptr))) return rc;
-        REO_HIP_CHECK(hipMemcpyAsync(n_gt + static_cast<size_t>(q0) * S, d_gt.p, rows * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        if (n_eq) REO_HIP_CHECK(hipMemcpyAsync(n_eq + static_cast<size_t>(q0) * S, d_eq.p, rows * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        if (n_sel) REO_HIP_CHECK(hipMemcpyAsync(n_sel + q0, d_sel.p, static_cast<size_t>(nq) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        if ((rc = wait_or_drop_table(c))) return rc;   // the next batch reuses the buffers
-    }
-    drain.dismiss();
-    return REO_OK;
-}
-
-// Up or down in one sample (include/reo_hip.h): the queries in batches; per batch two launches of the counting kernel of reo_sample_counts
-// (class masks 0x1C0 and 0x007, with tied counts) into device buffers that stay there, one launch of k_sample_fisher (sampletests.hip)
-// over them, and the copies of the batch's rows into the caller's arrays.  Reads the class table, the bit planes and a reference mask
-// slot; writes none of them.
-int32_t reo_sample_tests(reo_ctx *c, const int32_t *genes, int64_t n_genes, const uint8_t *partner_mask, int32_t *n_above_ctrl,
-                         int32_t *n_below_ctrl, int32_t *rev_up, int32_t *rev_down, int32_t *tied, double *p_up, double *p_down)
-{
-    int32_t rc = no_multi(c, "reo_sample_tests");
-    if (rc || (rc = use(c))) return rc;
-    if ((rc = need_complete_table(c))) return rc;
-    char msg[320];
-    if (sample_tests_check_args(c->G, genes, n_genes, p_up, p_down, msg, sizeof msg)) { set_error("%s", msg); return REO_EINVAL; }
-    if (!partner_mask && c->ref_slot < 0) {
-        set_error("reo_sample_tests: partner_mask is null and there is no reference set to take its place: %s", c->ref_gone);
-        return REO_EINVAL;
-    }
-    if ((rc = ensure_transform(c))) return rc;   // (in place whenever there is a class table: nothing runs)
-    std::vector<int32_t> map;
-    if (!sc_slot_map(c->group_id.data(), c->S, c->ngroups, map) || c->goff32.empty() || static_cast<int64_t>(map.size()) != c->goff32.back()) {
-        set_error("reo_sample_tests: the sample slots of the bit planes do not match the group labels");
-        return REO_EHIP;
-    }
-    const int64_t S = c->S, slots = static_cast<int64_t>(map.size());
-    const char *env = getenv("REO_SAMPLE_TESTS_BATCH");
-    const int64_t batch = st_batch_rows(n_genes, slots, env ? atoll(env) : 0);
-    const size_t nb = static_cast<size_t>(batch), cells = nb * static_cast<size_t>(S);
-    const int64_t lf_entries = st_lf_entries(c->G);
-    DevBuf<int32_t> d_genes, d_sel_a, d_sel_b, d_gt_a, d_eq_a, d_gt_b, d_eq_b, d_rev_up, d_rev_down, d_tied, d_flag;
-    DevBuf<double> d_p_up, d_p_down;
-    DevBuf<uint8_t> d_maskbytes;
-    DevBuf<uint32_t> d_maskbits;
-    if ((rc = d_genes.ensure(nb)) || (rc = d_sel_a.ensure(nb)) || (rc = d_sel_b.ensure(nb)) || (rc = d_gt_a.ensure(nb * slots)) ||
-        (rc = d_eq_a.ensure(nb * slots)) || (rc = d_gt_b.ensure(nb * slots)) || (rc = d_eq_b.ensure(nb * slots)) ||
-        (rev_up && (rc = d_rev_up.ensure(cells))) || (rev_down && (rc = d_rev_down.ensure(cells))) || (tied && (rc = d_tied.ensure(cells))) ||
-        (rc = d_p_up.ensure(cells)) || (rc = d_p_down.ensure(cells)) || (rc = d_flag.ensure(1)) || (rc = c->sc_slot2col.ensure(map.size())) ||
-        (rc = c->st_lf.ensure(static_cast<size_t>(lf_entries))))
-        return rc;
-    const uint32_t *maskbits = nullptr;
-    if (partner_mask) {
-        if ((rc = d_maskbytes.ensure(c->Gp)) || (rc = d_maskbits.ensure(c->Wp))) return rc;
-        maskbits = d_maskbits.p;
-    } else {
-        maskbits = c->refbits[c->ref_slot].p;
-    }
-    std::vector<double> lf;
-    int32_t flag = 0;
-    DrainOnExit drain(c);   // genes, partner_mask and lf in, the results out (declared after the buffers: the wait comes before their release)
-    if (c->st_lf_G != c->G) {   // once per context and gene count
-        st_build_lf(c->G, lf);
-        c->st_lf_G = -1;
-        REO_HIP_CHECK(hipMemcpyAsync(c->st_lf.p, lf.data(), lf.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        REO_HIP_CHECK(hipStreamSynchronize(c->stream));   // (lf is a local)
-        c->st_lf_G = c->G;
-    }
-    if ((rc = upload_slot2col(c, map))) return rc;
-    if (partner_mask) {
-        REO_HIP_CHECK(hipMemsetAsync(d_maskbytes.p, 0, c->Gp, c->stream));
-        REO_HIP_CHECK(hipMemcpyAsync(d_maskbytes.p, partner_mask, static_cast<size_t>(c->G), hipMemcpyHostToDevice, c->stream));
-        if ((rc = launch_pack_ref(c, d_maskbytes.p, d_maskbits.p))) return rc;
-    }
-    REO_HIP_CHECK(hipMemsetAsync(d_flag.p, 0, sizeof(int32_t), c->stream));
-    for (int64_t q0 = 0; q0 < n_genes; q0 += batch) {
-        const int64_t nq = std::min(batch, n_genes - q0);
-        const size_t rows = static_cast<size_t>(nq) * static_cast<size_t>(S), at = static_cast<size_t>(q0) * S;
-        REO_HIP_CHECK(hipMemcpyAsync(d_genes.p, genes + q0, static_cast<size_t>(nq) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        if ((rc = launch_sample_counts(c, d_genes.p, nq, maskbits, kStMaskAbove, c->sc_slot2col.p, d_sel_a.p, d_gt_a.p, d_eq_a.p)) ||
-            (rc = launch_sample_counts(c, d_genes.p, nq, maskbits, kStMaskBelow, c->sc_slot2col.p, d_sel_b.p, d_gt_b.p, d_eq_b.p)) ||
-            (rc = launch_sample_fisher(c, nq, d_sel_a.p, d_sel_b.p, d_gt_a.p, d_eq_a.p, d_gt_b.p, d_eq_b.p, c->st_lf.p, lf_entries,
-                                       rev_up ? d_rev_up.p : nullptr, rev_down ? d_rev_down.p : nullptr, tied ? d_tied.p : nullptr, d_p_up.p,
-                                       d_p_down.p, d_flag.p)))
-            return rc;
-        if (n_above_ctrl) REO_HIP_CHECK(hipMemcpyAsync(n_above_ctrl + q0, d_sel_a.p, static_cast<size_t>(nq) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        if (n_below_ctrl) REO_HIP_CHECK(hipMemcpyAsync(n_below_ctrl + q0, d_sel_b.p, static_cast<size_t>(nq) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        if (rev_up) REO_HIP_CHECK(hipMemcpyAsync(rev_up + at, d_rev_up.p, rows * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        if (rev_down) REO_HIP_CHECK(hipMemcpyAsync(rev_down + at, d_rev_down.p, rows * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        if (tied) REO_HIP_CHECK(hipMemcpyAsync(tied + at, d_tied.p, rows * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        REO_HIP_CHECK(hipMemcpyAsync(p_up + at, d_p_up.p, rows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        REO_HIP_CHECK(hipMemcpyAsync(p_down + at, d_p_down.p, rows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        REO_HIP_CHECK(hipMemcpyAsync(&flag, d_flag.p, sizeof flag, hipMemcpyDeviceToHost, c->stream));
-        if ((rc = wait_or_drop_table(c))) return rc;   // the next batch reuses the buffers
-        if (flag) {
-            set_error("reo_sample_tests: the counting kernel delivered counts that %lld genes cannot produce; the results are not valid", (long long)c->G);
-            return REO_EHIP;
-        }
-    }
-    drain.dismiss();
-    return REO_OK;
-}
-
-// How strongly (include/reo_hip.h): every check on the host first (pair_support.h), then the entries in batches whose count buffers and
-// outcome buffer stay under the budget; per batch the work items and the partners go up, one launch, and the batch's rows come back into
-// the caller's arrays.  Reads the bit planes of the transform and nothing of the class table or the iteration; writes none of them.
-int32_t reo_pair_support(reo_ctx *c, const int32_t *genes, int64_t n_genes, const int64_t *rowptr, const int32_t *partner, int32_t *n_gt,
-                         int32_t *n_eq, uint8_t *outcome)
-{
-    int32_t rc = no_multi(c, "reo_pair_support");
-    if (rc || (rc = use(c))) return rc;
-    if (c->dtype == 0 || c->group_id.empty() || static_cast<int64_t>(c->group_id.size()) != c->S) return ensure_transform(c);   // (its refusals: nothing runs)
-    char msg[320];
-    if (pair_support_check_args(c->G, genes, n_genes, rowptr, partner, n_gt, msg, sizeof msg)) { set_error("%s", msg); return REO_EINVAL; }
-    const int64_t total = rowptr[n_genes];
-    if (total == 0) return REO_OK;   // nothing listed: no transform, no launch
-    if ((rc = ensure_transform(c))) return rc;
-    const int64_t S = c->S, ng = c->ngroups;
-    std::vector<int32_t> map;
-    if (outcome && (!sc_slot_map(c->group_id.data(), S, c->ngroups, map) || c->goff32.empty() || static_cast<int64_t>(map.size()) != c->goff32.back())) {
-        set_error("reo_pair_support: the sample slots of the bit planes do not match the group labels");
-        return REO_EHIP;
-    }
-    const char *env = getenv("REO_PAIR_SUPPORT_BATCH");
-    const int64_t batch = ps_batch_entries(total, ng, S, outcome != nullptr, env ? atoll(env) : 0);
-    const size_t nb = static_cast<size_t>(batch);
-    DevBuf<PsItem> d_items;
-    DevBuf<int32_t> d_partner, d_gt, d_eq;
-    DevBuf<uint8_t> d_out;
-    if ((rc = d_items.ensure(nb)) || (rc = d_partner.ensure(nb)) || (rc = d_gt.ensure(nb * ng)) || (n_eq && (rc = d_eq.ensure(nb * ng))) ||
-        (outcome && ((rc = d_out.ensure(nb * static_cast<size_t>(S))) || (rc = c->sc_slot2col.ensure(map.size())))))
-        return rc;
-    std::vector<PsItem> items;
-    DrainOnExit drain(c);   // items and partners in, counts and outcomes out (declared after the buffers: the wait comes before their release)
-    if (outcome && (rc = upload_slot2col(c, map))) return rc;
-    int64_t row = 0;
-    for (int64_t e0 = 0; e0 < total; e0 += batch) {
-        const int64_t ne = std::min(batch, total - e0);
-        ps_build_items(genes, rowptr, n_genes, e0, e0 + ne, &row, items);
-        if (items.empty() || static_cast<int64_t>(items.size()) > ne) { set_error("reo_pair_support: %zu work items for %lld entries", items.size(), (long long)ne); return REO_EHIP; }
-        const size_t n = static_cast<size_t>(ne);
-        REO_HIP_CHECK(hipMemcpyAsync(d_items.p, items.data(), items.size() * sizeof(PsItem), hipMemcpyHostToDevice, c->stream));
-        REO_HIP_CHECK(hipMemcpyAsync(d_partner.p, partner + e0, n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        if ((rc = launch_pair_support(c, d_items.p, static_cast<int64_t>(items.size()), d_partner.p, outcome ? c->sc_slot2col.p : nullptr, d_gt.p,
-                                      n_eq ? d_eq.p : nullptr, outcome ? d_out.p : nullptr)))
-            return rc;
-        REO_HIP_CHECK(hipMemcpyAsync(n_gt + static_cast<size_t>(e0) * ng, d_gt.p, n * ng * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        if (n_eq) REO_HIP_CHECK(hipMemcpyAsync(n_eq + static_cast<size_t>(e0) * ng, d_eq.p, n * ng * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        if (outcome) REO_HIP_CHECK(hipMemcpyAsync(outcome + static_cast<size_t>(e0) * S, d_out.p, n * static_cast<size_t>(S), hipMemcpyDeviceToHost, c->stream));
-        if ((rc = wait_or_drop_table(c))) return rc;   // the next batch reuses the buffers and the item list
-    }
-    drain.dismiss();
     return REO_OK;
 }
 

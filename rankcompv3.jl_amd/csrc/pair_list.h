@@ -55,6 +55,26 @@ REO_PL_FN uint32_t pair_code_at(uint32_t cl, uint32_t ch, uint32_t tl, uint32_t 
     return 3u * ic + it;
 }
 
+// Two checks that every query entry point makes (reo_pair_list, reo_sample_counts, reo_sample_tests, reo_pair_support) with its own name
+// `what` in front: true when in order, otherwise false and the message in msg.  genes is a HOST array (null or n_genes < 1: nothing to check).
+inline bool query_genes_in_range(const char *what, int64_t G, const int32_t *genes, int64_t n_genes, char *msg, size_t msg_n)
+{
+    for (int64_t q = 0; genes && q < n_genes; ++q)
+        if (genes[q] < 0 || genes[q] >= G) {
+            snprintf(msg, msg_n, "%s: genes[%lld] = %d is outside [0, %lld)", what, (long long)q, genes[q], (long long)G);
+            return false;
+        }
+    return true;
+}
+
+inline bool query_class_mask_ok(const char *what, uint32_t class_mask, char *msg, size_t msg_n)
+{
+    if (class_mask != 0 && !(class_mask & ~kPairClassAll)) return true;
+    snprintf(msg, msg_n, "%s: class_mask 0x%X selects %s (bit c selects class code c = 3*(ic-1)+(it-1), c in 0..8: 0x1 .. 0x1FF)", what, class_mask,
+             class_mask == 0 ? "no class" : "bits above 8");
+    return false;
+}
+
 // Argument checks of reo_pair_list that need neither the context's state nor the GPU.  0 when everything is in order; otherwise the number
 // of the failed check (1 ..) and its message in msg.  genes is a HOST array.
 inline int pair_list_check_args(int64_t G, const int32_t *genes, int64_t n_genes, uint32_t class_mask, const int64_t *rowptr,
@@ -62,11 +82,7 @@ inline int pair_list_check_args(int64_t G, const int32_t *genes, int64_t n_genes
 {
     if (!genes || !rowptr) { snprintf(msg, msg_n, "reo_pair_list: genes and rowptr must not be null"); return 1; }
     if (n_genes < 1) { snprintf(msg, msg_n, "reo_pair_list: n_genes = %lld, at least one query gene is needed", (long long)n_genes); return 2; }
-    if (class_mask == 0 || (class_mask & ~kPairClassAll)) {
-        snprintf(msg, msg_n, "reo_pair_list: class_mask 0x%X selects %s (bit c selects class code c = 3*(ic-1)+(it-1), c in 0..8: 0x1 .. 0x1FF)",
-                 class_mask, class_mask == 0 ? "no class" : "bits above 8");
-        return 3;
-    }
+    if (!query_class_mask_ok("reo_pair_list", class_mask, msg, msg_n)) return 3;
     if ((partner == nullptr) != (code == nullptr)) {
         snprintf(msg, msg_n, "reo_pair_list: partner and code are both given, or both null (count only)");
         return 4;
@@ -75,12 +91,7 @@ inline int pair_list_check_args(int64_t G, const int32_t *genes, int64_t n_genes
         snprintf(msg, msg_n, "reo_pair_list: capacity %lld (it counts the entries of partner and code; 0 when they are null)", (long long)capacity);
         return 5;
     }
-    for (int64_t q = 0; q < n_genes; ++q)
-        if (genes[q] < 0 || genes[q] >= G) {
-            snprintf(msg, msg_n, "reo_pair_list: genes[%lld] = %d is outside [0, %lld)", (long long)q, genes[q], (long long)G);
-            return 6;
-        }
-    return 0;
+    return query_genes_in_range("reo_pair_list", G, genes, n_genes, msg, msg_n) ? 0 : 6;
 }
 
 // rowptr from the per-query counts (64-bit prefix sums); returns the total.

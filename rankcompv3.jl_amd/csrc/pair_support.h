@@ -5,7 +5,7 @@
 // stands for, and the argument checks -- all of which run on the host before anything is uploaded.  No HIP header in here: plain C++17 (the
 // kernel's unit defines the function attributes through pair_list.h).
 //
-// The comparison itself is the borrow chain of k1_counts over the pos / lo / hi planes (kernels.hip); it yields, for one pair and one block of
+// The comparison itself is the borrow chain of k1_counts over the pos / lo / hi planes (band_chain.h); it yields, for one pair and one block of
 // 32 sample slots, a word `lt` (bit s: x_i > x_j and not tied in slot s) and a word `le` (bit s: greater or tied).
 #pragma once
 
@@ -84,11 +84,7 @@ inline int pair_support_check_args(int64_t G, const int32_t *genes, int64_t n_ge
         snprintf(msg, msg_n, "reo_pair_support: n_genes = %lld, between 1 and 2^30 rows per call", (long long)n_genes);
         return 2;
     }
-    for (int64_t q = 0; q < n_genes; ++q)
-        if (genes[q] < 0 || genes[q] >= G) {
-            snprintf(msg, msg_n, "reo_pair_support: genes[%lld] = %d is outside [0, %lld)", (long long)q, genes[q], (long long)G);
-            return 3;
-        }
+    if (!query_genes_in_range("reo_pair_support", G, genes, n_genes, msg, msg_n)) return 3;
     if (rowptr[0] != 0) { snprintf(msg, msg_n, "reo_pair_support: rowptr[0] = %lld, a CSR starts at 0", (long long)rowptr[0]); return 4; }
     for (int64_t q = 0; q < n_genes; ++q)
         if (rowptr[q + 1] < rowptr[q]) {

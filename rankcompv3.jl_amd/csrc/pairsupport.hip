@@ -4,7 +4,7 @@
 //   k_pair_support<BIG, WITH_EQ, WITH_OUTCOME>   one wave per work item (pair_support.h: at most 64 consecutive entries of one row), four
 //     waves per workgroup, one lane per entry.  The wave walks the groups and, within a group, its blocks of 32 sample slots: the band edges
 //     lo_i / hi_i of the block are wave-uniform (the item's gene), a lane loads the pos planes of its own partner and runs the borrow chain
-//     of k1_counts (bitop3 0x8e over plane_bits(G) planes); popcount(lt) / popcount(le) go into two registers, stored at the group's end
+//     of band_chain.h over plane_bits(G) planes; popcount(lt) / popcount(le) go into two registers, stored at the group's end
 //     (n_eq = le - lt).  Padding slots read as zero in the planes (transform.hip): the counts need no mask word.
 //     WITH_OUTCOME: the lane expands lt / le of the block into bytes at outcome[e * S + slot2col[slot]] for the slots with a column in
 //     [0, S); padding slots are never written.  These byte stores are NOT coalesced across lanes (a lane walks its own row of S bytes):
@@ -15,6 +15,7 @@
 // are bounded by the counts the host passes; lanes past the item's count load the planes of the item's own gene and store nothing.
 #include "pair_support.h"
 #include "reo_internal.h"
+#include "band_chain.h"
 
 namespace reo {
 
@@ -37,7 +38,7 @@ __global__ __launch_bounds__(kPsThreads) void k_pair_support(const PsItem *__res
                                                              const uint4 *__restrict__ AH, int32_t *__restrict__ out_gt,
                                                              int32_t *__restrict__ out_eq, uint8_t *__restrict__ outcome, PsArgs a)
 {
-    constexpr int NQ = BIG ? 5 : 4, EQ = BIG ? 8 : 4;   // uint4 per gene and block: pos planes, edge row
+    constexpr int NQ = BandLayout<BIG>::NQ, EQ = BandLayout<BIG>::EQ;   // uint4 per gene and block: pos planes, edge row
     constexpr bool LE = WITH_EQ || WITH_OUTCOME;
     const int lane = threadIdx.x & (kPsLanes - 1);
     const int item = static_cast<int>(blockIdx.x) * kPsWaves + __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);
@@ -57,20 +58,15 @@ __global__ __launch_bounds__(kPsThreads) void k_pair_support(const PsItem *__res
             const uint4 *pb = P + static_cast<size_t>(b) * NQ * a.Gp + j;
 #pragma unroll
             for (int q = 0; q < NQ; ++q) {
-                const uint4 v = al[q];
-                lo[4 * q] = v.x; lo[4 * q + 1] = v.y; lo[4 * q + 2] = v.z; lo[4 * q + 3] = v.w;
-                if constexpr (LE) {
-                    const uint4 h = ah[q];
-                    hi[4 * q] = h.x; hi[4 * q + 1] = h.y; hi[4 * q + 2] = h.z; hi[4 * q + 3] = h.w;
-                }
-                const uint4 w = pb[static_cast<size_t>(q) * a.Gp];
-                p[4 * q] = w.x; p[4 * q + 1] = w.y; p[4 * q + 2] = w.z; p[4 * q + 3] = w.w;
+                band_unpack(al[q], lo, q);
+                if constexpr (LE) band_unpack(ah[q], hi, q);
+                band_unpack(pb[static_cast<size_t>(q) * a.Gp], p, q);
             }
             uint32_t lt = 0, le = 0;
 #pragma unroll
             for (int k = 0; k < 4 * NQ; ++k) {
                 if (k >= a.nbits) continue;   // (a guard per plane, not a break: the trip count stays constant and every p[k] a fixed register)
-                const int ew = BIG ? k : ((k + 15) & 15);   // the 16-plane layout keeps plane k of an edge in word (k + 15) % 16
+                const int ew = BandLayout<BIG>::edge_word(k);
                 lt = __builtin_amdgcn_bitop3_b32(p[k], lo[ew], lt, 0x8e);
                 if constexpr (LE) le = __builtin_amdgcn_bitop3_b32(p[k], hi[ew], le, 0x8e);
             }

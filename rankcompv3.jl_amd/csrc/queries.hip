@@ -1,0 +1,281 @@
+// The query entry points of the C ABI (include/reo_hip.h): reo_pair_list, reo_sample_counts, reo_sample_tests, reo_pair_support.  Host code
+// only; the kernels are in pairlist.hip, samplecounts.hip, sampletests.hip and pairsupport.hip.  What the four share stands once, in front.
+#include <algorithm>
+#include <cstdlib>
+
+#include "pair_list.h"
+#include "reo_internal.h"
+#include "sample_counts.h"
+#include "sample_tests.h"
+#include "pair_support.h"
+
+namespace reo {
+namespace {
+
+// How every query begins: one GPU, a usable context and, for the three that read it, a whole class table.
+int32_t begin_query(reo_ctx *c, const char *what, bool need_table)
+{
+    int32_t rc = no_multi(c, what);
+    if (rc || (rc = use(c))) return rc;
+    return need_table ? need_complete_table(c) : REO_OK;
+}
+
+// A null partner_mask stands for the reference set of the last reo_identify_degs: there must be one.
+int32_t need_partner_set(reo_ctx *c, const char *what, const uint8_t *partner_mask)
+{
+    if (partner_mask || c->ref_slot >= 0) return REO_OK;
+    set_error("%s: partner_mask is null and there is no reference set to take its place: %s", what, c->ref_gone);
+    return REO_EINVAL;
+}
+
+// The partner mask as bits on the device: the caller's bytes packed into buffers of the call, or the resident reference set.  Declared in
+// FRONT of the call's DrainOnExit, like every other device buffer of a call: the wait comes before their release.
+struct PartnerMask {
+    DevBuf<uint8_t> bytes;
+    DevBuf<uint32_t> packed;
+    const uint32_t *bits = nullptr;   // what the kernels read (after prepare)
+    int32_t prepare(reo_ctx *c, const uint8_t *partner_mask)   // behind need_partner_set: a null mask indexes refbits with ref_slot >= 0
+    {
+        int32_t rc;
+        if (!partner_mask) { bits = c->refbits[c->ref_slot].p; return REO_OK; }
+        if ((rc = bytes.ensure(c->Gp)) || (rc = packed.ensure(c->Wp))) return rc;
+        bits = packed.p;
+        return REO_OK;
+    }
+    int32_t upload(reo_ctx *c, const uint8_t *partner_mask)   // on the stream; nothing to do for the reference set
+    {
+        if (!partner_mask) return REO_OK;
+        REO_HIP_CHECK(hipMemsetAsync(bytes.p, 0, c->Gp, c->stream));
+        REO_HIP_CHECK(hipMemcpyAsync(bytes.p, partner_mask, static_cast<size_t>(c->G), hipMemcpyHostToDevice, c->stream));
+        return launch_pack_ref(c, bytes.p, packed.p);
+    }
+};
+
+// The caller's column of every sample slot, from the group labels the transform laid the slots out by.
+int32_t query_slot_map(reo_ctx *c, const char *what, std::vector<int32_t> &map)
+{
+    if (sc_slot_map(c->group_id.data(), c->S, c->ngroups, map) && !c->goff32.empty() && static_cast<int64_t>(map.size()) == c->goff32.back())
+        return REO_OK;
+    set_error("%s: the sample slots of the bit planes do not match the group labels", what);
+    return REO_EHIP;
+}
+
+// REO_*_BATCH (tests): a batch size that can only lower the budget's; 0 when unset.
+int64_t env_batch(const char *name) { const char *env = getenv(name); return env ? atoll(env) : 0; }
+
+// n elements from the device into host[at ..], on the stream; a null host array is one the caller did not ask for.
+template <class T>
+int32_t copy_back(reo_ctx *c, T *host, size_t at, const T *dev, size_t n)
+{
+    if (host) REO_HIP_CHECK(hipMemcpyAsync(host + at, dev, n * sizeof(T), hipMemcpyDeviceToHost, c->stream));
+    return REO_OK;
+}
+
+}  // namespace
+}  // namespace reo
+
+using namespace reo;
+
+extern "C" {
+
+// The partners behind the tallies (include/reo_hip.h): count on the device, prefix sums on the host (the caller wants rowptr anyway), fill on
+// the device into buffers sized from the counted total.
+int32_t reo_pair_list(reo_ctx *c, const int32_t *genes, int64_t n_genes, const uint8_t *partner_mask, uint32_t class_mask, int64_t *rowptr,
+                      int32_t *partner, uint8_t *code, int64_t capacity)
+{
+    int32_t rc = begin_query(c, "reo_pair_list", true);
+    if (rc) return rc;
+    char msg[320];
+    if (pair_list_check_args(c->G, genes, n_genes, class_mask, rowptr, partner, code, capacity, msg, sizeof msg)) { set_error("%s", msg); return REO_EINVAL; }
+    if ((rc = need_partner_set(c, "reo_pair_list", partner_mask))) return rc;
+    const size_t n = static_cast<size_t>(n_genes);
+    DevBuf<int32_t> d_genes, d_count, d_partner, d_flag;
+    DevBuf<int64_t> d_rowptr;
+    DevBuf<uint8_t> d_code;
+    PartnerMask mask;
+    if ((rc = d_genes.ensure(n)) || (rc = d_count.ensure(n)) || (rc = mask.prepare(c, partner_mask))) return rc;
+    std::vector<int32_t> count(n);
+    int32_t flag = 0;
+    DrainOnExit drain(c);   // genes and partner_mask in, partner and code out (declared after the buffers: the wait comes before their release)
+    REO_HIP_CHECK(hipMemcpyAsync(d_genes.p, genes, n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    if ((rc = mask.upload(c, partner_mask))) return rc;
+    if ((rc = launch_pair_count(c, d_genes.p, n_genes, mask.bits, class_mask, d_count.p))) return rc;
+    REO_HIP_CHECK(hipMemcpyAsync(count.data(), d_count.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = wait_or_drop_table(c))) return rc;
+    for (size_t q = 0; q < n; ++q)
+        if (count[q] < 0 || count[q] >= c->G) { set_error("reo_pair_list: the count of query %zu reads %d with %lld genes", q, count[q], (long long)c->G); return REO_EHIP; }
+    const int64_t total = pair_list_rowptr(count.data(), n_genes, rowptr);
+    if (!partner || total == 0) { drain.dismiss(); return REO_OK; }
+    if (total > capacity) {
+        set_error("reo_pair_list: the lists hold %lld entries, capacity is %lld (rowptr has been filled: allocate rowptr[n_genes] entries)",
+                  (long long)total, (long long)capacity);
+        return REO_EINVAL;
+    }
+    const size_t nt = static_cast<size_t>(total);
+    if ((rc = d_rowptr.ensure(n + 1)) || (rc = d_partner.ensure(nt)) || (rc = d_code.ensure(nt)) || (rc = d_flag.ensure(1))) return rc;
+    REO_HIP_CHECK(hipMemcpyAsync(d_rowptr.p, rowptr, (n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    REO_HIP_CHECK(hipMemsetAsync(d_flag.p, 0, sizeof(int32_t), c->stream));
+    if ((rc = launch_pair_fill(c, d_genes.p, n_genes, mask.bits, class_mask, d_rowptr.p, d_partner.p, d_code.p, total, d_flag.p))) return rc;
+    if ((rc = copy_back(c, partner, 0, d_partner.p, nt)) || (rc = copy_back(c, code, 0, d_code.p, nt)) || (rc = copy_back(c, &flag, 0, d_flag.p, 1)))
+        return rc;
+    if ((rc = wait_or_drop_table(c))) return rc;
+    drain.dismiss();
+    if (flag) {
+        set_error("reo_pair_list: the fill pass found another number of pairs in a row than the count pass (the class table changed between them?); "
+                  "the lists are not valid");
+        return REO_EHIP;
+    }
+    return REO_OK;
+}
+
+// In which samples (include/reo_hip.h): the queries in batches whose two count buffers stay under the budget of sample_counts.h; per batch one
+// launch and the copies of its rows into the caller's arrays.  Reads the class table, the bit planes and a reference mask slot; writes none of them.
+int32_t reo_sample_counts(reo_ctx *c, const int32_t *genes, int64_t n_genes, const uint8_t *partner_mask, uint32_t class_mask, int32_t *n_sel,
+                          int32_t *n_gt, int32_t *n_eq)
+{
+    int32_t rc = begin_query(c, "reo_sample_counts", true);
+    if (rc) return rc;
+    char msg[320];
+    if (sample_counts_check_args(c->G, genes, n_genes, class_mask, n_gt, msg, sizeof msg)) { set_error("%s", msg); return REO_EINVAL; }
+    if ((rc = need_partner_set(c, "reo_sample_counts", partner_mask))) return rc;
+    if ((rc = ensure_transform(c))) return rc;   // (in place whenever there is a class table: nothing runs)
+    std::vector<int32_t> map;
+    if ((rc = query_slot_map(c, "reo_sample_counts", map))) return rc;
+    const size_t S = static_cast<size_t>(c->S), slots = map.size();
+    const int64_t batch = sc_batch_rows(n_genes, static_cast<int64_t>(slots), env_batch("REO_SAMPLE_COUNTS_BATCH"));
+    const size_t nb = static_cast<size_t>(batch);
+    DevBuf<int32_t> d_genes, d_sel, d_gt, d_eq;
+    PartnerMask mask;
+    if ((rc = d_genes.ensure(nb)) || (rc = d_sel.ensure(nb)) || (rc = d_gt.ensure(nb * slots)) || (n_eq && (rc = d_eq.ensure(nb * slots))) ||
+        (rc = c->sc_slot2col.ensure(slots)) || (rc = mask.prepare(c, partner_mask)))
+        return rc;
+    DrainOnExit drain(c);   // genes and partner_mask in, the counts out (declared after the buffers: the wait comes before their release)
+    if ((rc = upload_slot2col(c, map)) || (rc = mask.upload(c, partner_mask))) return rc;
+    for (int64_t q0 = 0; q0 < n_genes; q0 += batch) {
+        const int64_t nq = std::min(batch, n_genes - q0);
+        const size_t at = static_cast<size_t>(q0), nrow = static_cast<size_t>(nq);
+        REO_HIP_CHECK(hipMemcpyAsync(d_genes.p, genes + q0, nrow * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        if ((rc = launch_sample_counts(c, d_genes.p, nq, mask.bits, class_mask, c->sc_slot2col.p, d_sel.p, d_gt.p, n_eq ? d_eq.p : nullptr))) return rc;
+        if ((rc = copy_back(c, n_gt, at * S, d_gt.p, nrow * S)) || (rc = copy_back(c, n_eq, at * S, d_eq.p, nrow * S)) ||
+            (rc = copy_back(c, n_sel, at, d_sel.p, nrow)))
+            return rc;
+        if ((rc = wait_or_drop_table(c))) return rc;   // the next batch reuses the buffers
+    }
+    drain.dismiss();
+    return REO_OK;
+}
+
+// Up or down in one sample (include/reo_hip.h): the queries in batches; per batch two launches of the counting kernel of reo_sample_counts
+// (class masks 0x1C0 and 0x007, with tied counts) into device buffers that stay there, one launch of k_sample_fisher (sampletests.hip)
+// over them, and the copies of the batch's rows into the caller's arrays.  Reads the class table, the bit planes and a reference mask
+// slot; writes none of them.
+int32_t reo_sample_tests(reo_ctx *c, const int32_t *genes, int64_t n_genes, const uint8_t *partner_mask, int32_t *n_above_ctrl,
+                         int32_t *n_below_ctrl, int32_t *rev_up, int32_t *rev_down, int32_t *tied, double *p_up, double *p_down)
+{
+    int32_t rc = begin_query(c, "reo_sample_tests", true);
+    if (rc) return rc;
+    char msg[320];
+    if (sample_tests_check_args(c->G, genes, n_genes, p_up, p_down, msg, sizeof msg)) { set_error("%s", msg); return REO_EINVAL; }
+    if ((rc = need_partner_set(c, "reo_sample_tests", partner_mask))) return rc;
+    if ((rc = ensure_transform(c))) return rc;   // (in place whenever there is a class table: nothing runs)
+    std::vector<int32_t> map;
+    if ((rc = query_slot_map(c, "reo_sample_tests", map))) return rc;
+    const size_t S = static_cast<size_t>(c->S), slots = map.size();
+    const int64_t batch = st_batch_rows(n_genes, static_cast<int64_t>(slots), env_batch("REO_SAMPLE_TESTS_BATCH"));
+    const size_t nb = static_cast<size_t>(batch), cells = nb * S;
+    const int64_t lf_entries = st_lf_entries(c->G);
+    DevBuf<int32_t> d_genes, d_sel_a, d_sel_b, d_gt_a, d_eq_a, d_gt_b, d_eq_b, d_rev_up, d_rev_down, d_tied, d_flag;
+    DevBuf<double> d_p_up, d_p_down;
+    PartnerMask mask;
+    if ((rc = d_genes.ensure(nb)) || (rc = d_sel_a.ensure(nb)) || (rc = d_sel_b.ensure(nb)) || (rc = d_gt_a.ensure(nb * slots)) ||
+        (rc = d_eq_a.ensure(nb * slots)) || (rc = d_gt_b.ensure(nb * slots)) || (rc = d_eq_b.ensure(nb * slots)) ||
+        (rev_up && (rc = d_rev_up.ensure(cells))) || (rev_down && (rc = d_rev_down.ensure(cells))) || (tied && (rc = d_tied.ensure(cells))) ||
+        (rc = d_p_up.ensure(cells)) || (rc = d_p_down.ensure(cells)) || (rc = d_flag.ensure(1)) || (rc = c->sc_slot2col.ensure(slots)) ||
+        (rc = c->st_lf.ensure(static_cast<size_t>(lf_entries))) || (rc = mask.prepare(c, partner_mask)))
+        return rc;
+    std::vector<double> lf;
+    int32_t flag = 0;
+    DrainOnExit drain(c);   // genes, partner_mask and lf in, the results out (declared after the buffers: the wait comes before their release)
+    if (c->st_lf_G != c->G) {   // once per context and gene count
+        st_build_lf(c->G, lf);
+        c->st_lf_G = -1;
+        REO_HIP_CHECK(hipMemcpyAsync(c->st_lf.p, lf.data(), lf.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        REO_HIP_CHECK(hipStreamSynchronize(c->stream));   // (lf is a local)
+        c->st_lf_G = c->G;
+    }
+    if ((rc = upload_slot2col(c, map)) || (rc = mask.upload(c, partner_mask))) return rc;
+    REO_HIP_CHECK(hipMemsetAsync(d_flag.p, 0, sizeof(int32_t), c->stream));
+    for (int64_t q0 = 0; q0 < n_genes; q0 += batch) {
+        const int64_t nq = std::min(batch, n_genes - q0);
+        const size_t at = static_cast<size_t>(q0), nrow = static_cast<size_t>(nq);
+        REO_HIP_CHECK(hipMemcpyAsync(d_genes.p, genes + q0, nrow * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        if ((rc = launch_sample_counts(c, d_genes.p, nq, mask.bits, kStMaskAbove, c->sc_slot2col.p, d_sel_a.p, d_gt_a.p, d_eq_a.p)) ||
+            (rc = launch_sample_counts(c, d_genes.p, nq, mask.bits, kStMaskBelow, c->sc_slot2col.p, d_sel_b.p, d_gt_b.p, d_eq_b.p)) ||
+            (rc = launch_sample_fisher(c, nq, d_sel_a.p, d_sel_b.p, d_gt_a.p, d_eq_a.p, d_gt_b.p, d_eq_b.p, c->st_lf.p, lf_entries,
+                                       rev_up ? d_rev_up.p : nullptr, rev_down ? d_rev_down.p : nullptr, tied ? d_tied.p : nullptr, d_p_up.p,
+                                       d_p_down.p, d_flag.p)))
+            return rc;
+        if ((rc = copy_back(c, n_above_ctrl, at, d_sel_a.p, nrow)) || (rc = copy_back(c, n_below_ctrl, at, d_sel_b.p, nrow)) ||
+            (rc = copy_back(c, rev_up, at * S, d_rev_up.p, nrow * S)) || (rc = copy_back(c, rev_down, at * S, d_rev_down.p, nrow * S)) ||
+            (rc = copy_back(c, tied, at * S, d_tied.p, nrow * S)) || (rc = copy_back(c, p_up, at * S, d_p_up.p, nrow * S)) ||
+            (rc = copy_back(c, p_down, at * S, d_p_down.p, nrow * S)) || (rc = copy_back(c, &flag, 0, d_flag.p, 1)))
+            return rc;
+        if ((rc = wait_or_drop_table(c))) return rc;   // the next batch reuses the buffers
+        if (flag) {
+            set_error("reo_sample_tests: the counting kernel delivered counts that %lld genes cannot produce; the results are not valid", (long long)c->G);
+            return REO_EHIP;
+        }
+    }
+    drain.dismiss();
+    return REO_OK;
+}
+
+// How strongly (include/reo_hip.h): every check on the host first (pair_support.h), then the entries in batches whose count buffers and
+// outcome buffer stay under the budget; per batch the work items and the partners go up, one launch, and the batch's rows come back into
+// the caller's arrays.  Reads the bit planes of the transform and nothing of the class table or the iteration; writes none of them.
+int32_t reo_pair_support(reo_ctx *c, const int32_t *genes, int64_t n_genes, const int64_t *rowptr, const int32_t *partner, int32_t *n_gt,
+                         int32_t *n_eq, uint8_t *outcome)
+{
+    int32_t rc = begin_query(c, "reo_pair_support", false);
+    if (rc) return rc;
+    if (c->dtype == 0 || c->group_id.empty() || static_cast<int64_t>(c->group_id.size()) != c->S) return ensure_transform(c);   // (its refusals: nothing runs)
+    char msg[320];
+    if (pair_support_check_args(c->G, genes, n_genes, rowptr, partner, n_gt, msg, sizeof msg)) { set_error("%s", msg); return REO_EINVAL; }
+    const int64_t total = rowptr[n_genes];
+    if (total == 0) return REO_OK;   // nothing listed: no transform, no launch
+    if ((rc = ensure_transform(c))) return rc;
+    const size_t S = static_cast<size_t>(c->S), ng = static_cast<size_t>(c->ngroups);
+    std::vector<int32_t> map;
+    if (outcome && (rc = query_slot_map(c, "reo_pair_support", map))) return rc;
+    const int64_t batch = ps_batch_entries(total, c->ngroups, c->S, outcome != nullptr, env_batch("REO_PAIR_SUPPORT_BATCH"));
+    const size_t nb = static_cast<size_t>(batch);
+    DevBuf<PsItem> d_items;
+    DevBuf<int32_t> d_partner, d_gt, d_eq;
+    DevBuf<uint8_t> d_out;
+    if ((rc = d_items.ensure(nb)) || (rc = d_partner.ensure(nb)) || (rc = d_gt.ensure(nb * ng)) || (n_eq && (rc = d_eq.ensure(nb * ng))) ||
+        (outcome && ((rc = d_out.ensure(nb * S)) || (rc = c->sc_slot2col.ensure(map.size())))))
+        return rc;
+    std::vector<PsItem> items;
+    DrainOnExit drain(c);   // items and partners in, counts and outcomes out (declared after the buffers: the wait comes before their release)
+    if (outcome && (rc = upload_slot2col(c, map))) return rc;
+    int64_t row = 0;
+    for (int64_t e0 = 0; e0 < total; e0 += batch) {
+        const int64_t ne = std::min(batch, total - e0);
+        ps_build_items(genes, rowptr, n_genes, e0, e0 + ne, &row, items);
+        if (items.empty() || static_cast<int64_t>(items.size()) > ne) { set_error("reo_pair_support: %zu work items for %lld entries", items.size(), (long long)ne); return REO_EHIP; }
+        const size_t at = static_cast<size_t>(e0), n = static_cast<size_t>(ne);
+        REO_HIP_CHECK(hipMemcpyAsync(d_items.p, items.data(), items.size() * sizeof(PsItem), hipMemcpyHostToDevice, c->stream));
+        REO_HIP_CHECK(hipMemcpyAsync(d_partner.p, partner + e0, n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        if ((rc = launch_pair_support(c, d_items.p, static_cast<int64_t>(items.size()), d_partner.p, outcome ? c->sc_slot2col.p : nullptr, d_gt.p,
+                                      n_eq ? d_eq.p : nullptr, outcome ? d_out.p : nullptr)))
+            return rc;
+        if ((rc = copy_back(c, n_gt, at * ng, d_gt.p, n * ng)) || (rc = copy_back(c, n_eq, at * ng, d_eq.p, n * ng)) ||
+            (rc = copy_back(c, outcome, at * S, d_out.p, n * S)))
+            return rc;
+        if ((rc = wait_or_drop_table(c))) return rc;   // the next batch reuses the buffers and the item list
+    }
+    drain.dismiss();
+    return REO_OK;
+}
+
+}  // extern "C"

@@ -474,4 +474,30 @@ void tic(reo_ctx *c, int slot);
 void toc(reo_ctx *c);
 void collect_timings(reo_ctx *c);
 
+// query prologue (api.hip): what the entry points of queries.hip share with the rest of the C ABI
+int32_t use(reo_ctx *c);                               // a context, and its device made current
+int32_t no_multi(reo_ctx *c, const char *what);        // `what` refuses a reo_create_multi context
+int32_t need_complete_table(reo_ctx *c);               // a class table, and every shard's part of it
+int32_t ensure_transform(reo_ctx *c);                  // matrix and groups set and of one size; the bit planes made if they are not in place
+int32_t wait_or_drop_table(reo_ctx *c);                // the stream wait of a call that may be the first to see a failed pair kernel
+// The slot -> column map of sc_slot_map (sample_counts.h) into c->sc_slot2col (already sized by the caller), on the stream
+int32_t upload_slot2col(reo_ctx *c, const std::vector<int32_t> &map);
+// Every call that enqueues an asynchronous copy from or into CALLER memory (or a local) holds one of these: whatever way the call
+// ends -- a failing REO_HIP_CHECK between the enqueue and the wait included -- the stream has been waited for before the caller
+// gets its arrays back (include/reo_hip.h: "no host pointer is retained after return").  A call that has done its own wait
+// dismisses the guard; the extra wait of an error path costs nothing that matters.
+struct DrainOnExit {
+    reo_ctx *c;
+    bool armed = true;
+    explicit DrainOnExit(reo_ctx *ctx) : c(ctx) {}
+    DrainOnExit(const DrainOnExit &) = delete;
+    DrainOnExit &operator=(const DrainOnExit &) = delete;
+    void dismiss() { armed = false; }
+    ~DrainOnExit()
+    {
+        if (!armed || !c || !c->stream) return;
+        (void)hipStreamSynchronize(c->stream);
+    }
+};
+
 }  // namespace reo

@@ -4,7 +4,7 @@
 // per-sample counts, the number of planes that n additions need, the slot -> column map of the sample slots, and the argument checks that
 // need no GPU.  No HIP header in here: plain C++17 (the kernel's unit defines the function attributes through pair_list.h).
 //
-// The comparison itself is the borrow chain of k1_counts over the pos / lo / hi planes (kernels.hip); it yields, for one partner and one
+// The comparison itself is the borrow chain of k1_counts over the pos / lo / hi planes (band_chain.h); it yields, for one partner and one
 // block of 32 sample slots, a word `lt` (bit s: x_i > x_j and not tied in slot s) and a word `le` (bit s: greater or tied).  A lane adds the
 // words of its partners into vertical counters: plane k holds bit k of the 32 running counts.
 #pragma once
@@ -98,17 +98,8 @@ inline int sample_counts_check_args(int64_t G, const int32_t *genes, int64_t n_g
         snprintf(msg, msg_n, "reo_sample_counts: n_genes = %lld, between 1 and 2^30 query genes per call", (long long)n_genes);
         return 2;
     }
-    if (class_mask == 0 || (class_mask & ~kPairClassAll)) {
-        snprintf(msg, msg_n, "reo_sample_counts: class_mask 0x%X selects %s (bit c selects class code c = 3*(ic-1)+(it-1), c in 0..8: 0x1 .. 0x1FF)",
-                 class_mask, class_mask == 0 ? "no class" : "bits above 8");
-        return 3;
-    }
-    for (int64_t q = 0; q < n_genes; ++q)
-        if (genes[q] < 0 || genes[q] >= G) {
-            snprintf(msg, msg_n, "reo_sample_counts: genes[%lld] = %d is outside [0, %lld)", (long long)q, genes[q], (long long)G);
-            return 4;
-        }
-    return 0;
+    if (!query_class_mask_ok("reo_sample_counts", class_mask, msg, msg_n)) return 3;
+    return query_genes_in_range("reo_sample_counts", G, genes, n_genes, msg, msg_n) ? 0 : 4;
 }
 
 }  // namespace reo

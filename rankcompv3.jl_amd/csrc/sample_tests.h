@@ -127,12 +127,7 @@ inline int sample_tests_check_args(int64_t G, const int32_t *genes, int64_t n_ge
         snprintf(msg, msg_n, "reo_sample_tests: n_genes = %lld, between 1 and 2^30 query genes per call", (long long)n_genes);
         return 2;
     }
-    for (int64_t q = 0; q < n_genes; ++q)
-        if (genes[q] < 0 || genes[q] >= G) {
-            snprintf(msg, msg_n, "reo_sample_tests: genes[%lld] = %d is outside [0, %lld)", (long long)q, genes[q], (long long)G);
-            return 3;
-        }
-    return 0;
+    return query_genes_in_range("reo_sample_tests", G, genes, n_genes, msg, msg_n) ? 0 : 3;
 }
 
 }  // namespace reo

@@ -5,8 +5,8 @@
 //       select   threads 0 .. 127 form the selected-pair word of one table word each (pair_list.h, the mask as bits), a scan over the two
 //                waves gives every word its place, and the set bits become a list of 16-bit column offsets in LDS;
 //       chain    wave w takes blocks w, w + 4, ... of the chunk, its lanes the listed partners: the band edges lo_i / hi_i of the block are
-//                wave-uniform, a lane loads its partner's pos planes and runs the borrow chain of k1_counts (bitop3 0x8e over plane_bits(G)
-//                planes); the 32-sample words lt (and le) are added into lane-local vertical counters (sample_counts.h), as many planes
+//                wave-uniform, a lane loads its partner's pos planes and runs the borrow chain of band_chain.h over plane_bits(G)
+//                planes; the 32-sample words lt (and le) are added into lane-local vertical counters (sample_counts.h), as many planes
 //                as the lane's share of the tile needs;
 //       reduce   per plane k and sample bit s: popcount(ballot(bit)) << k, summed over k, kept by lane s and added to the block's 32 int32
 //                accumulators in LDS (a block belongs to one wave: no atomics).
@@ -17,6 +17,7 @@
 // stores go to columns slot2col[slot] in [0, S) of the workgroup's own query row.
 #include "sample_counts.h"
 #include "reo_internal.h"
+#include "band_chain.h"
 
 namespace reo {
 
@@ -57,7 +58,7 @@ __device__ __forceinline__ uint32_t wave_counts(const uint32_t (&c)[kScMaxPlanes
 template <bool BIG, bool WITH_EQ>
 __global__ __launch_bounds__(kScThreads) void k_sample_counts(ScArgs a)
 {
-    constexpr int NQ = BIG ? 5 : 4, EQ = BIG ? 8 : 4;   // uint4 per gene and block: pos planes, edge row
+    constexpr int NQ = BandLayout<BIG>::NQ, EQ = BandLayout<BIG>::EQ;   // uint4 per gene and block: pos planes, edge row
     __shared__ uint16_t list[kScTileCols];
     __shared__ int32_t acc_lt[kScThreads], acc_le[WITH_EQ ? kScThreads : 1];
     __shared__ int32_t wave_tot[2];
@@ -106,12 +107,8 @@ __global__ __launch_bounds__(kScThreads) void k_sample_counts(ScArgs a)
             const uint4 *al = a.AL + (static_cast<size_t>(b) * a.Gp + row) * EQ, *ah = a.AH + (static_cast<size_t>(b) * a.Gp + row) * EQ;
 #pragma unroll
             for (int q = 0; q < NQ; ++q) {
-                const uint4 v = al[q];
-                lo[4 * q] = v.x; lo[4 * q + 1] = v.y; lo[4 * q + 2] = v.z; lo[4 * q + 3] = v.w;
-                if constexpr (WITH_EQ) {
-                    const uint4 h = ah[q];
-                    hi[4 * q] = h.x; hi[4 * q + 1] = h.y; hi[4 * q + 2] = h.z; hi[4 * q + 3] = h.w;
-                }
+                band_unpack(al[q], lo, q);
+                if constexpr (WITH_EQ) band_unpack(ah[q], hi, q);
             }
             uint32_t clt[kScMaxPlanes] = {0, 0, 0, 0, 0, 0, 0}, cle[kScMaxPlanes] = {0, 0, 0, 0, 0, 0, 0};
             const uint4 *pb = a.P + static_cast<size_t>(b) * NQ * a.Gp;
@@ -119,15 +116,12 @@ __global__ __launch_bounds__(kScThreads) void k_sample_counts(ScArgs a)
                 const int j = t0 + list[e];
                 uint32_t p[4 * NQ];
 #pragma unroll
-                for (int q = 0; q < NQ; ++q) {
-                    const uint4 v = pb[static_cast<size_t>(q) * a.Gp + j];
-                    p[4 * q] = v.x; p[4 * q + 1] = v.y; p[4 * q + 2] = v.z; p[4 * q + 3] = v.w;
-                }
+                for (int q = 0; q < NQ; ++q) band_unpack(pb[static_cast<size_t>(q) * a.Gp + j], p, q);
                 uint32_t lt = 0, le = 0;
 #pragma unroll
                 for (int k = 0; k < 4 * NQ; ++k) {
                     if (k >= a.nbits) break;
-                    const int ew = BIG ? k : ((k + 15) & 15);   // the 16-plane layout keeps plane k of an edge in word (k + 15) % 16
+                    const int ew = BandLayout<BIG>::edge_word(k);
                     lt = __builtin_amdgcn_bitop3_b32(p[k], lo[ew], lt, 0x8e);
                     if constexpr (WITH_EQ) le = __builtin_amdgcn_bitop3_b32(p[k], hi[ew], le, 0x8e);
                 }

@@ -121,6 +121,23 @@ void run_checks()
     expect_check(6, 4, genes, 3, 0x44, rowptr, partner, code, 2, "genes[0] = 4 is outside [0, 4)");
     genes[1] = -1;
     expect_check(6, 5, genes, 3, 0x44, rowptr, partner, code, 2, "genes[1] = -1");
+    // the two checks that the other query entry points share with this one, called directly (genes is {4, -1, 4} here)
+    char msg[320] = "";
+    const auto expect_shared = [&](bool got, bool want, const char *needle) {
+        ++g_checks;
+        if (got != want || (!want && !strstr(msg, needle))) {
+            fprintf(stderr, "FAIL shared query check: %d expected %d (\"%s\"), message \"%s\"\n", got, want, needle, msg);
+            ++g_fail;
+        }
+    };
+    expect_shared(reo::query_genes_in_range("reo_x", 5, nullptr, 3, msg, sizeof msg), true, "");   // (null genes: the caller's own refusal)
+    expect_shared(reo::query_genes_in_range("reo_x", 5, genes, 0, msg, sizeof msg), true, "");
+    expect_shared(reo::query_genes_in_range("reo_x", 5, genes, 1, msg, sizeof msg), true, "");
+    expect_shared(reo::query_genes_in_range("reo_x", 4, genes, 1, msg, sizeof msg), false, "reo_x: genes[0] = 4 is outside [0, 4)");
+    expect_shared(reo::query_genes_in_range("reo_x", 5, genes, 3, msg, sizeof msg), false, "reo_x: genes[1] = -1 is outside [0, 5)");
+    expect_shared(reo::query_class_mask_ok("reo_x", 0x1FF, msg, sizeof msg), true, "");
+    expect_shared(reo::query_class_mask_ok("reo_x", 0, msg, sizeof msg), false, "reo_x: class_mask 0x0 selects no class");
+    expect_shared(reo::query_class_mask_ok("reo_x", 0x200, msg, sizeof msg), false, "reo_x: class_mask 0x200 selects bits above 8");
     const int32_t count[3] = {2, 0, 5};
     ++g_checks;
     if (reo::pair_list_rowptr(count, 3, rowptr) != 7 || rowptr[0] != 0 || rowptr[1] != 2 || rowptr[2] != 2 || rowptr[3] != 7) {

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import float32_cases as fc
+from query_cases import band_matrix, halves, planted_ranks, tie_rich
 import sample_counts_cases as scc
 
 pytestmark = pytest.mark.gpu
@@ -13,19 +14,6 @@ pytestmark = pytest.mark.gpu
 ALL = 0x1FF
 N13, N31 = 2, 6
 TODAY = {"k", "result", "labels", "iters_run", "trace"}
-
-
-def halves(S, ngroups=2):
-    return np.array([f"g{min(s * ngroups // S, ngroups - 1)}" for s in range(S)], dtype=object)
-
-
-def tie_rich(G, S, seed, second):
-    """small integers with gene levels and an effect in the samples `second` (bool over the samples): greater, tied and smaller all occur"""
-    rng = np.random.default_rng(seed)
-    X = rng.integers(0, 8, size=(G, 1)) + rng.integers(0, 3, size=(G, S))
-    X[: G // 4, second] += 4
-    X[G // 4: G // 2, second] -= 4
-    return X.astype(np.int64)
 
 
 def open_plain(pkg, X, labels, seed=11, matrix_first=False):
@@ -207,19 +195,6 @@ def test_outcomes_in_the_callers_column_order(pkg, monkeypatch):
         assert (n_gt == -7).all() and (n_eq == -7).all() and (out == 0xAB).all()
 
 
-def planted_ranks(G, S, seed, n_up=30, n_dn=30):
-    """tie-free Int64, every sample a permutation of 0 .. G - 1: stable gene levels with a little noise, the first n_up genes far up and the
-    next n_dn far down in the second half of the samples"""
-    rng = np.random.default_rng(seed)
-    v = 10.0 * rng.permutation(G)[:, None] + rng.integers(-12, 13, size=(G, S))
-    v[:n_up, S // 2:] += 1200.0
-    v[n_up:n_up + n_dn, S // 2:] -= 1200.0
-    order = np.argsort(v, axis=0, kind="stable")
-    X = np.empty((G, S), dtype=np.int64)
-    np.put_along_axis(X, order, np.broadcast_to(np.arange(G, dtype=np.int64)[:, None], (G, S)), axis=0)
-    return X
-
-
 def class_codes(n_gt, sizes, thr, k=0):
     """the class of every entry by the rule of src/RankCompV3.jl:376-377, from the counts of a tie-free matrix: nre = the count in group k,
     not = the count in all other samples; code = 3 (ic - 1) + (it - 1)"""
@@ -304,17 +279,6 @@ def test_after_a_slot_order_build_the_gene_order_planes_are_intact(pkg):
         assert ctx.info()["k1_slot_order"] == 1 and ctx.info()["has_ties"] == 0
         ps, _ = check(ctx, X, gid, make_csr(rng, G, [69, 10, 0, 64], distinct=True), pkg, outcomes=True)
         assert (ps.n_eq == 0).all()
-
-
-def band_matrix(G, S, seed):
-    """Float64 with many pairs near the 0.1 band, and planted pairs a hair inside and outside it"""
-    rng = np.random.default_rng(seed)
-    X = rng.normal(0.0, 0.4, size=(G, S)) + (np.arange(G)[:, None] % 5) * 0.3
-    X[G // 3:, S // 2:] += 0.35
-    for s in range(S):
-        for k, d in enumerate((0.1 - 1e-12, 0.1 + 1e-12, float(np.nextafter(0.1, 0.0)), 0.1, float(np.nextafter(0.1, 1.0)))):
-            X[2 * k + 1, s] = X[2 * k, s] + (d if s % 2 else -d)
-    return np.asfortranarray(X)
 
 
 def all_pairs(G):

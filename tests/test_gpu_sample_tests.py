@@ -5,6 +5,7 @@ integers), under the tolerance constant measured there.  Every test prints the l
 import numpy as np
 import pytest
 
+from query_cases import band_matrix, code_rows, halves, planted_ranks
 import sample_counts_cases as scc
 import sample_tests_cases as stc
 
@@ -12,10 +13,6 @@ pytestmark = pytest.mark.gpu
 
 TODAY = {"k", "result", "labels", "iters_run", "trace"}
 INTS = ("n_above_ctrl", "n_below_ctrl", "rev_up", "rev_down", "tied")
-
-
-def halves(S, ngroups=2):
-    return np.array([f"g{min(s * ngroups // S, ngroups - 1)}" for s in range(S)], dtype=object)
 
 
 def interleaved_33_37():
@@ -35,30 +32,6 @@ def tie_rich(G, S, seed, second):
     return X.astype(np.int64)
 
 
-def band_matrix(G, S, seed):
-    """Float64 with many pairs near the 0.1 band, and planted pairs a hair inside and outside it"""
-    rng = np.random.default_rng(seed)
-    X = rng.normal(0.0, 0.4, size=(G, S)) + (np.arange(G)[:, None] % 5) * 0.3
-    X[G // 3:, S // 2:] += 0.35
-    for s in range(S):
-        for k, d in enumerate((0.1 - 1e-12, 0.1 + 1e-12, float(np.nextafter(0.1, 0.0)), 0.1, float(np.nextafter(0.1, 1.0)))):
-            X[2 * k + 1, s] = X[2 * k, s] + (d if s % 2 else -d)
-    return np.asfortranarray(X)
-
-
-def planted_ranks(G, S, seed, n_up=30, n_dn=30):
-    """tie-free Int64, every sample a permutation of 0 .. G - 1: stable gene levels with a little noise, the first n_up genes far up and the
-    next n_dn far down in the second half of the samples"""
-    rng = np.random.default_rng(seed)
-    v = 10.0 * rng.permutation(G)[:, None] + rng.integers(-12, 13, size=(G, S))
-    v[:n_up, S // 2:] += 1200.0
-    v[n_up:n_up + n_dn, S // 2:] -= 1200.0
-    order = np.argsort(v, axis=0, kind="stable")
-    X = np.empty((G, S), dtype=np.int64)
-    np.put_along_axis(X, order, np.broadcast_to(np.arange(G, dtype=np.int64)[:, None], (G, S)), axis=0)
-    return X
-
-
 def open_ctx(pkg, X, labels, pval_reo=0.1, seed=11, k=0, treat=None):
     ctx = pkg.Context(device=0, seed=seed)
     gid, lev = pkg.encode_groups(labels)
@@ -70,10 +43,6 @@ def open_ctx(pkg, X, labels, pval_reo=0.1, seed=11, k=0, treat=None):
     else:
         ctx.build_contrast(k, treat)
     return ctx
-
-
-def code_rows(ctx, genes):
-    return {int(i): ctx.get_codes(int(i), int(i) + 1, 0, ctx.G)[0] for i in set(np.asarray(genes).reshape(-1).tolist())}
 
 
 def same_integers(got, exp, tag=None, counts=True):
