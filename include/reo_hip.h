@@ -428,6 +428,38 @@ int32_t reo_sample_tests(reo_ctx *ctx, const int32_t *genes, int64_t n_genes,
                          int32_t *rev_up, int32_t *rev_down, int32_t *tied /* n_genes x S row-major, ld = S; may be NULL */,
                          double *p_up, double *p_down /* n_genes x S row-major, ld = S */);
 
+/* The calls themselves: is gene genes[q] up (+1), down (-1) or neither (0) in sample s, with the multiple-testing correction made on the
+ * device -- one byte per cell comes back instead of the two tails.  Per cell p_up and p_down are exactly those of reo_sample_tests for
+ * the same genes and partner_mask (same kernels, same batches' arithmetic), and
+ *     pval = min(1, 2 min(p_up, p_down))
+ *     padj = Benjamini-Hochberg of pval down sample column s over the n_genes rows of THIS call (a repeated gene is a row of its own):
+ *            with the rows in ascending order of pval, padj_(i) = min(1, min over j >= i of pval_(j) (n_genes / j))
+ *     calls[q * S + s] = +1 where pval <= pval_deg, padj <= padj_deg and p_up < p_down; -1 with the tails the other way; else 0
+ *     cut[s]    = the rows of column s with padj <= padj_deg, whatever pval_deg says (the step-up rule's k*)
+ *     n_up[s], n_down[s] = the rows of column s called +1 / -1
+ * in the CALLER's column order.  The padj values themselves are not formed (they need the sorted order): reo_sample_tests and the
+ * caller's own correction keep that route.  The decision is that of the sorted rule bit for bit: with m_i = min{r : pval_i (n / r) <=
+ * padj_deg} and H(r) = #{i : m_i <= r}, k* = max{r : H(r) >= r} and padj_i <= padj_deg <=> m_i <= k* (csrc/sample_calls.h; DESIGN.md
+ * section 3.4), and pval (n / r) is evaluated with the two roundings of the sorted rule's p * (n / rank).
+ * Three phases (csrc/samplecalls.hip): per batch of queries the launches of reo_sample_tests into device buffers that stay there, then
+ * k_call_rank packs rank, direction and the pval_deg bit of every cell into a 32-bit word, kept by sample for the whole call
+ * (4 x n_genes x S bytes, n_genes rounded up to 32); k_call_cut, one workgroup per sample, finds k* from a histogram of the ranks in LDS;
+ * k_call_emit stores the bytes, which come back in one copy.  Batches as reo_sample_tests; REO_SAMPLE_CALLS_BATCH in the environment,
+ * read per call, lowers the batch (tests of the batch seam).  Needs the class table and the transform; reads the reference mask and
+ * changes nothing: reo_get_ref_mask and a following reo_identify_degs behave as if the call had not happened.  Both plane layouts,
+ * every S.  Host arrays only; no stage timer of its own.  cut, n_up and n_down may be NULL.
+ * REO_EINVAL, each with its own message, decided before anything is uploaded, and a refused call writes nothing: a NULL genes or calls;
+ * n_genes < 1 or above 2^29 - 2 (the rank and three more bits share the word); pval_deg or padj_deg NaN or outside [0, 1]; a gene outside
+ * [0, G); no class table; a NULL partner_mask while reo_get_ref_mask would refuse (its reason is passed on); a reo_create_multi context.
+ * REO_ENOMEM, with the bytes needed in the message: the call's device buffers (the resident words foremost) exceed the free device memory.
+ * An incomplete sharded table: REO_ECOMM, as reo_tally.  Counts that G genes cannot produce: REO_EHIP, and no call is written. */
+int32_t reo_sample_calls(reo_ctx *ctx, const int32_t *genes, int64_t n_genes,
+                         const uint8_t *partner_mask /* G bytes; NULL = the mask of reo_get_ref_mask */,
+                         double pval_deg, double padj_deg,
+                         int8_t *calls  /* n_genes x S row-major, ld = S, caller's column order */,
+                         int32_t *cut   /* S; may be NULL: k*, the number of rows with padj <= padj_deg in the column */,
+                         int32_t *n_up, int32_t *n_down /* S each; may be NULL: rows called +1 / -1 in the column */);
+
 /* McCullagh test on 3x3 tables given as 9 tallies each (n x 9 row-major),
  * evaluated by the device routine the iteration uses; out is n x 5 row-major
  * (pval, delta1, delta2, se, z1) -- src/RankCompV3.jl:225-259. */

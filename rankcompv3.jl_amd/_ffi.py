@@ -18,6 +18,7 @@ CSRC = os.path.join(_HERE, "csrc")
 
 REO_OK, REO_EINVAL, REO_EHIP, REO_ECOMM, REO_ENOMEM = 0, -1, -2, -3, -4
 NTIMINGS = 12
+CALL_BINS = 8192   # kCallBins of csrc/sample_calls.h: ranks per histogram tile of k_call_cut (tests place their rows either side of it)
 
 # every symbol include/reo_hip.h declares
 SYMBOLS = [
@@ -33,8 +34,8 @@ SYMBOLS = [
     "reo_pseudobulk_dense_f64", "reo_pseudobulk_dense_i64", "reo_pseudobulk_csc_f64", "reo_pseudobulk_csc_i64",
     "reo_set_matrix_pseudobulk_dense_f64", "reo_set_matrix_pseudobulk_dense_i64", "reo_set_matrix_pseudobulk_csc_f64", "reo_set_matrix_pseudobulk_csc_i64",
     "reo_filter_matrix", "reo_get_matrix", "reo_get_ref_mask", "reo_pair_list", "reo_sample_counts", "reo_pair_support",
-    "reo_sample_tests",
-] + [f"reo_set_matrix_{form}_{t}" for form in ("csc_dev", "pseudobulk_csc_dev", "pseudobulk_dense_dev") for t in ("f64", "i64", "f32", "i32")]
+    "reo_sample_tests", "reo_sample_calls",
+] +[f"reo_set_matrix_{form}_{t}" for form in ("csc_dev", "pseudobulk_csc_dev", "pseudobulk_dense_dev") for t in ("f64", "i64", "f32", "i32")]
 
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p)
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p)
@@ -142,6 +143,7 @@ def lib() -> ctypes.CDLL:
         "reo_sample_counts": (i32, [vp, vp, i64, vp, ctypes.c_uint32, vp, vp, vp]),
         "reo_pair_support": (i32, [vp, vp, i64, vp, vp, vp, vp, vp]),
         "reo_sample_tests": (i32, [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "reo_sample_calls": (i32, [vp, vp, i64, vp, f64, f64, vp, vp, vp, vp]),
     }
     for t in ("f64", "i64", "f32", "i32"):   # SPARSE ON THE DEVICE
         sig["reo_set_matrix_csc_dev_" + t] = (i32, [vp, i64, i64, i64, vp, vp, i32, vp])
@@ -451,6 +453,17 @@ class SampleTests(NamedTuple):
         out[sig & (self.p_up < self.p_down)] = 1
         out[sig & (self.p_down < self.p_up)] = -1
         return out
+
+
+class SampleCalls(NamedTuple):
+    """reo_sample_calls: per query gene (row) and sample (column, the caller's order) the call that SampleTests.calls(pval_deg, padj_deg)
+    forms on the host, formed on the device -- Benjamini-Hochberg per sample column over the queried genes included.  No p-values and no
+    padj values come back (SampleTests keeps those)."""
+    genes: np.ndarray    # int32, the queries as given
+    calls: np.ndarray    # int8, len(genes) x S: +1 up, -1 down, 0 neither
+    cut: np.ndarray      # int32, S: rows of the column with padj <= padj_deg (the step-up rule's k*), whatever pval_deg says
+    n_up: np.ndarray     # int32, S: rows of the column called +1
+    n_down: np.ndarray   # int32, S: rows of the column called -1
 
 
 class SampleScores(NamedTuple):
@@ -814,6 +827,24 @@ class Context:
         self.sample_tests_raw(g, pm, n_above, n_below, ints[0], ints[1], ints[2], p_up, p_down)
         cut = lambda a: None if a is None else a[:, : self.S]   # noqa: E731
         return SampleTests(g, n_above, n_below, cut(ints[0]), cut(ints[1]), cut(ints[2]), cut(p_up), cut(p_down))
+
+    def sample_calls_raw(self, genes, partner_mask, pval_deg: float, padj_deg: float, calls, cut, n_up, n_down) -> None:
+        """reo_sample_calls on caller-made arrays (cut, n_up and n_down may be None); sample_calls is the convenient form."""
+        check(self._L.reo_sample_calls(self._h, *_genes(genes), _opt(partner_mask), float(pval_deg), float(padj_deg), _opt(calls), _opt(cut),
+                                       _opt(n_up), _opt(n_down)))
+
+    def sample_calls(self, pval_deg: float, padj_deg: float, genes=None, partner_mask=None) -> SampleCalls:
+        """Up (+1), down (-1) or neither (0) per query gene (None: all genes) and sample (reo_sample_calls): the tails of sample_tests for
+        the same genes and partner_mask, the two-sided value, Benjamini-Hochberg down every sample column over the queried genes and the
+        two thresholds, all on the device -- byte for byte sample_tests(genes, partner_mask).calls(pval_deg, padj_deg), with one byte per
+        cell coming back.  Host arrays; not available on a multi-GPU context."""
+        g = np.arange(self.G, dtype=np.int32) if genes is None else np.ascontiguousarray(genes, dtype=np.int32).reshape(-1)
+        pm = self._partner_mask(partner_mask)
+        S = max(self.S, 1)
+        calls = np.zeros((g.size, S), dtype=np.int8)
+        cut, n_up, n_down = (np.zeros(S, dtype=np.int32) for _ in range(3))
+        self.sample_calls_raw(g, pm, pval_deg, padj_deg, calls, cut, n_up, n_down)
+        return SampleCalls(g, calls[:, : self.S], cut[: self.S], n_up[: self.S], n_down[: self.S])
 
     def pair_support_raw(self, genes, rowptr, partner, n_gt, n_eq, outcome) -> None:
         """reo_pair_support on caller-made arrays (any may be None); pair_support is the convenient form."""

@@ -598,7 +598,7 @@ using namespace reo;
 
 extern "C" {
 
-int32_t reo_version(void) { return 1000; }
+int32_t reo_version(void) { return 1100; }
 
 int32_t reo_trim_memory(void)
 {

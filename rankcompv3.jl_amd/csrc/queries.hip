@@ -1,5 +1,6 @@
-// The query entry points of the C ABI (include/reo_hip.h): reo_pair_list, reo_sample_counts, reo_sample_tests, reo_pair_support.  Host code
-// only; the kernels are in pairlist.hip, samplecounts.hip, sampletests.hip and pairsupport.hip.  What the four share stands once, in front.
+// The query entry points of the C ABI (include/reo_hip.h): reo_pair_list, reo_sample_counts, reo_sample_tests, reo_sample_calls,
+// reo_pair_support.  Host code only; the kernels are in pairlist.hip, samplecounts.hip, sampletests.hip, samplecalls.hip and pairsupport.hip.
+// What the five share stands once, in front.
 #include <algorithm>
 #include <cstdlib>
 
@@ -7,6 +8,7 @@
 #include "reo_internal.h"
 #include "sample_counts.h"
 #include "sample_tests.h"
+#include "sample_calls.h"
 #include "pair_support.h"
 
 namespace reo {
@@ -226,6 +228,87 @@ int32_t reo_sample_tests(reo_ctx *c, const int32_t *genes, int64_t n_genes, cons
             return REO_EHIP;
         }
     }
+    drain.dismiss();
+    return REO_OK;
+}
+
+// The calls themselves (include/reo_hip.h): phase 1 is reo_sample_tests' batch loop with nothing copied back -- the two counting launches
+// and k_sample_fisher into the batch's buffers, then k_call_rank (samplecalls.hip) turns the batch's tails into the cell words of
+// sample_calls.h, stored by sample into a buffer that stays for the whole call; phase 2, k_call_cut, finds every sample column's
+// Benjamini-Hochberg cut from a histogram of the ranks; phase 3, k_call_emit, stores the int8 calls, which come back in one copy.  The
+// batches follow each other on the stream without a host wait: the query genes go up once.  Reads the class table, the bit planes and a
+// reference mask slot; writes none of them.
+int32_t reo_sample_calls(reo_ctx *c, const int32_t *genes, int64_t n_genes, const uint8_t *partner_mask, double pval_deg, double padj_deg,
+                         int8_t *calls, int32_t *cut, int32_t *n_up, int32_t *n_down)
+{
+    int32_t rc = begin_query(c, "reo_sample_calls", true);
+    if (rc) return rc;
+    char msg[320];
+    if (sample_calls_check_args(c->G, genes, n_genes, pval_deg, padj_deg, calls, msg, sizeof msg)) { set_error("%s", msg); return REO_EINVAL; }
+    if ((rc = need_partner_set(c, "reo_sample_calls", partner_mask))) return rc;
+    if ((rc = ensure_transform(c))) return rc;   // (in place whenever there is a class table: nothing runs)
+    std::vector<int32_t> map;
+    if ((rc = query_slot_map(c, "reo_sample_calls", map))) return rc;
+    const size_t S = static_cast<size_t>(c->S), slots = map.size(), n = static_cast<size_t>(n_genes);
+    const int64_t batch = call_batch_rows(n_genes, static_cast<int64_t>(slots), env_batch("REO_SAMPLE_CALLS_BATCH"));
+    const size_t nb = static_cast<size_t>(batch), cells = nb * S;
+    const int64_t lf_entries = st_lf_entries(c->G);
+    const int64_t need = call_device_bytes(n_genes, c->S, static_cast<int64_t>(slots), batch);
+    size_t free_bytes = 0, total_bytes = 0;
+    REO_HIP_CHECK(hipMemGetInfo(&free_bytes, &total_bytes));
+    if (need < 0 || static_cast<uint64_t>(need) > free_bytes) {
+        set_error("reo_sample_calls: %lld queries x %lld samples need %lld bytes of device memory (%lld of them the resident cell words), %zu are "
+                  "free: query fewer genes per call", (long long)n_genes, (long long)c->S, (long long)need,
+                  (long long)(4 * call_padded_rows(n_genes) * c->S), free_bytes);
+        return REO_ENOMEM;
+    }
+    DevBuf<int32_t> d_genes, d_sel_a, d_sel_b, d_gt_a, d_eq_a, d_gt_b, d_eq_b, d_flag, d_kstar, d_cut, d_up, d_down;
+    DevBuf<double> d_p_up, d_p_down;
+    DevBuf<uint32_t> d_words;
+    DevBuf<int8_t> d_calls;
+    PartnerMask mask;
+    if ((rc = d_genes.ensure(n)) || (rc = d_sel_a.ensure(nb)) || (rc = d_sel_b.ensure(nb)) || (rc = d_gt_a.ensure(nb * slots)) ||
+        (rc = d_eq_a.ensure(nb * slots)) || (rc = d_gt_b.ensure(nb * slots)) || (rc = d_eq_b.ensure(nb * slots)) ||
+        (rc = d_p_up.ensure(cells)) || (rc = d_p_down.ensure(cells)) || (rc = d_flag.ensure(1)) || (rc = d_kstar.ensure(S)) ||
+        (rc = d_cut.ensure(S)) || (rc = d_up.ensure(S)) || (rc = d_down.ensure(S)) ||
+        (rc = d_words.ensure(static_cast<size_t>(call_padded_rows(n_genes)) * S)) || (rc = d_calls.ensure(n * S)) ||
+        (rc = c->sc_slot2col.ensure(slots)) || (rc = c->st_lf.ensure(static_cast<size_t>(lf_entries))) || (rc = mask.prepare(c, partner_mask)))
+        return rc;
+    std::vector<double> lf;
+    int32_t flag = 0;
+    DrainOnExit drain(c);   // genes, partner_mask and lf in, the calls out (declared after the buffers: the wait comes before their release)
+    if (c->st_lf_G != c->G) {   // once per context and gene count, shared with reo_sample_tests
+        st_build_lf(c->G, lf);
+        c->st_lf_G = -1;
+        REO_HIP_CHECK(hipMemcpyAsync(c->st_lf.p, lf.data(), lf.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        REO_HIP_CHECK(hipStreamSynchronize(c->stream));   // (lf is a local)
+        c->st_lf_G = c->G;
+    }
+    if ((rc = upload_slot2col(c, map)) || (rc = mask.upload(c, partner_mask))) return rc;
+    REO_HIP_CHECK(hipMemsetAsync(d_flag.p, 0, sizeof(int32_t), c->stream));
+    REO_HIP_CHECK(hipMemcpyAsync(d_genes.p, genes, n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    for (int64_t q0 = 0; q0 < n_genes; q0 += batch) {   // phase 1 (the stream orders the batches: they share the batch's buffers)
+        const int64_t nq = std::min(batch, n_genes - q0);
+        const int32_t *g = d_genes.p + q0;
+        if ((rc = launch_sample_counts(c, g, nq, mask.bits, kStMaskAbove, c->sc_slot2col.p, d_sel_a.p, d_gt_a.p, d_eq_a.p)) ||
+            (rc = launch_sample_counts(c, g, nq, mask.bits, kStMaskBelow, c->sc_slot2col.p, d_sel_b.p, d_gt_b.p, d_eq_b.p)) ||
+            (rc = launch_sample_fisher(c, nq, d_sel_a.p, d_sel_b.p, d_gt_a.p, d_eq_a.p, d_gt_b.p, d_eq_b.p, c->st_lf.p, lf_entries, nullptr, nullptr,
+                                       nullptr, d_p_up.p, d_p_down.p, d_flag.p)) ||
+            (rc = launch_call_rank(c, n_genes, q0, nq, d_p_up.p, d_p_down.p, pval_deg, padj_deg, d_words.p)))
+            return rc;
+    }
+    if ((rc = launch_call_cut(c, n_genes, d_words.p, d_kstar.p, d_cut.p, d_up.p, d_down.p)) ||   // phase 2
+        (rc = launch_call_emit(c, n_genes, d_words.p, d_kstar.p, d_calls.p)))                     // phase 3
+        return rc;
+    if ((rc = copy_back(c, &flag, 0, d_flag.p, 1)) || (rc = wait_or_drop_table(c))) return rc;
+    if (flag) {   // before anything of the caller's is written
+        set_error("reo_sample_calls: the counting kernel delivered counts that %lld genes cannot produce; no call was written", (long long)c->G);
+        return REO_EHIP;
+    }
+    if ((rc = copy_back(c, calls, 0, d_calls.p, n * S)) || (rc = copy_back(c, cut, 0, d_cut.p, S)) || (rc = copy_back(c, n_up, 0, d_up.p, S)) ||
+        (rc = copy_back(c, n_down, 0, d_down.p, S)))
+        return rc;
+    if ((rc = wait_or_drop_table(c))) return rc;
     drain.dismiss();
     return REO_OK;
 }

@@ -437,6 +437,15 @@ int32_t launch_sample_fisher(reo_ctx *c, int64_t n_queries, const int32_t *d_sel
                              const int32_t *d_eq_a, const int32_t *d_gt_b, const int32_t *d_eq_b, const double *d_lf, int64_t lf_entries,
                              int32_t *d_rev_up, int32_t *d_rev_down, int32_t *d_tied, double *d_p_up, double *d_p_down, int32_t *d_flag);
 
+// samplecalls.hip: the three kernels of reo_sample_calls (shared arithmetic and host checks: sample_calls.h).  d_words: the resident cell
+// words, [S][call_padded_rows(n_genes)].  launch_call_rank turns the tails of one batch (d_p_up / d_p_down: [nq][S], rows q0 .. q0 + nq - 1
+// of the call) into words; launch_call_cut finds every column's cut (d_kstar) and counts the rows within it and the calls of either
+// sign (d_cut, d_n_up, d_n_down: [S] each); launch_call_emit stores the calls, d_calls: [n_genes][S]
+int32_t launch_call_rank(reo_ctx *c, int64_t n_genes, int64_t q0, int64_t nq, const double *d_p_up, const double *d_p_down, double pval_deg,
+                         double padj_deg, uint32_t *d_words);
+int32_t launch_call_cut(reo_ctx *c, int64_t n_genes, const uint32_t *d_words, int32_t *d_kstar, int32_t *d_cut, int32_t *d_n_up, int32_t *d_n_down);
+int32_t launch_call_emit(reo_ctx *c, int64_t n_genes, const uint32_t *d_words, const int32_t *d_kstar, int8_t *d_calls);
+
 // pairsupport.hip: the kernel of reo_pair_support (work items, batches and host checks: pair_support.h).  d_items: [n_items] work items of the
 // batch; d_partner: [entries of the batch] partners, checked by the caller to lie in [0, G) and off the diagonal; d_slot2col as above (read
 // only with d_outcome); d_gt / d_eq: [entries][ngroups] (d_eq null: no tied counts); d_outcome: [entries][S] bytes or null

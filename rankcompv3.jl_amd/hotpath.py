@@ -15,7 +15,7 @@ from typing import NamedTuple
 import numpy as np
 
 from . import _ffi, synth
-from ._ffi import PairList, PairSupport, SampleCounts, SampleScores, SampleTests, class_mask  # noqa: F401
+from ._ffi import PairList, PairSupport, SampleCalls, SampleCounts, SampleScores, SampleTests, class_mask  # noqa: F401
 
 HEADER = ["pval", "padj", "n11", "n12", "n13", "n21", "n22", "n23", "n31", "n32", "n33",
           "Δ1", "Δ2", "se", "z1", "up_down"]  # src/RankCompV3.jl:665
@@ -215,7 +215,7 @@ def write_pairs_tsv(path, gene_names, pair_list) -> None:
 def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref_gene, n_iter, n_conv, *,
                       seed: int = 0, device: int = -1, shard=(0, 1), allreduce=None, allgather=None, profile: bool = False,
                       pairs=None, sample_scores: bool = False, pair_support: bool = False, contrasts=None,
-                      sample_tests: bool = False) -> DegRun:
+                      sample_tests: bool = False, sample_calls: bool = False) -> DegRun:
     """identify_degs with the extras (trace, timings) kept.  `data` is a host matrix (numpy, anything np.asarray takes) or a torch
     tensor on a ROCm device, which is used in place (_ffi.device_matrix).  A column-major host matrix is read in place; a row-major one
     (numpy's default C order, column slices of a wider C-ordered array) is copied column-major on the host first, or, with REO_ROWMAJOR=1
@@ -240,6 +240,9 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
     reference set of its tallies (Context.sample_tests: per gene and sample, Fisher's exact test of the sample's orderings against the pairs
     that are stable in the comparison's control side), taken at the same moment as "sample_scores".  False (the default): no further call,
     no new key.
+    `sample_calls` (not in the reference): True adds "sample_calls" to every comparison dict, the SampleCalls of ALL genes with the run's own
+    pval_deg and padj_deg against the reference set of its tallies (Context.sample_calls: what "sample_tests" .calls(pval_deg, padj_deg)
+    gives, formed on the device, one byte per cell coming back), taken at the same moment.  False (the default): no further call, no new key.
     `pair_support` (not in the reference): True needs `pairs` (DimensionMismatch otherwise) and adds "pair_support" to every comparison
     dict, the PairSupport of that comparison's pair list (Context.pair_support: per listed pair and group, in how many samples the DEG lies
     above its partner, and in how many the two are tied), taken at the same moment as "pairs".  False (the default): no further call, no new
@@ -297,6 +300,8 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
                 comps[-1].update(deg_sample_scores(ctx, comps[-1]["labels"]))
             if sample_tests:
                 comps[-1]["sample_tests"] = ctx.sample_tests()   # all genes, against the reference set of this comparison's tallies
+            if sample_calls:
+                comps[-1]["sample_calls"] = ctx.sample_calls(pval_deg, padj_deg)   # all genes, the run's thresholds, the same reference set
         timings = ctx.timings() if profile else {}
         info = ctx.info()
     first = comps[0]
@@ -336,7 +341,7 @@ class CellsDegRun(NamedTuple):
 def identify_degs_cells(cells, cell_group, gene_names, n_pseudo, pval_reo, pval_deg, padj_deg, ref_gene, n_iter, n_conv, *,
                         min_profiles: int = 0, min_features: int = 0, ref_gene_max: int = 3000, seed: int = 0, device: int = 0,
                         profile: bool = False, pairs=None, sample_scores: bool = False, pair_support: bool = False,
-                        contrasts=None, sample_tests: bool = False) -> CellsDegRun:
+                        contrasts=None, sample_tests: bool = False, sample_calls: bool = False) -> CellsDegRun:
     """Cells to DEGs without a host trip for the profiles: `cells` is a genes x cells matrix (scipy.sparse, anything np.asarray takes, or
     a torch tensor on a ROCm device -- sparse or strided -- which is read where it is: reo_set_matrix_pseudobulk_*_dev_*),
     cell_group one label per cell.  cells_partition -> the pseudo-bulk sums written into the context's matrix (set_matrix_pseudobulk) ->
@@ -344,7 +349,7 @@ def identify_degs_cells(cells, cell_group, gene_names, n_pseudo, pval_reo, pval_
     pair table and iteration as in run_identify_degs.  ref_gene is a bool mask over the INPUT genes (subset by gene_kept here), or None for
     synth.ref_mask(G', min(G', ref_gene_max), seed), the draw reoa makes.  Bit-identical to Context.pseudobulk -> numpy filters ->
     run_identify_degs on the same seed.  (reoa() keeps its host route: its writers want the profile matrix on the host.)
-    `pairs`, `sample_scores`, `pair_support`, `sample_tests`: as in run_identify_degs; gene indices are those of the KEPT genes (run.gene_names), columns
+    `pairs`, `sample_scores`, `pair_support`, `sample_tests`, `sample_calls`: as in run_identify_degs; gene indices are those of the KEPT genes (run.gene_names), columns
     the kept profiles.  `contrasts`: as in run_identify_degs, over the group levels of the cells (checked against the levels of cell_group
     before any context is opened, and again against those of the kept profiles)."""
     need_pairs_for_support(pairs, pair_support)
@@ -393,6 +398,8 @@ def identify_degs_cells(cells, cell_group, gene_names, n_pseudo, pval_reo, pval_
                 comps[-1].update(deg_sample_scores(ctx, comps[-1]["labels"]))
             if sample_tests:
                 comps[-1]["sample_tests"] = ctx.sample_tests()   # all genes, against the reference set of this comparison's tallies
+            if sample_calls:
+                comps[-1]["sample_calls"] = ctx.sample_calls(pval_deg, padj_deg)   # all genes, the run's thresholds, the same reference set
         timings = ctx.timings() if profile else {}
         info = ctx.info()
     first = comps[0]

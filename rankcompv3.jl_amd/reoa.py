@@ -287,7 +287,8 @@ def reoa(fn_expr: str = "fn_expr.txt", fn_meta: str = "fn_meta.txt", *, expr_thr
          n_pseudo: int = 0, use_hk_genes: str = "yes", hk_file: str | None = None, gene_name_type: str = "ENSEMBL",
          ref_gene_max: int = 3000, ref_gene_min: int = 100, n_iter: int = 128, n_conv: int = 5, work_dir: str = "./",
          use_testdata: str = "no", seed: int = 0, device: int = -1, testdata_dir: str | None = None, align_meta: bool | None = None,
-         pairs=None, sample_scores: bool = False, pair_support: bool = False, contrasts=None, sample_tests: bool = False):
+         pairs=None, sample_scores: bool = False, pair_support: bool = False, contrasts=None, sample_tests: bool = False,
+         sample_calls: bool = False):
     """reoa(fn_expr, fn_meta; kwargs...) -- src/RankCompV3.jl:536-555.  `expr_threshold` is accepted and
     unused, as in the reference (:539).  Extra keywords: `seed` (the reference's RNG is unseeded),
     `device`, `testdata_dir` (where fn_expr.txt / fn_meta.txt of the reference's test/ directory live), `align_meta`
@@ -299,7 +300,9 @@ def reoa(fn_expr: str = "fn_expr.txt", fn_meta: str = "fn_meta.txt", *, expr_thr
     `pairs`: additionally writes `<stem>_<fg_name>_pair_support.tsv` per comparison, one line per listed pair: gene, partner, class, and
     per group level in how many of its samples the DEG lies above the partner, `<level>_gt`, and level with it, `<level>_eq`),
     `sample_tests` (True: additionally writes `<stem>_<fg_name>_sample_calls.tsv` per comparison, one row per gene that is called up (1)
-    or down (-1) in at least one sample and one column per sample -- SampleTests.calls(pval_deg, padj_deg) of all genes), `contrasts`
+    or down (-1) in at least one sample and one column per sample -- SampleTests.calls(pval_deg, padj_deg) of all genes), `sample_calls`
+    (True: writes the same file from Context.sample_calls, the calls formed on the device; with `sample_tests` as well the file is
+    written once, from the device's calls), `contrasts`
     ("all" or (ctrl_level, treat_level) pairs as in run_identify_degs: one comparison per contrast, group against group, instead of the
     reference's; the files are `<stem>_<ctrl>_<treat>_result.tsv`, the gene_up_down columns `<ctrl>_vs_<treat>` -- the reference's two-group
     naming -- and the optional files carry the same `<ctrl>_<treat>`)."""
@@ -323,7 +326,7 @@ def reoa(fn_expr: str = "fn_expr.txt", fn_meta: str = "fn_meta.txt", *, expr_thr
     run = run_identify_degs(prep["data"], prep["sample_groups"], prep["gene_names"], pval_reo, pval_deg, padj_deg,
                             prep["ref"], n_iter, n_conv, seed=seed, device=device, pairs=pairs,
                             sample_scores=sample_scores, pair_support=pair_support, contrasts=contrasts,
-                            sample_tests=sample_tests)  # :652-662
+                            sample_tests=sample_tests, sample_calls=sample_calls)  # :652-662
     for p, (d, n) in enumerate(run.trace):
         log.info("INFO: iteration %d,  # DEGs %d, # non-DEGs %d", p, d, n)  # :418
     df = write_outputs(stem, prep, run, work_dir)
@@ -348,7 +351,11 @@ def write_extras(stem: str, prep: dict, run, work_dir: str = ".", pval_deg: floa
         if "sample_scores" in cm:
             out.append(os.path.join(work_dir, f"{stem}_{fg}_sample_scores.tsv"))
             write_sample_scores_tsv(out[-1], prep["gene_names"], prep["sample_names"], cm["sample_scores"])
-        if "sample_tests" in cm:
+        if "sample_calls" in cm:   # the device's calls (at the run's own thresholds): written once, also when "sample_tests" is there too
+            out.append(os.path.join(work_dir, f"{stem}_{fg}_sample_calls.tsv"))
+            sc = cm["sample_calls"]
+            write_sample_calls_tsv(out[-1], prep["gene_names"], prep["sample_names"], sc.genes, sc.calls)
+        elif "sample_tests" in cm:
             out.append(os.path.join(work_dir, f"{stem}_{fg}_sample_calls.tsv"))
             st = cm["sample_tests"]
             write_sample_calls_tsv(out[-1], prep["gene_names"], prep["sample_names"], st.genes, st.calls(pval_deg, padj_deg))
