@@ -618,7 +618,10 @@ int32_t reo_get_timings(reo_ctx *ctx, double *ms, int32_t n);
  * into gene order (0: no slot build; 8 or 4: a word at a time, 8 or 4 table rows per 32- or 16-bit entry -- the default, by the LDS the
  * gene count needs; 1: a bit at a time, REO_K1_UNSLOT=0 in the environment; REO_K1_UNSLOT=8 or 4 asks for that word form wherever its
  * LDS fits; the table is the same bit for bit under all of them), 29 the treat group of the resident class table (reo_build_pairs_contrast;
- * -1: every other sample, reo_build_pairs with more than two groups, and -1 while there is no table). */
+ * -1: every other sample, reo_build_pairs with more than two groups, and -1 while there is no table), 30 the slot orders of that
+ * build (0: no slot build; 1: one order for both sides; 2: an order per side, the default where the two sides together have at least
+ * 16 sample blocks of 32 and a word form puts the columns back; REO_K1_SLOT_SIDES=1 or 2 in the environment asks for that one
+ * everywhere; the table is the same bit for bit under both). */
 int32_t reo_get_info(reo_ctx *ctx, int64_t *info, int32_t n);
 
 #ifdef __cplusplus

@@ -357,7 +357,7 @@ static void invalidate(reo_ctx *c)
     c->eager_k1 = false;
     // no class table any more: nothing is left of a build in slot order either (reo_get_info 25, 26 read 0; the maps and the item list that
     // field 26 would count over belong to the old geometry)
-    c->last_k1_slots = 0; c->k1_slot_items = nullptr; c->k1_slot_items_n = 0; c->k1_slot_gp = 0;
+    c->last_k1_slots = 0; c->last_k1_slot_sides = 0; c->k1_slot_items = nullptr; c->k1_slot_items_n = 0; c->k1_slot_gp = 0;
 }
 
 // dtype: what the caller hands over -- 1 Float64, 2 Int64, 3 Float32, 4 Int32 (which becomes a resident Int64 matrix: its tie is equality)
@@ -658,6 +658,7 @@ int32_t reo_create(reo_ctx **out, int32_t device, uint64_t seed)
     if (const char *e = getenv("REO_K1_SLOTS")) c->k1_slots = (e[0] != '0');
     if (const char *e = getenv("REO_K1_QUEUE")) c->k1_queue = (e[0] != '0');
     if (const char *e = getenv("REO_K1_UNSLOT")) { const int v = atoi(e); c->k1_unslot = (v == 8 || v == 4) ? v : (e[0] == '0' ? 0 : -1); }
+    if (const char *e = getenv("REO_K1_SLOT_SIDES")) { const int v = atoi(e); c->k1_slot_sides = (v == 1 || v == 2) ? v : 0; }
     if (const char *e = getenv("REO_K1_WORKERS")) c->k1_workers = std::max(1, atoi(e));
     if (const char *e = getenv("REO_K1_ORDER")) c->k1_order = std::max(0, std::min(2, atoi(e)));
     {
@@ -1503,14 +1504,15 @@ int32_t reo_get_info(reo_ctx *c, int64_t *info, int32_t n)
         int32_t rc = use(c);
         if (rc || (rc = launch_slot_separated(c, &separated))) return rc;
     }
-    const int64_t v[30] = {c->G, c->S, c->Gp, static_cast<int64_t>(c->table.n * sizeof(uint32_t)), c->has_ties,
+    const int64_t v[31] = {c->G, c->S, c->Gp, static_cast<int64_t>(c->table.n * sizeof(uint32_t)), c->has_ties,
                            c->tiles_owned, c->tiles_total, kTileI, c->k1_cj, c->k1_q, kUnitH,
                            c->goff32.empty() ? 0 : c->goff32.back(), c->last_k1_shared,
                            static_cast<int64_t>(c->gcounts.n * sizeof(uint16_t)), c->transform_in_lds, c->xcc_local,
                            c->it_cycle_period, c->it_cycle_at, c->it_cycle_skipped, c->narrowed_bytes, c->eager_range_launches, c->rowmajor_upload,
                            c->csc_upload, c->csc_nnz, c->dtype, c->last_k1_slots, separated, c->csc_device,
-                           c->last_k1_slots ? c->last_k1_unslot : 0, c->built_k >= 0 ? c->built_treat : -1};
-    for (int i = 0; i < n && i < 30; ++i) info[i] = v[i];
+                           c->last_k1_slots ? c->last_k1_unslot : 0, c->built_k >= 0 ? c->built_treat : -1,
+                           c->last_k1_slots ? c->last_k1_slot_sides : 0};
+    for (int i = 0; i < n && i < 31; ++i) info[i] = v[i];
     return REO_OK;
 }
 

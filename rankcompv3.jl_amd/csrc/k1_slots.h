@@ -5,6 +5,9 @@
 //   key(g)  = pmin_0 + pmax_0 + pmin_1 + pmax_1          the per-side extremes of gene g's positions over the side's real samples
 //   slot(g) = #{ g' : (key(g'), g') < (key(g), g) }     a counting rank: a permutation of 0 .. G-1
 //   s2g[slot(g)] = g, g2s[g] = slot(g); slots G .. Gp-1 (padding genes) map to themselves
+// PER-SIDE ORDER: an item belongs to one side and a side's words stay inside its two planes of the table, so each side may have an order
+// of its own, key_z(g) = pmin_z + pmax_z, with its own g2s / s2g: a gene whose level differs between the groups is then in its place on
+// both sides instead of between its two levels on either (slot_side_key, slot_sides_wanted and the *_sides / *_pair functions below).
 #pragma once
 
 #include <cstddef>
@@ -36,6 +39,25 @@ REO_SLOTS_HD uint32_t slot_key(uint32_t side0, uint32_t side1) { return slot_min
 
 // key and gene as one number: its order is the order of (key, gene)
 REO_SLOTS_HD uint64_t slot_order_key(uint32_t key, uint32_t gene) { return static_cast<uint64_t>(key) << 32 | gene; }
+
+// the key of one side alone (per-side order)
+REO_SLOTS_HD uint32_t slot_side_key(uint32_t side) { return slot_min(side) + slot_max(side); }
+
+// ... in 32 bits where they fit: up to 32 768 genes a position is below 2^15, every key (of one side or of both) below 2^17 and a gene
+// below 2^15.  The rank (kernels.hip: sorted spans in LDS and binary searches; here: the counting rank) then moves half the bytes.
+constexpr int kSlotKey32Genes = 32768;
+REO_SLOTS_HD bool slot_order_key32_fits(int G) { return G <= kSlotKey32Genes; }
+REO_SLOTS_HD uint32_t slot_order_key32(uint32_t key, uint32_t gene) { return key << 15 | gene; }
+
+// Which builds order their sides separately: those whose two sides together have at least kSlotSidesBlocks sample blocks of 32.  The
+// saving is a share of the count loops, whose length is the number of blocks; the second rank, invert and map cost the same at every
+// sample count.  force: 0 this rule, 1 the common order everywhere, 2 per-side order everywhere (REO_K1_SLOT_SIDES).
+constexpr int kSlotSidesBlocks = 16;
+REO_SLOTS_HD int slot_sides_wanted(int blocks0, int blocks1, int force)
+{
+    if (force == 1 || force == 2) return force;
+    return blocks0 + blocks1 >= kSlotSidesBlocks ? 2 : 1;
+}
 
 // What an item's counts are without counting, from the ranges of its i-tile (rmin, rmax) and its wave chunk (cmin, cmax) on its side:
 // 1 every real sample counts (each column gene lies below each row gene in every sample), -1 none does, 0 the loop has to run.
@@ -70,6 +92,41 @@ inline void slot_invert(const uint32_t *g2s_G, int G, int Gp, uint32_t *g2s, uin
 {
     for (int g = 0; g < G; ++g) { g2s[g] = g2s_G[g]; s2g[g2s_G[g]] = static_cast<uint32_t>(g); }
     for (int g = G; g < Gp; ++g) g2s[g] = s2g[g] = static_cast<uint32_t>(g);
+}
+
+// the 32-bit form of slot_rank (G <= kSlotKey32Genes): the same permutation
+inline void slot_rank32(const uint32_t *key, int G, uint32_t *g2s)
+{
+    for (int g = 0; g < G; ++g) {
+        uint32_t n = 0;
+        for (int h = 0; h < G; ++h) n += slot_order_key32(key[h], static_cast<uint32_t>(h)) < slot_order_key32(key[g], static_cast<uint32_t>(g)) ? 1u : 0u;
+        g2s[g] = n;
+    }
+}
+
+// Per-side order on the host: gmm[z][g] (Gp apart) -> key[z][g], g2s[z][.], s2g[z][.] (Gp apart each; the device does the same with
+// the side as a grid dimension)
+inline void slot_maps_sides(const uint32_t *gmm, int G, int Gp, uint32_t *key, uint32_t *g2s, uint32_t *s2g, uint32_t *rank_G)
+{
+    for (int z = 0; z < 2; ++z) {
+        const size_t o = static_cast<size_t>(z) * Gp;
+        for (int g = 0; g < G; ++g) key[o + g] = slot_side_key(gmm[o + g]);
+        if (slot_order_key32_fits(G)) slot_rank32(key + o, G, rank_G);
+        else slot_rank(key + o, G, rank_G);
+        slot_invert(rank_G, G, Gp, g2s + o, s2g + o);
+    }
+}
+
+// the ranges of side z's 32-slot tiles and 256-slot chunks over their slots below G (k1_slot_ranges): trng[Gp / 32], crng[Gp / 256]
+inline void slot_ranges_side(const uint32_t *gmm_z, const uint32_t *s2g_z, int G, int Gp, uint32_t *trng, uint32_t *crng)
+{
+    for (int t = 0; t < Gp / kSlotTile; ++t) trng[t] = slot_pack(kSlotNoMin, kSlotNoMax);
+    for (int q = 0; q < Gp / kSlotChunk; ++q) crng[q] = slot_pack(kSlotNoMin, kSlotNoMax);
+    for (int k = 0; k < G; ++k) {
+        const uint32_t r = gmm_z[s2g_z[k]];
+        trng[k / kSlotTile] = slot_join(trng[k / kSlotTile], r);
+        crng[k / kSlotChunk] = slot_join(crng[k / kSlotChunk], r);
+    }
 }
 
 // One bit row of the class table (W words) from slot-order columns into gene-order columns: out bit j = in bit g2s[j] for j < G, columns
@@ -211,6 +268,34 @@ inline void unslot_group_model(uint32_t *table, int r0, int n_rows, int G, int W
         for (int c = 0; c < 32; ++c) ks[c] = g2s[32 * wo + c];
         unslot_out_word<R>(u, ks, wo, T, G, 32 * Wp);
         for (int q = 0; q < 4 * nr; ++q) rows[static_cast<size_t>(q) * Wp + wo] = u[q];
+    }
+}
+
+// ---- the PAIR form of the word un-permute (per-side order: k1_unslot_pair): a side's two planes have that side's slot order, so a
+// workgroup takes 2R rows of ONE side's plane pair -- the same 4R x 32 bit blocks, entries, T and transposes as above, another meaning
+// of an entry's bits -- and uses that side's g2s.
+REO_SLOTS_HD int unslot_pair_bit(int row, int plane) { return 2 * row + plane; }   // row of the group's 2R, plane 0 / 1 of the side's pair
+// where the word of entry bit q lies among the group's rows (whole rows: four planes of Wp words), in words from the group's first row
+REO_SLOTS_HD size_t unslot_pair_word(int q, int side, int Wp, int w) { return (static_cast<size_t>(q >> 1) * 4 + 2 * side + (q & 1)) * Wp + w; }
+
+// The serial host model of one workgroup of k1_unslot_pair<R>: planes 2 side and 2 side + 1 of rows r0 .. r0 + 2R - 1, in place, with
+// g2s the map of that side; the side's other planes and the rows from n_rows on are neither read nor written.
+template <int R>
+inline void unslot_pair_model(uint32_t *table, int r0, int n_rows, int side, int G, int Wp, const uint32_t *g2s, uint32_t *T)
+{
+    const int nr = n_rows - r0 < 2 * R ? n_rows - r0 : 2 * R;
+    if (nr <= 0) return;
+    uint32_t *rows = table + static_cast<size_t>(r0) * 4 * Wp;
+    for (int w = 0; w < Wp; ++w) {
+        uint32_t m[4 * R];
+        for (int q = 0; q < 4 * R; ++q) m[q] = q < 2 * nr ? rows[unslot_pair_word(q, side, Wp, w)] : 0u;
+        unslot_in_word<R>(m, w, T);
+    }
+    for (int wo = 0; wo < Wp; ++wo) {   // (behind the barrier)
+        uint32_t u[4 * R], ks[32];
+        for (int c = 0; c < 32; ++c) ks[c] = g2s[32 * wo + c];
+        unslot_out_word<R>(u, ks, wo, T, G, 32 * Wp);
+        for (int q = 0; q < 2 * nr; ++q) rows[unslot_pair_word(q, side, Wp, wo)] = u[q];
     }
 }
 

@@ -276,7 +276,7 @@ struct K1Args {
     int park_mode;               // bit 0: add the parked counts of the blocks before this range; bit 1: park the sums instead of classifying
     // SLOT ORDER (k1w_pairs_slots; k1_slots.h): P and AL are then the planes in slot order, every index of the kernel is a slot, and
     // only the table's ROW is looked up (s2g); the columns come back in gene order afterwards (k1_unslot_words).  Else null.
-    const uint32_t *s2g;         // [Gp] slot -> gene
+    const uint32_t *s2g;         // [2 sides][Gp] slot -> gene on the item's side (the common order: the same map twice)
     const uint32_t *trng, *crng; // [2 sides][Gp / 32], [2 sides][Gp / 256]: position ranges (min | max << 16) of the i-tiles and wave chunks
     // ITEM QUEUES (k1w_pairs_slots; k1_queue.h): the launch has one workgroup per wave slot of the device, and each takes items of the
     // list from these counters until none is left.  Null: workgroup b runs item b and ends (REO_K1_QUEUE=0, the A/B partner).
@@ -351,7 +351,7 @@ __device__ __forceinline__ void emit_gene(const K1Args &a, int i0, int j, int bi
     else emit_rows<RI, 0>(near, d, lanes_ok, hi_thr, lo_thr, wL, wH, fLlo, fLhi, fHlo, fHhi, val);
     const bool diag = (bj == bi);
     if (lane < RI && i0 + lane < a.G) {
-        const size_t gi = SLOTS ? a.s2g[i0 + lane] : static_cast<size_t>(i0 + lane);   // (slot order: the row of the gene in that slot)
+        const size_t gi = SLOTS ? a.s2g[(pl >> 1) * a.Gp + i0 + lane] : static_cast<size_t>(i0 + lane);   // (slot order: the row of the gene in that slot of the side, pl >> 1)
         uint32_t *row = a.table + (gi * kPlanes + pl) * a.Wp + 2 * bj;
         if (!diag) {
             *reinterpret_cast<uint2 *>(row) = uint2{fLlo, fLhi};
@@ -364,7 +364,7 @@ __device__ __forceinline__ void emit_gene(const K1Args &a, int i0, int j, int bi
         }
     }
     if (j < a.G) {  // mirror: pair (j, i) is in state 2 - state(i, j)
-        const size_t gj = SLOTS ? a.s2g[j] : static_cast<size_t>(j);
+        const size_t gj = SLOTS ? a.s2g[(pl >> 1) * a.Gp + j] : static_cast<size_t>(j);
         uint32_t *row = a.table + (gj * kPlanes + pl) * a.Wp + (i0 >> 5);
         if (RI == 16) {  // a half-height item owns one 16-bit half of the word (the other half: its twin, or nobody)
             const int half = (i0 >> 4) & 1;
@@ -404,7 +404,8 @@ __device__ __forceinline__ void emit_constant(const K1Args &a, int i0, int jl, i
     else if (n <= lo_thr) ++mir;
     else return;
     const bool row_ok = lane < RI && i0 + lane < a.G;
-    uint32_t *frow = a.table + (static_cast<size_t>(row_ok ? a.s2g[i0 + lane] : 0u) * kPlanes + fwd) * a.Wp;
+    const uint32_t *s2g = a.s2g + side * a.Gp;   // (the side's own order)
+    uint32_t *frow = a.table + (static_cast<size_t>(row_ok ? s2g[i0 + lane] : 0u) * kPlanes + fwd) * a.Wp;
 #pragma unroll
     for (int r = 0; r < kRJ; ++r) {
         const int j = jl + 64 * r;
@@ -414,7 +415,7 @@ __device__ __forceinline__ void emit_constant(const K1Args &a, int i0, int jl, i
         if (!lanes_ok) continue;
         if (row_ok) *reinterpret_cast<uint2 *>(frow + 2 * bj) = uint2{static_cast<uint32_t>(lanes_ok), static_cast<uint32_t>(lanes_ok >> 32)};
         if (j < a.G) {
-            uint32_t *row = a.table + (static_cast<size_t>(a.s2g[j]) * kPlanes + mir) * a.Wp + (i0 >> 5);
+            uint32_t *row = a.table + (static_cast<size_t>(s2g[j]) * kPlanes + mir) * a.Wp + (i0 >> 5);
             if (RI == 16) reinterpret_cast<uint16_t *>(row)[(i0 >> 4) & 1] = 0xFFFFu;   // (its half of the word, as in emit_gene)
             else *row = 0xFFFFFFFFu;
         }
@@ -744,7 +745,7 @@ __global__ __launch_bounds__(64, 3) void k1w_pairs_slots(K1Args a)
 
 // ---- slot order: the small kernels around the pair kernel (launch_k1 -> k1_slots; the rules: k1_slots.h)
 constexpr int kSlotSplits = 16;    // slices of a side's samples in k1_slot_part
-constexpr int kSlotRankSpan = 2048;  // genes g' that one workgroup of k1_slot_rank compares its 256 genes with
+constexpr int kSlotRankSpan = 2048;  // genes of a sorted span: one workgroup of k1_slot_sort, one binary search per gene and span in k1_slot_rank
 
 // the position range of gene g on side z over slice y of the side's REAL sample slots (the first n of them from slot s0; padding slots
 // hold zeros and must not enter): part[y][z][g] = min | max << 16
@@ -764,8 +765,8 @@ __global__ __launch_bounds__(256) void k1_slot_part(const uint16_t *__restrict__
     part[(static_cast<size_t>(split) * 2 + side) * Gp + g] = slot_pack(mn, mx);
 }
 
-// ... joined over the slices: gmm[side][g], and the gene's key
-__global__ __launch_bounds__(256) void k1_slot_keys(const uint32_t *__restrict__ part, int Gp, int G, uint32_t *__restrict__ gmm, uint32_t *__restrict__ key)
+// ... joined over the slices: gmm[side][g], and the gene's key -- one for both sides (key[g]), or one per side (key[side][g])
+__global__ __launch_bounds__(256) void k1_slot_keys(const uint32_t *__restrict__ part, int Gp, int G, int sides, uint32_t *__restrict__ gmm, uint32_t *__restrict__ key)
 {
     const int g = blockIdx.x * 256 + threadIdx.x;
     if (g >= G) return;
@@ -776,33 +777,76 @@ __global__ __launch_bounds__(256) void k1_slot_keys(const uint32_t *__restrict__
         r1 = slot_join(r1, part[(static_cast<size_t>(y) * 2 + 1) * Gp + g]);
     }
     gmm[g] = r0; gmm[Gp + g] = r1;
-    key[g] = slot_key(r0, r1);
+    if (sides == 2) { key[g] = slot_side_key(r0); key[Gp + g] = slot_side_key(r1); }
+    else key[g] = slot_key(r0, r1);
 }
 
-// g2s[g] += the number of genes g' of span y with (key, g') < (key, g)   (g2s cleared by the host: a counting rank, G^2 comparisons)
-__global__ __launch_bounds__(256) void k1_slot_rank(const uint32_t *__restrict__ key, int G, uint32_t *__restrict__ g2s)
+// The rank in two steps (all (key, gene) are distinct, so slot(g) = the sum over the spans of the number of their elements below g's):
+// k1_slot_sort sorts every span of kSlotRankSpan genes by (key_z, gene) -- a bitonic sort in LDS, two elements per thread -- and
+// k1_slot_rank adds, for its 256 genes and span y, the place of each gene's own element in that sorted span: one binary search of 11
+// LDS reads where the counting rank before it made 2 048 comparisons (G^2 in all: 46 us at config 3 for ONE order; the two orders of a
+// per-side build together now take less).  blockIdx.z / .y: the side of a per-side order (key, g2s Gp apart; srt: spans * kSlotRankSpan apart).
+// K32 (at most 32 768 genes: slot_order_key32): key and gene share one word, half the LDS and the traffic.  g2s is cleared by the host.
+template <bool K32>
+__global__ __launch_bounds__(kSlotRankSpan / 2) void k1_slot_sort(const uint32_t *__restrict__ key, int G, int Gp, void *__restrict__ srt_)
 {
-    __shared__ uint64_t sk[kSlotRankSpan];
-    const int h0 = blockIdx.y * kSlotRankSpan;
-    for (int t = threadIdx.x; t < kSlotRankSpan; t += 256)
-        sk[t] = h0 + t < G ? slot_order_key(key[h0 + t], static_cast<uint32_t>(h0 + t)) : ~0ull;   // (beyond the genes: below nobody)
+    typedef typename std::conditional<K32, uint32_t, uint64_t>::type Key;
+    __shared__ Key sk[kSlotRankSpan];
+    key += static_cast<size_t>(blockIdx.y) * Gp;
+    Key *srt = static_cast<Key *>(srt_) + (static_cast<size_t>(blockIdx.y) * gridDim.x + blockIdx.x) * kSlotRankSpan;
+    const int h0 = blockIdx.x * kSlotRankSpan, t = threadIdx.x;
+    for (int e = t; e < kSlotRankSpan; e += kSlotRankSpan / 2) {
+        Key v = static_cast<Key>(~0ull);   // (beyond the genes: below nobody, behind everybody)
+        if (h0 + e < G) {
+            if constexpr (K32) v = slot_order_key32(key[h0 + e], static_cast<uint32_t>(h0 + e));
+            else v = slot_order_key(key[h0 + e], static_cast<uint32_t>(h0 + e));
+        }
+        sk[e] = v;
+    }
+    for (int k = 2; k <= kSlotRankSpan; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            __syncthreads();
+            const int l = ((t & ~(j - 1)) << 1) | (t & (j - 1)), r = l | j;   // the t-th pair at distance j
+            const Key x = sk[l], y = sk[r];
+            if ((x > y) == ((l & k) == 0)) { sk[l] = y; sk[r] = x; }
+        }
+    __syncthreads();
+    for (int e = t; e < kSlotRankSpan; e += kSlotRankSpan / 2) srt[e] = sk[e];
+}
+
+template <bool K32>
+__global__ __launch_bounds__(256) void k1_slot_rank(const uint32_t *__restrict__ key, const void *__restrict__ srt_, int G, int Gp, uint32_t *__restrict__ g2s)
+{
+    typedef typename std::conditional<K32, uint32_t, uint64_t>::type Key;
+    __shared__ Key sk[kSlotRankSpan];
+    key += static_cast<size_t>(blockIdx.z) * Gp; g2s += static_cast<size_t>(blockIdx.z) * Gp;
+    const Key *srt = static_cast<const Key *>(srt_) + (static_cast<size_t>(blockIdx.z) * gridDim.y + blockIdx.y) * kSlotRankSpan;
+    for (int t = threadIdx.x; t < kSlotRankSpan; t += 256) sk[t] = srt[t];
     __syncthreads();
     const int g = blockIdx.x * 256 + threadIdx.x;
     if (g >= G) return;
-    const uint64_t mine = slot_order_key(key[g], static_cast<uint32_t>(g));
-    uint32_t n = 0;
-#pragma unroll 8
-    for (int t = 0; t < kSlotRankSpan; ++t) n += sk[t] < mine ? 1u : 0u;   // broadcast reads
+    Key mine;
+    if constexpr (K32) mine = slot_order_key32(key[g], static_cast<uint32_t>(g));
+    else mine = slot_order_key(key[g], static_cast<uint32_t>(g));
+    uint32_t n = 0;   // elements of the span below mine: at most kSlotRankSpan
+#pragma unroll
+    for (int step = kSlotRankSpan / 2; step > 0; step >>= 1) n += sk[n + step - 1] < mine ? step : 0;
+    n += sk[n] < mine ? 1u : 0u;   // (n <= kSlotRankSpan - 1 here)
     if (n) atomicAdd(&g2s[g], n);
 }
 
-// s2g from g2s; padding slots map to themselves
-__global__ __launch_bounds__(256) void k1_slot_invert(uint32_t *__restrict__ g2s, uint32_t *__restrict__ s2g, int G, int Gp)
+// s2g from g2s; padding slots map to themselves.  sides == 2: blockIdx.y is the side (both maps Gp apart); sides == 1: the one order is
+// written as the map of BOTH sides (s2g[0] and s2g[1]), so that every reader indexes s2g by its side.
+__global__ __launch_bounds__(256) void k1_slot_invert(uint32_t *__restrict__ g2s, uint32_t *__restrict__ s2g, int G, int Gp, int sides)
 {
     const int g = blockIdx.x * 256 + threadIdx.x;
     if (g >= Gp) return;
-    if (g < G) { const uint32_t k = g2s[g]; if (k < static_cast<uint32_t>(G)) s2g[k] = static_cast<uint32_t>(g); }   // (k < G always: a rank among G genes)
-    else { g2s[g] = static_cast<uint32_t>(g); s2g[g] = static_cast<uint32_t>(g); }
+    if (sides == 2) { g2s += static_cast<size_t>(blockIdx.y) * Gp; s2g += static_cast<size_t>(blockIdx.y) * Gp; }
+    uint32_t k = static_cast<uint32_t>(g), v = static_cast<uint32_t>(g);
+    if (g < G) { k = g2s[g]; if (k >= static_cast<uint32_t>(G)) return; }   // (k < G always: a rank among G genes)
+    else g2s[g] = v;
+    s2g[k] = v;
+    if (sides != 2) s2g[static_cast<size_t>(Gp) + k] = v;
 }
 
 // the position ranges of the i-tiles (32 slots) and wave chunks (256 slots) of side y, over their slots below G
@@ -812,7 +856,7 @@ __global__ __launch_bounds__(256) void k1_slot_ranges(const uint32_t *__restrict
     static_assert(kSlotTile == kTileI && kSlotChunk == 64 * kRJ, "k1_slots.h carries its own copy of the item geometry");
     __shared__ uint32_t sm[8];
     const int k = blockIdx.x * 256 + threadIdx.x, side = blockIdx.y;   // (Gp is a multiple of 1024: every thread has a slot)
-    uint32_t r = k < G ? gmm[static_cast<size_t>(side) * Gp + s2g[k]] : slot_pack(kSlotNoMin, kSlotNoMax);
+    uint32_t r = k < G ? gmm[static_cast<size_t>(side) * Gp + s2g[static_cast<size_t>(side) * Gp + k]] : slot_pack(kSlotNoMin, kSlotNoMax);
 #pragma unroll
     for (int o = 1; o < 32; o <<= 1) r = slot_join(r, static_cast<uint32_t>(__shfl_xor(static_cast<int>(r), o)));
     if ((threadIdx.x & 31) == 0) { trng[static_cast<size_t>(side) * (Gp >> 5) + (k >> 5)] = r; sm[threadIdx.x >> 5] = r; }
@@ -824,11 +868,13 @@ __global__ __launch_bounds__(256) void k1_slot_ranges(const uint32_t *__restrict
 }
 
 // the planes of sample block y in slot order: Ps[(b 4 + q) Gp + k] = P[(b 4 + q) Gp + s2g[k]] (16 bytes each), and the 64-byte
-// records ALs[b Gp + k] = AL[b Gp + s2g[k]], four threads per record
-__global__ __launch_bounds__(256) void k1_slot_gather(const uint4 *__restrict__ P, const uint4 *__restrict__ AL, const uint32_t *__restrict__ s2g, int Gp,
+// records ALs[b Gp + k] = AL[b Gp + s2g[k]], four threads per record.  s2g: the map of the side that reads the block -- side 0 counts
+// the blocks cb .. ce - 1, side 1 every other one (by the launch's block ranges, not by group ids: comparison 1 swaps the groups)
+__global__ __launch_bounds__(256) void k1_slot_gather(const uint4 *__restrict__ P, const uint4 *__restrict__ AL, const uint32_t *__restrict__ s2g, int Gp, int cb, int ce,
                                                       uint4 *__restrict__ Ps, uint4 *__restrict__ ALs)
 {
     const int k = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
+    if (b < cb || b >= ce) s2g += Gp;
     const uint32_t g = s2g[k];
 #pragma unroll
     for (int q = 0; q < 4; ++q) Ps[(static_cast<size_t>(b) * 4 + q) * Gp + k] = P[(static_cast<size_t>(b) * 4 + q) * Gp + g];
@@ -928,6 +974,41 @@ __global__ __launch_bounds__(kUnslotThreadsMax) void k1_unslot_words(uint32_t *_
 #pragma unroll
         for (int q = 0; q < NQ; ++q)
             if (q < nq) rows[static_cast<size_t>(q) * Wp + wo] = u[q];
+    }
+}
+
+// The PAIR form (per-side order; k1_slots.h, unslot_pair_model): a side's two planes have that side's slot order, so a workgroup takes
+// 2R rows of the plane pair of side blockIdx.y and that side's g2s.  The same 4R words per thread, T, transposes and stores per word as
+// k1_unslot_words<R>; the two launches' halves together move the same bytes.
+template <int R>
+__global__ __launch_bounds__(kUnslotThreadsMax) void k1_unslot_pair(uint32_t *__restrict__ table, const uint32_t *__restrict__ g2s, int G, int Wp)
+{
+    constexpr int NQ = 4 * R;
+    extern __shared__ uint32_t unslot_t[];
+    const int r0 = blockIdx.x * 2 * R, nr = min(2 * R, G - r0), side = blockIdx.y;
+    if (nr <= 0) return;
+    const int nq = nr * 2;   // (the last group's missing rows are neither loaded nor stored)
+    g2s += static_cast<size_t>(side) * 32 * Wp;
+    uint32_t *rows = table + static_cast<size_t>(r0) * kPlanes * Wp;
+    for (int w = threadIdx.x; w < Wp; w += blockDim.x) {
+        uint32_t m[NQ];
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) m[q] = q < nq ? rows[unslot_pair_word(q, side, Wp, w)] : 0u;   // (wave-uniform)
+        unslot_in_word<R>(m, w, unslot_t);
+    }
+    __syncthreads();   // every word of these rows' plane pair is in T: from here on they are only written
+    for (int wo = threadIdx.x; wo < Wp; wo += blockDim.x) {
+        const uint4 *kq = reinterpret_cast<const uint4 *>(g2s) + static_cast<size_t>(wo) * 8;   // (g2s holds Gp = 32 Wp slots per side)
+        uint32_t ks[32], u[NQ];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const uint4 k4 = kq[i];
+            ks[4 * i] = k4.x; ks[4 * i + 1] = k4.y; ks[4 * i + 2] = k4.z; ks[4 * i + 3] = k4.w;
+        }
+        unslot_out_word<R>(u, ks, wo, unslot_t, G, 32 * Wp);
+#pragma unroll
+        for (int q = 0; q < NQ; ++q)
+            if (q < nq) rows[unslot_pair_word(q, side, Wp, wo)] = u[q];
     }
 }
 
@@ -4374,17 +4455,22 @@ static int32_t apply_range(reo_ctx *c, K1Args &a, int sides, const K1Range *rang
 // the genes ordered by level (the sum of the extremes of their positions on the two sides), which puts most items' tile and chunk
 // apart on the item's side -- every count of such an item is 0 or the side's size, and its count loop is skipped.  Slot order lives and
 // dies inside launch_k1: the table that leaves it is the identity order's, bit for bit, and nobody else learns that slots exist.
+// From 16 sample blocks on each SIDE has an order of its own (key_z = the sum of that side's two extremes; k1_slots.h, slot_sides_wanted): a
+// gene whose level differs between the groups is then in place on both sides, and fewer items are mixed.
 
 // the parts of c->k1_slot_maps (uint32 each)
-struct SlotMaps { uint32_t *gmm, *key, *g2s, *s2g, *trng, *crng; unsigned long long *count; };
-static size_t slot_maps_words(int Gp) { return static_cast<size_t>(Gp) * 5 + static_cast<size_t>(Gp) / 16 + static_cast<size_t>(Gp) / 128 + 2; }
+// (gmm, key, g2s, s2g: [2 sides][Gp] each.  The common order fills key[0] and g2s[0] only, and both halves of s2g with its one map.)
+// srt: the sorted spans of the rank, [2 sides][Gp + kSlotRankSpan] 64-bit elements at most.
+struct SlotMaps { uint32_t *gmm, *key, *g2s, *s2g, *trng, *crng; unsigned long long *count, *srt; };
+static size_t slot_maps_words(int Gp) { return static_cast<size_t>(Gp) * 8 + static_cast<size_t>(Gp) / 16 + static_cast<size_t>(Gp) / 128 + 2 + 4 * (static_cast<size_t>(Gp) + kSlotRankSpan); }
 static SlotMaps slot_maps(const reo_ctx *c)
 {
     SlotMaps m;
     const size_t Gp = static_cast<size_t>(c->Gp);
-    m.gmm = c->k1_slot_maps.p; m.key = m.gmm + 2 * Gp; m.g2s = m.key + Gp; m.s2g = m.g2s + Gp;
-    m.trng = m.s2g + Gp; m.crng = m.trng + Gp / 16;
+    m.gmm = c->k1_slot_maps.p; m.key = m.gmm + 2 * Gp; m.g2s = m.key + 2 * Gp; m.s2g = m.g2s + 2 * Gp;
+    m.trng = m.s2g + 2 * Gp; m.crng = m.trng + Gp / 16;
     m.count = reinterpret_cast<unsigned long long *>(m.crng + Gp / 128);   // (an even number of words in front of it)
+    m.srt = m.count + 1;
     return m;
 }
 
@@ -4408,18 +4494,26 @@ static int32_t k1_slots_alloc(reo_ctx *c)
 }
 
 // in front of the pair kernel: ranges, keys, order, planes in slot order, tile and chunk ranges; a's operands become the slot form's
-static int32_t k1_slots_front(reo_ctx *c, K1Args &a)
+// (sides: 1 the common order, 2 an order per side -- k1_slot_sides)
+static int32_t k1_slots_front(reo_ctx *c, K1Args &a, int sides)
 {
     const int G = a.G, Gp = a.Gp, nblk = c->goff32[2] / 32;
     const SlotMaps m = slot_maps(c);
-    const unsigned gb = static_cast<unsigned>((G + 255) / 256);
-    REO_HIP_CHECK(hipMemsetAsync(m.g2s, 0, static_cast<size_t>(Gp) * 2 * sizeof(uint32_t), c->stream));   // (g2s is summed up; s2g: no stray index, whatever happens)
+    const unsigned gb = static_cast<unsigned>((G + 255) / 256), zs = static_cast<unsigned>(sides);
+    REO_HIP_CHECK(hipMemsetAsync(m.g2s, 0, static_cast<size_t>(Gp) * 4 * sizeof(uint32_t), c->stream));   // (g2s is summed up; s2g: no stray index, whatever happens)
     k1_slot_part<<<dim3(gb, kSlotSplits, 2), 256, 0, c->stream>>>(c->t_pos16.p, Gp, G, a.cb * 32, a.nc, a.tb * 32, a.nt, c->k1_slot_part.p);
-    k1_slot_keys<<<gb, 256, 0, c->stream>>>(c->k1_slot_part.p, Gp, G, m.gmm, m.key);
-    k1_slot_rank<<<dim3(gb, static_cast<unsigned>((G + kSlotRankSpan - 1) / kSlotRankSpan)), 256, 0, c->stream>>>(m.key, G, m.g2s);
-    k1_slot_invert<<<static_cast<unsigned>(Gp / 256), 256, 0, c->stream>>>(m.g2s, m.s2g, G, Gp);
+    k1_slot_keys<<<gb, 256, 0, c->stream>>>(c->k1_slot_part.p, Gp, G, sides, m.gmm, m.key);
+    const unsigned spans = static_cast<unsigned>((G + kSlotRankSpan - 1) / kSlotRankSpan);   // (spans * kSlotRankSpan <= Gp + kSlotRankSpan: slot_maps_words)
+    if (slot_order_key32_fits(G)) {
+        k1_slot_sort<true><<<dim3(spans, zs), kSlotRankSpan / 2, 0, c->stream>>>(m.key, G, Gp, m.srt);
+        k1_slot_rank<true><<<dim3(gb, spans, zs), 256, 0, c->stream>>>(m.key, m.srt, G, Gp, m.g2s);
+    } else {
+        k1_slot_sort<false><<<dim3(spans, zs), kSlotRankSpan / 2, 0, c->stream>>>(m.key, G, Gp, m.srt);
+        k1_slot_rank<false><<<dim3(gb, spans, zs), 256, 0, c->stream>>>(m.key, m.srt, G, Gp, m.g2s);
+    }
+    k1_slot_invert<<<dim3(static_cast<unsigned>(Gp / 256), zs), 256, 0, c->stream>>>(m.g2s, m.s2g, G, Gp, sides);
     k1_slot_ranges<<<dim3(static_cast<unsigned>(Gp / 256), 2), 256, 0, c->stream>>>(m.gmm, m.s2g, G, Gp, m.trng, m.crng);
-    k1_slot_gather<<<dim3(static_cast<unsigned>(Gp / 256), static_cast<unsigned>(nblk)), 256, 0, c->stream>>>(c->pos.p, c->lo.p, m.s2g, Gp, c->pos_s.p, c->lo_s.p);
+    k1_slot_gather<<<dim3(static_cast<unsigned>(Gp / 256), static_cast<unsigned>(nblk)), 256, 0, c->stream>>>(c->pos.p, c->lo.p, m.s2g, Gp, a.cb, a.ce, c->pos_s.p, c->lo_s.p);
     REO_HIP_CHECK(hipGetLastError());
     a.P = c->pos_s.p; a.AL = c->lo_s.p; a.AH = c->lo_s.p;   // (the tie-free form reads no hi planes)
     a.s2g = m.s2g; a.trng = m.trng; a.crng = m.crng;
@@ -4433,7 +4527,7 @@ static int32_t k1_slots_front(reo_ctx *c, K1Args &a)
 }
 
 // behind it: the table's columns back into gene order (its rows were written in gene order)
-static int32_t k1_slots_back(reo_ctx *c, const K1Args &a)
+static int32_t k1_slots_back(reo_ctx *c, const K1Args &a, int sides)
 {
     // the word forms (k1_unslot_words; REO_K1_UNSLOT unset: the form of unslot_form; 8 or 4: that form wherever its LDS fits)
     if (c->k1_unslot != 0) {
@@ -4443,12 +4537,17 @@ static int32_t k1_slots_back(reo_ctx *c, const K1Args &a)
         if (lds <= kUnslotLdsLimit) {   // (a slot build has at most 65 535 genes: the narrow form always fits)
             auto go = [&](auto rtag) -> int32_t {
                 constexpr int R = decltype(rtag)::value;
-                const int bit = R == kUnslotWide ? 1 : 2;
-                if (!(c->k1_unslot_attr & bit)) {   // more than 64 KB of dynamic LDS: once per context and form
-                    REO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k1_unslot_words<R>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kUnslotLdsLimit)));
+                const int bit = (R == kUnslotWide ? 1 : 2) << (sides == 2 ? 2 : 0);
+                const void *fn = sides == 2 ? reinterpret_cast<const void *>(k1_unslot_pair<R>) : reinterpret_cast<const void *>(k1_unslot_words<R>);
+                if (!(c->k1_unslot_attr & bit)) {   // more than 64 KB of dynamic LDS: once per context, form and kernel
+                    REO_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kUnslotLdsLimit)));
                     c->k1_unslot_attr |= bit;
                 }
-                k1_unslot_words<R><<<static_cast<unsigned>((a.G + R - 1) / R), static_cast<unsigned>(unslot_threads(a.Wp)), lds, c->stream>>>(a.table, slot_maps(c).g2s, a.G, a.Wp);
+                const unsigned threads = static_cast<unsigned>(unslot_threads(a.Wp));
+                if (sides == 2)   // an order per side: 2R rows of a side's plane pair per workgroup, that side's g2s
+                    k1_unslot_pair<R><<<dim3(static_cast<unsigned>((a.G + 2 * R - 1) / (2 * R)), 2), threads, lds, c->stream>>>(a.table, slot_maps(c).g2s, a.G, a.Wp);
+                else
+                    k1_unslot_words<R><<<static_cast<unsigned>((a.G + R - 1) / R), threads, lds, c->stream>>>(a.table, slot_maps(c).g2s, a.G, a.Wp);
                 return REO_OK;
             };
             const int32_t rc = form == kUnslotWide ? go(std::integral_constant<int, kUnslotWide>{}) : go(std::integral_constant<int, kUnslotNarrow>{});
@@ -4458,7 +4557,8 @@ static int32_t k1_slots_back(reo_ctx *c, const K1Args &a)
             return REO_OK;
         }
     }
-    // the bit form (REO_K1_UNSLOT=0: the A/B partner of the word forms and the second opinion of the tests)
+    // the bit form (REO_K1_UNSLOT=0: the A/B partner of the word forms and the second opinion of the tests); it knows one map only
+    if (sides != 1) { set_error("the bit form of the column un-permute: the common slot order only"); return REO_EINVAL; }
     c->last_k1_unslot = 1;
     // rows per workgroup: as many as fit 60 KB of LDS (six up to 20 480 genes, four up to 30 720, two up to 61 440, else one).  60 and not
     // the 64 KB that a launch may ask for without a function attribute: 16 bytes x Gp / 32 per row and Gp a multiple of 1 024 make a row a
@@ -4521,7 +4621,7 @@ int32_t launch_k1(reo_ctx *c, int k, int sides, bool keep_table, const int32_t *
     if ((rc = upload_unit_map(c, units))) return rc;
     a.unit_map = c->unit_map.p;
     a.gate = gate;
-    if (!prepare) { c->last_k1_slots = 0; c->k1_slot_items = nullptr; c->k1_slot_items_n = 0; c->k1_slot_gp = 0; }
+    if (!prepare) { c->last_k1_slots = 0; c->last_k1_slot_sides = 0; c->k1_slot_items = nullptr; c->k1_slot_items_n = 0; c->k1_slot_gp = 0; }
     if ((range || prepare) && (sides != 1 && sides != 2)) { set_error("a range of sample blocks / a prepared launch: one side of the pair kernel"); return REO_EINVAL; }
     if (gate && (!pl.wave || pl.wide || pl.big)) { set_error("a gated launch of the pair kernel: wave form, at most 65535 genes and samples"); return REO_EINVAL; }
     c->x_pipelined = false;
@@ -4562,12 +4662,15 @@ int32_t launch_k1(reo_ctx *c, int k, int sides, bool keep_table, const int32_t *
     }
     if (a.stamps) k_time_mark<<<1, 64, 0, c->stream>>>(a.stamps + c->k1_items_n * 4);
     tic(c, 1);
-    if (pl.slots && (rc = k1_slots_front(c, a))) { toc(c); return rc; }
+    // ... with an order per side where the build is long enough to pay for it (k1_slots.h, slot_sides_wanted); the bit form of the
+    // un-permute has one map, so a build under REO_K1_UNSLOT=0 keeps the common order
+    const int slot_sides = !pl.slots ? 0 : (c->k1_unslot == 0 ? 1 : slot_sides_wanted(a.ce - a.cb, a.te - a.tb, c->k1_slot_sides));
+    if (pl.slots && (rc = k1_slots_front(c, a, slot_sides))) { toc(c); return rc; }
     dispatch_pairs(c, a, pl);
-    if (pl.slots && (rc = k1_slots_back(c, a))) { toc(c); return rc; }
+    if (pl.slots && (rc = k1_slots_back(c, a, slot_sides))) { toc(c); return rc; }
     toc(c);
     if (pl.slots) {
-        c->last_k1_slots = 1;
+        c->last_k1_slots = 1; c->last_k1_slot_sides = slot_sides;
         c->k1_slot_items = a.items; c->k1_slot_items_n = c->k1_items_n; c->k1_slot_gp = a.Gp;
     }
     if (a.stamps) k_time_mark<<<1, 64, 0, c->stream>>>(a.stamps + c->k1_items_n * 4 + 1);

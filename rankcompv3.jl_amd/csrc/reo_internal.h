@@ -265,13 +265,16 @@ struct reo_ctx {
     int last_k1_slots = 0;              // reo_get_info 25: the last build of the class table used the slot order
     int k1_unslot = -1;                 // REO_K1_UNSLOT: the column un-permute behind a slot build -- unset: the word form of unslot_form (k1_slots.h); 0: the bit form
                                         // (k1_unslot_columns; A/B, tests); 8 or 4: that word form wherever its LDS fits (tests)
+    int k1_slot_sides = 0;              // REO_K1_SLOT_SIDES: 1 one slot order for both sides everywhere, 2 an order per side wherever slot order runs with a word
+                                        // un-permute (A/B, tests); unset: per side from 16 sample blocks on (k1_slots.h, slot_sides_wanted)
+    int last_k1_slot_sides = 0;         // reo_get_info 30: 0 no slot build, 1 the common order, 2 an order per side
     int last_k1_unslot = 0;             // reo_get_info 28: the un-permute of the last build (0: no slot build; 1: the bit form; 8 or 4: the word forms)
-    int k1_unslot_attr = 0;             // word forms whose kernel has been given its LDS size (bit 0: wide, bit 1: narrow)
+    int k1_unslot_attr = 0;             // word forms whose kernel has been given its LDS size (bit 0: wide, bit 1: narrow; bits 2, 3: their pair forms)
     const uint32_t *k1_slot_items = nullptr;   // ... and its item list (one of k1_wave_items), for the count of separated items (reo_get_info 26)
     size_t k1_slot_items_n = 0;
     int k1_slot_gp = 0;                 // ... and the padded gene count its maps and ranges are laid out for
     reo::DevBuf<uint32_t> k1_slot_part; // [kSlotSplits][2][Gp] the sides' position ranges of every gene over a slice of the samples (min | max << 16)
-    reo::DevBuf<uint32_t> k1_slot_maps; // [2][Gp] ranges per side, [Gp] keys, [Gp] g2s, [Gp] s2g, [2][Gp / 32] tile ranges, [2][Gp / 256] chunk ranges, [2] a count
+    reo::DevBuf<uint32_t> k1_slot_maps; // [2][Gp] ranges per side, [2][Gp] keys, [2][Gp] g2s, [2][Gp] s2g, [2][Gp / 32] tile ranges, [2][Gp / 256] chunk ranges, [2] a count
     reo::DevBuf<uint4> pos_s, lo_s;     // the pos and lo planes in slot order (the layouts of pos and lo)
     // item queues of the slot form (kernels.hip, k1w_pairs_slots; index rules: k1_queue.h): resident waves take items from eight counters
     int k1_queue = 1;                   // REO_K1_QUEUE=0: one workgroup per item, as the identity order's kernels (A/B, tests)
