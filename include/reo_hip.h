@@ -388,6 +388,39 @@ int32_t reo_pair_support(reo_ctx *ctx, const int32_t *genes, int64_t n_genes,
                          int32_t *n_gt, int32_t *n_eq /* entries x ngroups, row-major; n_eq may be NULL */,
                          uint8_t *outcome /* entries x S, row-major, caller's column order; may be NULL */);
 
+/* Missing values: pair classes from the samples where BOTH genes were observed.  The reference drops every gene with a missing cell
+ * (dropmissing!, src/RankCompV3.jl:601) and the library refuses a NaN; with a validity mask V beside the resident matrix a pair (i, j) is
+ * compared in the samples where both values exist, and its stability is judged against the threshold of that many samples.
+ * For every i < j and every group g:  A_g = {s in g : V[i,s] and V[j,s]}, n_g = |A_g|;  gt_g = #{s in A_g : x_i > x_j, not tied},
+ * eq_g = #{s in A_g : tied} under the comparator of the resident element type, exactly as reo_pair_counts applies it;
+ * nre_g = gt_g + the keyed coins of (seed, i, j, g) for eq_g ties (the stream of reo_build_pairs).  For comparison k:
+ * a = nre_k, n1 = n_k, b = sum of nre_g over g != k, n2 = sum of n_g over g != k, m(n) = reo_threshold(n, pval_reo);
+ * ic = 2 if n1 < min_complete[0], else 3 if a >= m(n1), else 1 if n1 - a >= m(n1), else 2;  `it` likewise from b, n2, min_complete[1].
+ * The code of (i, j) is 3(ic-1)+(it-1), that of (j, i) 8 minus it.  A side with fewer than min_complete jointly observed samples is
+ * unstable, never "stable by unanimity of three samples".  With an all-ones mask and min_complete <= the side sizes the table equals that
+ * of reo_compute_thresholds(pval_reo) + reo_build_pairs(k) byte for byte, ties and coins included.
+ *
+ * reo_set_valid_mask: G x S bytes (nonzero = observed), column-major in the caller's column order, host memory, ld >= G; the shape must be
+ * the resident matrix's.  NULL clears the mask.  The bytes are kept on the device, so a later reo_set_groups needs nothing from the
+ * caller; a matrix of another shape drops the mask.  The matrix cell under an invalid byte is ignored, but it must still be a number
+ * the library accepts: NaN stays refused, the caller writes a filler.
+ * While a mask is set, reo_sample_counts, reo_sample_tests, reo_sample_calls, reo_pair_support and reo_build_pairs_contrast are refused
+ * (REO_EINVAL, a message that names the mask): they compare on the planes of the whole matrix and would count the fillers.  With no mask
+ * set, no call behaves differently.
+ *
+ * reo_build_pairs_masked builds the class table by the rule above and leaves the context as reo_build_pairs(k) leaves it (reo_get_info 29
+ * reads -1, the table is complete); it neither reads nor changes the context's thresholds.  reo_get_info 31 reads 1 while the resident
+ * table came from this call; any other build sets it back to 0.  reo_tally, reo_identify_degs, reo_get_ref_mask, reo_pair_list and
+ * reo_get_codes run on the table unchanged.
+ * reo_pair_counts_masked is the parity hook: n_gt, n_eq and n_avail (= n_g) of the rectangle [i0, i1) x [j0, j1) per group, int32, in the
+ * layout of reo_pair_counts ([i - i0][j - j0][g]); at most 2^28 counts per array and call.
+ * REO_EINVAL, each with its own message, and a refused call writes nothing: no mask, or none of the matrix's shape; min_complete < 1 or
+ * NULL; pval_reo outside (0, 1] (or 1, for which no threshold exists); k outside the groups; S > 65535; G > 65535 (the 16-plane layout
+ * only); a sharded context (reo_set_shard with more than one shard) or a reo_create_multi context. */
+int32_t reo_set_valid_mask(reo_ctx *ctx, const uint8_t *valid, int64_t G, int64_t S, int64_t ld);
+int32_t reo_build_pairs_masked(reo_ctx *ctx, int32_t k, double pval_reo, const int32_t *min_complete /* 2 */);
+int32_t reo_pair_counts_masked(reo_ctx *ctx, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int32_t *n_gt, int32_t *n_eq, int32_t *n_avail);
+
 /* Sample tests: is gene i UP OR DOWN IN ONE SAMPLE?  The tallies call a gene over the groups; this call tests one sample's orderings of
  * the gene against the pairs that are stable in the control group, with Fisher's exact test -- the individual-level question of the
  * RankComp family.  The reference has no such output.
@@ -621,7 +654,8 @@ int32_t reo_get_timings(reo_ctx *ctx, double *ms, int32_t n);
  * -1: every other sample, reo_build_pairs with more than two groups, and -1 while there is no table), 30 the slot orders of that
  * build (0: no slot build; 1: one order for both sides; 2: an order per side, the default where the two sides together have at least
  * 16 sample blocks of 32 and a word form puts the columns back; REO_K1_SLOT_SIDES=1 or 2 in the environment asks for that one
- * everywhere; the table is the same bit for bit under both). */
+ * everywhere; the table is the same bit for bit under both), 31 the resident class table came from reo_build_pairs_masked (1; any other
+ * build, and no table: 0). */
 int32_t reo_get_info(reo_ctx *ctx, int64_t *info, int32_t n);
 
 #ifdef __cplusplus

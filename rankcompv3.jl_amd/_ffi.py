@@ -34,7 +34,7 @@ SYMBOLS = [
     "reo_pseudobulk_dense_f64", "reo_pseudobulk_dense_i64", "reo_pseudobulk_csc_f64", "reo_pseudobulk_csc_i64",
     "reo_set_matrix_pseudobulk_dense_f64", "reo_set_matrix_pseudobulk_dense_i64", "reo_set_matrix_pseudobulk_csc_f64", "reo_set_matrix_pseudobulk_csc_i64",
     "reo_filter_matrix", "reo_get_matrix", "reo_get_ref_mask", "reo_pair_list", "reo_sample_counts", "reo_pair_support",
-    "reo_sample_tests", "reo_sample_calls",
+    "reo_sample_tests", "reo_sample_calls", "reo_set_valid_mask", "reo_build_pairs_masked", "reo_pair_counts_masked",
 ] +[f"reo_set_matrix_{form}_{t}" for form in ("csc_dev", "pseudobulk_csc_dev", "pseudobulk_dense_dev") for t in ("f64", "i64", "f32", "i32")]
 
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p)
@@ -144,6 +144,9 @@ def lib() -> ctypes.CDLL:
         "reo_pair_support": (i32, [vp, vp, i64, vp, vp, vp, vp, vp]),
         "reo_sample_tests": (i32, [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
         "reo_sample_calls": (i32, [vp, vp, i64, vp, f64, f64, vp, vp, vp, vp]),
+        "reo_set_valid_mask": (i32, [vp, vp, i64, i64, i64]),
+        "reo_build_pairs_masked": (i32, [vp, i32, f64, vp]),
+        "reo_pair_counts_masked": (i32, [vp, i64, i64, i64, i64, vp, vp, vp]),
     }
     for t in ("f64", "i64", "f32", "i32"):   # SPARSE ON THE DEVICE
         sig["reo_set_matrix_csc_dev_" + t] = (i32, [vp, i64, i64, i64, vp, vp, i32, vp])
@@ -277,6 +280,44 @@ def csc_entry(M):
     rowidx = np.ascontiguousarray(m.indices, dtype=np.int32)
     colptr = np.ascontiguousarray(m.indptr, dtype=np.int64)
     return "reo_set_matrix_csc_" + _NATIVE[want], colptr, rowidx, val, int(G), int(S)
+
+
+def valid_mask_bytes(valid, shape) -> np.ndarray:
+    """A validity mask as the column-major uint8 array (0 / 1) that reo_set_valid_mask reads.  Pure: no library, no GPU.  Anything
+    np.asarray takes; nonzero / True = observed.  A mask whose shape is not `shape` (genes x samples) raises DimensionMismatch."""
+    v = np.asarray(valid)
+    if v.ndim != 2 or tuple(v.shape) != tuple(int(n) for n in shape):
+        raise DimensionMismatch(REO_EINVAL, f"valid mask has shape {tuple(v.shape)}, the matrix is {tuple(int(n) for n in shape)} (genes x samples)")
+    return np.asfortranarray(v != 0, dtype=np.uint8)
+
+
+def first_informative_n(pval_reo: float) -> int:
+    """The smallest n with min(1, 2 * 0.5**n) < pval_reo: the first sample count at which reo_threshold leaves its fallback branch
+    (8 at 0.01).  Pure."""
+    p = float(pval_reo)
+    if not 0.0 < p <= 1.0:
+        raise DimensionMismatch(REO_EINVAL, f"pval_reo = {pval_reo!r} is outside (0, 1]")
+    n = 1
+    while n < 2000 and not min(1.0, 2.0 * 0.5 ** n) < p:
+        n += 1
+    return n
+
+
+def resolve_min_complete(min_complete, side_sizes, pval_reo: float):
+    """The two integers of reo_build_pairs_masked.  Pure.  None: per side min(side size, first_informative_n(pval_reo)), at least 1; an
+    int applies to both sides; a pair is taken as it is.  Anything below 1 raises DimensionMismatch."""
+    if min_complete is None:
+        n = first_informative_n(pval_reo)
+        return tuple(max(1, min(int(s), n)) for s in side_sizes)
+    if isinstance(min_complete, (int, np.integer)) and not isinstance(min_complete, (bool, np.bool_)):
+        mc = (int(min_complete), int(min_complete))
+    else:
+        mc = tuple(int(m) for m in min_complete)
+        if len(mc) != 2:
+            raise DimensionMismatch(REO_EINVAL, f"min_complete = {min_complete!r}: None, an int or one int per side")
+    if mc[0] < 1 or mc[1] < 1:
+        raise DimensionMismatch(REO_EINVAL, f"min_complete = {mc}: each side needs at least 1 jointly observed sample")
+    return mc
 
 
 # the nine classes of an ordered pair in the order of their codes 3*(ic-1)+(it-1): the tally columns of the result (hotpath.HEADER[2:11])
@@ -725,6 +766,40 @@ class Context:
         check(self._L.reo_pair_counts(self._h, i0, i1, j0, j1, _ptr(gt), _ptr(eq)))
         return gt, eq
 
+    # -- missing values ---------------------------------------------------------
+    def set_valid_mask(self, valid) -> None:
+        """reo_set_valid_mask: a G x S validity mask (nonzero / True = observed) beside the resident matrix, in the caller's column
+        order; None clears it.  The cell under an invalid entry is ignored by build_pairs_masked but must still be a number (NaN stays
+        refused).  While a mask is set, sample_counts, sample_tests, sample_calls, pair_support and build_contrast are refused."""
+        if valid is None:
+            check(self._L.reo_set_valid_mask(self._h, None, 0, 0, 0))
+            return
+        v = valid_mask_bytes(valid, (self.G, self.S))
+        check(self._L.reo_set_valid_mask(self._h, _ptr(v), v.shape[0], v.shape[1], max(v.shape[0], 1)))
+
+    def side_sizes(self, k: int = 0):
+        """(samples of group k, every other sample) under the labels of set_groups."""
+        n1 = int(np.count_nonzero(self._group_id == int(k)))
+        return n1, int(self._group_id.size) - n1
+
+    def build_pairs_masked(self, k: int = 0, pval_reo: float = 0.01, min_complete=None):
+        """reo_build_pairs_masked: the class table of comparison k from the samples where both genes of a pair are valid under the mask
+        of set_valid_mask, each side judged against reo_threshold(jointly valid samples of the side, pval_reo); a side with fewer than
+        min_complete such samples is unstable.  min_complete: None (per side min(side size, the first n at which the threshold leaves
+        its fallback branch: 8 at 0.01)), an int for both sides, or a pair.  Returns the two integers used.  The context's thresholds
+        are neither read nor changed."""
+        mc = resolve_min_complete(min_complete, self.side_sizes(k), pval_reo)
+        arr = np.asarray(mc, dtype=np.int32)
+        check(self._L.reo_build_pairs_masked(self._h, int(k), float(pval_reo), _ptr(arr)))
+        return mc
+
+    def pair_counts_masked(self, i0: int, i1: int, j0: int, j1: int):
+        """reo_pair_counts_masked (parity hook): (n_gt, n_eq, n_avail), int32, each (i1 - i0) x (j1 - j0) x ngroups."""
+        shape = (i1 - i0, j1 - j0, max(self.ngroups, 1))
+        gt, eq, av = (np.zeros(shape, dtype=np.int32) for _ in range(3))
+        check(self._L.reo_pair_counts_masked(self._h, i0, i1, j0, j1, _ptr(gt), _ptr(eq), _ptr(av)))
+        return gt, eq, av
+
     def get_codes(self, i0: int, i1: int, j0: int, j1: int) -> np.ndarray:
         code = np.zeros((i1 - i0, j1 - j0), dtype=np.uint8)
         check(self._L.reo_get_codes(self._h, i0, i1, j0, j1, _ptr(code)))
@@ -983,8 +1058,8 @@ class Context:
                 "k2_full_launches": int(ms[9]), "k2_delta_ms": ms[10], "set_matrix_host_wall_ms": ms[11]}
 
     def info(self) -> dict:
-        w = np.zeros(31, dtype=np.int64)
-        check(self._L.reo_get_info(self._h, _ptr(w), 31))
+        w = np.zeros(32, dtype=np.int64)
+        check(self._L.reo_get_info(self._h, _ptr(w), 32))
         v = np.zeros(28, dtype=np.int64)   # fields 0-27 keep their places (tests/test_csc_device_cpu.py reads this line); 28 is appended
         v[:] = w[:28]
         return {"G": int(v[0]), "S": int(v[1]), "Gp": int(v[2]), "table_bytes": int(v[3]), "has_ties": int(v[4]),
@@ -995,4 +1070,5 @@ class Context:
                 "eager_range_launches": int(v[20]), "rowmajor_upload": int(v[21]),
                 "csc_upload": int(v[22]), "csc_nnz": int(v[23]), "resident_dtype": int(v[24]),
                 "k1_slot_order": int(v[25]), "k1_half_tiles_separated": int(v[26]), "csc_device": int(v[27]),
-                "k1_unslot_form": int(w[28]), "contrast_treat": int(w[29]), "k1_slot_sides": int(w[30])}
+                "k1_unslot_form": int(w[28]), "contrast_treat": int(w[29]), "k1_slot_sides": int(w[30]),
+                "masked_build": int(w[31])}

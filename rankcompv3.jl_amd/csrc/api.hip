@@ -15,6 +15,8 @@
 
 #include "reo_internal.h"
 #include "contrast.h"
+#include "masked_pairs.h"
+#include "sample_counts.h"
 #include "upload_csc.h"
 
 #include <mutex>
@@ -228,32 +230,8 @@ void collect_timings(reo_ctx *c)
     c->k2_seen = 0;
 }
 
-// get_major_reo_lower_count, src/RankCompV3.jl:81-92, with
-// pvalue(Binomial(n, 1/2), x; tail = :both) = min(1, 2 min(ccdf(x-1), cdf(x)))
-// (HypothesisTests, call sites :83,85).  The cdf is accumulated term by term in
-// long double, pmf(t) = exp(log C(n,t) - n ln 2), so the scan over x is O(n).
-static int32_t major_reo_lower_count(int32_t n, double thr)
-{
-    const long double ln2 = 0.693147180559945309417232121458L;
-    long double logc = 0.0L, cdf_prev = 0.0L;  // cdf(x-1)
-    int32_t first_above = -1;
-    double pmin = 1.0;
-    for (int x = 0; x <= n / 2; ++x) {
-        if (x > 0) logc += std::log(static_cast<long double>(n - x + 1)) - std::log(static_cast<long double>(x));
-        long double cdf = x >= n ? 1.0L : cdf_prev + std::exp(logc - static_cast<long double>(n) * ln2);
-        if (cdf > 1.0L) cdf = 1.0L;
-        const long double hi = 1.0L - cdf_prev;
-        long double p = 2.0L * (cdf < hi ? cdf : hi);
-        if (p > 1.0L) p = 1.0L;
-        if (x == 0) {
-            pmin = static_cast<double>(p);
-            if (!(pmin < thr)) return n;  // the WARN branch (:87-90)
-        }
-        if (static_cast<double>(p) > thr) { first_above = x; break; }
-        cdf_prev = cdf;
-    }
-    return first_above < 0 ? -1 : n - first_above + 1;  // -idx + 2 + n with idx = x + 1
-}
+// get_major_reo_lower_count (src/RankCompV3.jl:81-92): masked_pairs.h, which tabulates it for the masked build as well
+static int32_t major_reo_lower_count(int32_t n, double thr) { return reo_lower_count(n, thr); }
 
 // Host wait for the stream on the hot path.  REO_SPIN_WAIT=1 polls the stream instead of the blocking wait; measured on
 // the bench step (tools/step_breakdown.py, round 3): 6.05 against 6.10 ms -- the host-side gaps of a step are not the
@@ -346,6 +324,23 @@ int32_t no_multi(reo_ctx *c, const char *what)
     return REO_OK;
 }
 
+// The validity mask of reo_set_valid_mask, if it is still the mask of the resident matrix: a matrix of another shape drops it.
+bool mask_in_force(reo_ctx *c)
+{
+    if (c->vmask_set && (c->vmask_G != c->G || c->vmask_S != c->S)) { c->vmask_set = false; c->vwords_valid = false; }
+    return c->vmask_set;
+}
+
+// What the calls that compare on the bit planes answer while a mask is set: they would count the fillers under the invalid cells.
+int32_t refuse_under_mask(reo_ctx *c, const char *what)
+{
+    if (!c || !mask_in_force(c)) return REO_OK;
+    char msg[320];
+    mp_query_refusal(what, msg, sizeof msg);
+    set_error("%s", msg);
+    return REO_EINVAL;
+}
+
 static void invalidate(reo_ctx *c)
 {
     drop_ref_mask(c, "the matrix or the groups changed after the last reo_identify_degs (reo_set_matrix_*, reo_filter_matrix, reo_set_groups): "
@@ -353,8 +348,13 @@ static void invalidate(reo_ctx *c)
     c->transformed = false;
     c->built_k = -1;
     c->built_treat = -1;
+    c->built_masked = 0;
     c->gc_valid = false;
     c->eager_k1 = false;
+    // the validity words follow the sample slots of the groups; the mask itself stays (reo_set_groups needs nothing from the caller) unless
+    // the matrix that is being replaced already had another shape than the mask's
+    c->vwords_valid = false;
+    (void)mask_in_force(c);
     // no class table any more: nothing is left of a build in slot order either (reo_get_info 25, 26 read 0; the maps and the item list that
     // field 26 would count over belong to the old geometry)
     c->last_k1_slots = 0; c->last_k1_slot_sides = 0; c->k1_slot_items = nullptr; c->k1_slot_items_n = 0; c->k1_slot_gp = 0;
@@ -598,7 +598,7 @@ using namespace reo;
 
 extern "C" {
 
-int32_t reo_version(void) { return 1100; }
+int32_t reo_version(void) { return 1200; }
 
 int32_t reo_trim_memory(void)
 {
@@ -1067,6 +1067,7 @@ static int32_t enqueue_local(reo_ctx *c, int32_t k, int32_t treat = -1)
     if ((rc = c->table.ensure(static_cast<size_t>(c->G) * kPlanes * c->Wp))) return rc;
     c->built_k = -1;
     c->built_treat = -1;
+    c->built_masked = 0;
     return launch_k1(c, k, 3, false, nullptr, nullptr, false, treat);
 }
 
@@ -1143,6 +1144,8 @@ int32_t reo_build_pairs_contrast(reo_ctx *c, int32_t ctrl, int32_t treat)
     // every refusal first, from what the context already knows: a refused call leaves the table and the reference mask as they were
     char msg[320];
     ContrastState st{};
+    int32_t rcm = refuse_under_mask(c, "reo_build_pairs_contrast");
+    if (rcm) return rcm;
     if (c) {
         st.ngroups = c->ngroups; st.thr_set = c->thr_set; st.multi_device = c->in_multi || !c->peers.empty();
         st.S = c->S; st.share_counts = c->share_counts != 0; st.planes_fit = true; st.planes_bytes = 0;
@@ -1184,6 +1187,120 @@ int32_t reo_pair_counts(reo_ctx *c, int64_t i0, int64_t i1, int64_t j0, int64_t 
     }
     dg.release(); de.release();
     return rc;
+}
+
+// ---- missing values: a validity mask beside the resident matrix (kernels: maskedpairs.hip; rules and checks: masked_pairs.h) ----
+
+static MpState mp_state(reo_ctx *c)
+{
+    MpState st{};
+    st.multi = c->in_multi || !c->peers.empty();
+    st.world = c->world;
+    st.G = c->dtype ? c->G : 0; st.S = c->dtype ? c->S : 0;
+    st.ngroups = c->ngroups;
+    st.has_mask = mask_in_force(c);
+    return st;
+}
+
+// The validity words of the current groups in c->vwords (made once per mask and set of labels), behind ensure_transform.
+static int32_t ensure_valid_words(reo_ctx *c, const char *what)
+{
+    if (c->vwords_valid && c->vwords.p) return REO_OK;
+    std::vector<int32_t> map;
+    if (!sc_slot_map(c->group_id.data(), c->S, c->ngroups, map) || c->goff32.empty() || static_cast<int64_t>(map.size()) != c->goff32.back()) {
+        set_error("%s: the sample slots of the bit planes do not match the group labels", what);
+        return REO_EHIP;
+    }
+    int32_t rc;
+    if ((rc = c->sc_slot2col.ensure(map.size())) || (rc = c->vwords.ensure(map.size() / 32 * static_cast<size_t>(c->Gp)))) return rc;
+    if ((rc = upload_slot2col(c, map)) || (rc = launch_valid_words(c, c->sc_slot2col.p))) return rc;
+    c->vwords_valid = true;
+    return REO_OK;
+}
+
+int32_t reo_set_valid_mask(reo_ctx *c, const uint8_t *valid, int64_t G, int64_t S, int64_t ld)
+{
+    int32_t rc = use(c);
+    if (rc) return rc;
+    if (!valid) { c->vmask_set = false; c->vwords_valid = false; return REO_OK; }
+    char msg[320];
+    if (mp_check_mask_args(mp_state(c), G, S, ld, msg, sizeof msg)) { set_error("%s", msg); return REO_EINVAL; }
+    REO_HIP_CHECK(stream_wait(c));   // (a masked build still reading the old bytes)
+    if ((rc = c->vmask.ensure(static_cast<size_t>(G) * S))) { c->vmask_set = false; c->vwords_valid = false; return rc; }
+    c->vmask_set = false; c->vwords_valid = false;
+    DrainOnExit drain(c);   // valid in
+    REO_HIP_CHECK(hipMemcpy2DAsync(c->vmask.p, static_cast<size_t>(G), valid, static_cast<size_t>(ld), static_cast<size_t>(G), static_cast<size_t>(S),
+                                   hipMemcpyHostToDevice, c->stream));
+    REO_HIP_CHECK(hipStreamSynchronize(c->stream));
+    drain.dismiss();
+    c->vmask_set = true; c->vmask_G = G; c->vmask_S = S;
+    return REO_OK;
+}
+
+int32_t reo_build_pairs_masked(reo_ctx *c, int32_t k, double pval_reo, const int32_t *min_complete)
+{
+    int32_t rc = use(c);
+    if (rc) return rc;
+    // every refusal first: a refused call leaves the table, the reference mask and the context's thresholds as they were
+    const MpState st = mp_state(c);
+    if (!st.multi && st.world <= 1 && (c->dtype == 0 || c->group_id.empty() || static_cast<int64_t>(c->group_id.size()) != c->S))
+        return ensure_transform(c);   // (its refusals: nothing runs)
+    char msg[320];
+    if (mp_check_build_args(st, k, pval_reo, min_complete, msg, sizeof msg)) { set_error("%s", msg); return REO_EINVAL; }
+    int32_t n1 = 0;
+    for (int32_t g : c->group_id) n1 += g == k;
+    const int32_t n2 = static_cast<int32_t>(c->S) - n1;
+    if (c->mp_thr_n[0] != n1 || c->mp_thr_n[1] != n2 || c->mp_thr_pval != pval_reo || c->mp_thr_host.size() != static_cast<size_t>(n1) + n2 + 2) {
+        std::vector<int32_t> m1, m2;
+        if (!mp_threshold_table(n1, pval_reo, m1) || !mp_threshold_table(n2, pval_reo, m2)) {
+            set_error("reo_build_pairs_masked: no count in 0..n/2 has a two-sided binomial p above %g (the reference's findfirst returns nothing)", pval_reo);
+            return REO_EINVAL;
+        }
+        c->mp_thr_host = m1;
+        c->mp_thr_host.insert(c->mp_thr_host.end(), m2.begin(), m2.end());
+        c->mp_thr_n[0] = n1; c->mp_thr_n[1] = n2; c->mp_thr_pval = pval_reo;
+        c->mp_thr_uploaded = nullptr;
+    }
+    if ((rc = ensure_transform(c))) return rc;
+    if ((rc = c->table.ensure(static_cast<size_t>(c->G) * kPlanes * c->Wp)) || (rc = c->mp_thr.ensure(c->mp_thr_host.size()))) return rc;
+    if (c->mp_thr_uploaded != c->mp_thr.p) {
+        REO_HIP_CHECK(hipMemcpyAsync(c->mp_thr.p, c->mp_thr_host.data(), c->mp_thr_host.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        REO_HIP_CHECK(hipStreamSynchronize(c->stream));
+        c->mp_thr_uploaded = c->mp_thr.p;
+    }
+    if ((rc = ensure_valid_words(c, "reo_build_pairs_masked"))) return rc;
+    drop_ref_mask(c, "reo_build_pairs_masked has replaced the class table that the last reo_identify_degs ran on: no reo_identify_degs has run on the current one");
+    c->built_k = -1; c->built_treat = -1; c->built_masked = 0; c->eager_k1 = false; c->table_complete = false;
+    c->last_k1_slots = 0; c->last_k1_slot_sides = 0; c->k1_slot_items = nullptr; c->k1_slot_items_n = 0; c->k1_slot_gp = 0; c->last_k1_shared = 0;
+    REO_HIP_CHECK(hipMemsetAsync(c->table.p, 0, static_cast<size_t>(c->G) * kPlanes * c->Wp * sizeof(uint32_t), c->stream));
+    c->table_prezeroed = false;
+    if ((rc = launch_pairs_masked(c, k, c->mp_thr.p, n1, c->mp_thr.p + n1 + 1, n2, min_complete[0], min_complete[1]))) return rc;
+    // one GPU, nothing to exchange: the kernel is left running, as by reo_build_pairs; a failure surfaces at the next wait
+    c->built_k = k; c->built_masked = 1; c->table_complete = true;
+    return REO_OK;
+}
+
+int32_t reo_pair_counts_masked(reo_ctx *c, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int32_t *n_gt, int32_t *n_eq, int32_t *n_avail)
+{
+    int32_t rc = use(c);
+    if (rc) return rc;
+    const MpState st = mp_state(c);
+    if (!st.multi && st.world <= 1 && (c->dtype == 0 || c->group_id.empty() || static_cast<int64_t>(c->group_id.size()) != c->S))
+        return ensure_transform(c);   // (its refusals: nothing runs)
+    char msg[320];
+    if (mp_check_counts_args(st, i0, i1, j0, j1, n_gt, n_eq, n_avail, msg, sizeof msg)) { set_error("%s", msg); return REO_EINVAL; }
+    if ((rc = ensure_transform(c)) || (rc = ensure_valid_words(c, "reo_pair_counts_masked"))) return rc;
+    const size_t n = static_cast<size_t>(i1 - i0) * (j1 - j0) * c->ngroups;
+    DevBuf<int32_t> dg, de, da;
+    if ((rc = dg.ensure(n)) || (rc = de.ensure(n)) || (rc = da.ensure(n))) return rc;
+    DrainOnExit drain(c);   // (declared after the buffers: the wait comes before their release)
+    if ((rc = launch_counts_masked(c, i0, i1, j0, j1, dg.p, de.p, da.p))) return rc;
+    REO_HIP_CHECK(hipMemcpyAsync(n_gt, dg.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    REO_HIP_CHECK(hipMemcpyAsync(n_eq, de.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    REO_HIP_CHECK(hipMemcpyAsync(n_avail, da.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = wait_or_drop_table(c))) return rc;
+    drain.dismiss();
+    return REO_OK;
 }
 
 int32_t reo_get_codes(reo_ctx *c, int64_t i0, int64_t i1, int64_t j0, int64_t j1, uint8_t *code)
@@ -1504,15 +1621,15 @@ int32_t reo_get_info(reo_ctx *c, int64_t *info, int32_t n)
         int32_t rc = use(c);
         if (rc || (rc = launch_slot_separated(c, &separated))) return rc;
     }
-    const int64_t v[31] = {c->G, c->S, c->Gp, static_cast<int64_t>(c->table.n * sizeof(uint32_t)), c->has_ties,
+    const int64_t v[32] = {c->G, c->S, c->Gp, static_cast<int64_t>(c->table.n * sizeof(uint32_t)), c->has_ties,
                            c->tiles_owned, c->tiles_total, kTileI, c->k1_cj, c->k1_q, kUnitH,
                            c->goff32.empty() ? 0 : c->goff32.back(), c->last_k1_shared,
                            static_cast<int64_t>(c->gcounts.n * sizeof(uint16_t)), c->transform_in_lds, c->xcc_local,
                            c->it_cycle_period, c->it_cycle_at, c->it_cycle_skipped, c->narrowed_bytes, c->eager_range_launches, c->rowmajor_upload,
                            c->csc_upload, c->csc_nnz, c->dtype, c->last_k1_slots, separated, c->csc_device,
                            c->last_k1_slots ? c->last_k1_unslot : 0, c->built_k >= 0 ? c->built_treat : -1,
-                           c->last_k1_slots ? c->last_k1_slot_sides : 0};
-    for (int i = 0; i < n && i < 31; ++i) info[i] = v[i];
+                           c->last_k1_slots ? c->last_k1_slot_sides : 0, (c->built_k >= 0 && c->built_masked) ? 1 : 0};
+    for (int i = 0; i < n && i < 32; ++i) info[i] = v[i];
     return REO_OK;
 }
 

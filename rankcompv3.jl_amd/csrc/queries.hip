@@ -136,7 +136,7 @@ int32_t reo_sample_counts(reo_ctx *c, const int32_t *genes, int64_t n_genes, con
                           int32_t *n_gt, int32_t *n_eq)
 {
     int32_t rc = begin_query(c, "reo_sample_counts", true);
-    if (rc) return rc;
+    if (rc || (rc = refuse_under_mask(c, "reo_sample_counts"))) return rc;
     char msg[320];
     if (sample_counts_check_args(c->G, genes, n_genes, class_mask, n_gt, msg, sizeof msg)) { set_error("%s", msg); return REO_EINVAL; }
     if ((rc = need_partner_set(c, "reo_sample_counts", partner_mask))) return rc;
@@ -175,7 +175,7 @@ int32_t reo_sample_tests(reo_ctx *c, const int32_t *genes, int64_t n_genes, cons
                          int32_t *n_below_ctrl, int32_t *rev_up, int32_t *rev_down, int32_t *tied, double *p_up, double *p_down)
 {
     int32_t rc = begin_query(c, "reo_sample_tests", true);
-    if (rc) return rc;
+    if (rc || (rc = refuse_under_mask(c, "reo_sample_tests"))) return rc;
     char msg[320];
     if (sample_tests_check_args(c->G, genes, n_genes, p_up, p_down, msg, sizeof msg)) { set_error("%s", msg); return REO_EINVAL; }
     if ((rc = need_partner_set(c, "reo_sample_tests", partner_mask))) return rc;
@@ -242,7 +242,7 @@ int32_t reo_sample_calls(reo_ctx *c, const int32_t *genes, int64_t n_genes, cons
                          int8_t *calls, int32_t *cut, int32_t *n_up, int32_t *n_down)
 {
     int32_t rc = begin_query(c, "reo_sample_calls", true);
-    if (rc) return rc;
+    if (rc || (rc = refuse_under_mask(c, "reo_sample_calls"))) return rc;
     char msg[320];
     if (sample_calls_check_args(c->G, genes, n_genes, pval_deg, padj_deg, calls, msg, sizeof msg)) { set_error("%s", msg); return REO_EINVAL; }
     if ((rc = need_partner_set(c, "reo_sample_calls", partner_mask))) return rc;
@@ -320,7 +320,7 @@ int32_t reo_pair_support(reo_ctx *c, const int32_t *genes, int64_t n_genes, cons
                          int32_t *n_eq, uint8_t *outcome)
 {
     int32_t rc = begin_query(c, "reo_pair_support", false);
-    if (rc) return rc;
+    if (rc || (rc = refuse_under_mask(c, "reo_pair_support"))) return rc;
     if (c->dtype == 0 || c->group_id.empty() || static_cast<int64_t>(c->group_id.size()) != c->S) return ensure_transform(c);   // (its refusals: nothing runs)
     char msg[320];
     if (pair_support_check_args(c->G, genes, n_genes, rowptr, partner, n_gt, msg, sizeof msg)) { set_error("%s", msg); return REO_EINVAL; }

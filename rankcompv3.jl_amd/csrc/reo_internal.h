@@ -318,6 +318,18 @@ struct reo_ctx {
     // reo_sample_tests: the log-factorial table lf[0 .. 2 (G - 1)] (sample_tests.h), uploaded once and rebuilt when G changes
     reo::DevBuf<double> st_lf;
     int64_t st_lf_G = -1;               // the G it was built for (-1: none)
+    // missing values (reo_set_valid_mask, reo_build_pairs_masked; maskedpairs.hip, masked_pairs.h)
+    reo::DevBuf<uint8_t> vmask;         // [S][G] the validity bytes, column-major in the caller's column order (nonzero = observed)
+    bool vmask_set = false;
+    int64_t vmask_G = 0, vmask_S = 0;   // the shape it was set for: a matrix of another shape drops it (api.hip, mask_in_force)
+    reo::DevBuf<uint32_t> vwords;       // [sample blocks][Gp] one validity word per block of 32 sample slots and gene, in slot order
+    bool vwords_valid = false;          // ... made from vmask under the current groups (set_groups and a new mask clear it)
+    reo::DevBuf<int32_t> mp_thr;        // m(0 .. n1) then m(0 .. n2): the thresholds of every number of jointly observed samples per side
+    std::vector<int32_t> mp_thr_host;   // what it holds ...
+    int32_t mp_thr_n[2] = {-1, -1};     // ... for these side sizes ...
+    double mp_thr_pval = -1.0;          // ... and this pval_reo
+    const int32_t *mp_thr_uploaded = nullptr;   // ... and in which allocation
+    int built_masked = 0;               // reo_get_info 31: the resident class table came from reo_build_pairs_masked
     reo::DevBuf<int32_t> raw;           // [G][8]
     reo::DevBuf<uint32_t> delta_list;   // [2][Gp] changed genes (gene << 1 | added) per pass parity
     reo::DevBuf<int32_t> cont;          // [G][9]
@@ -456,6 +468,14 @@ struct PsItem;
 int32_t launch_pair_support(reo_ctx *c, const PsItem *d_items, int64_t n_items, const int32_t *d_partner, const int32_t *d_slot2col,
                             int32_t *d_gt, int32_t *d_eq, uint8_t *d_outcome);
 
+// maskedpairs.hip: the kernels of reo_set_valid_mask / reo_build_pairs_masked / reo_pair_counts_masked (shared arithmetic and host checks:
+// masked_pairs.h).  launch_valid_words: c->vmask and d_slot2col ([32 * sample blocks], -1 for padding) into c->vwords (sized by the
+// caller).  launch_pairs_masked: the class table of comparison k from the planes and c->vwords (the caller has cleared the table);
+// d_m1 / d_m2: the thresholds m(0 .. n1) / m(0 .. n2) of the two sides.  launch_counts_masked: the rectangle layout of launch_counts, int32
+int32_t launch_valid_words(reo_ctx *c, const int32_t *d_slot2col);
+int32_t launch_pairs_masked(reo_ctx *c, int k, const int32_t *d_m1, int n1, const int32_t *d_m2, int n2, int min_complete1, int min_complete2);
+int32_t launch_counts_masked(reo_ctx *c, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int32_t *d_gt, int32_t *d_eq, int32_t *d_avail);
+
 // pseudobulk.hip: the checks, upload and kernels of reo_pseudobulk_*, the G x n_out sums left in c->dX_owned (ld = G) instead of a host array
 int32_t pseudobulk_resident_dense(reo_ctx *c, const void *X, bool is_int, int64_t G, int64_t C, int64_t ld, const int32_t *order,
                                   int64_t n_order, const int32_t *chunk_ptr, int32_t n_out);
@@ -492,6 +512,8 @@ int32_t no_multi(reo_ctx *c, const char *what);        // `what` refuses a reo_c
 int32_t need_complete_table(reo_ctx *c);               // a class table, and every shard's part of it
 int32_t ensure_transform(reo_ctx *c);                  // matrix and groups set and of one size; the bit planes made if they are not in place
 int32_t wait_or_drop_table(reo_ctx *c);                // the stream wait of a call that may be the first to see a failed pair kernel
+bool mask_in_force(reo_ctx *c);                        // a validity mask is set and has the resident matrix's shape (another shape drops it)
+int32_t refuse_under_mask(reo_ctx *c, const char *what);   // `what` compares on the bit planes: refused while a validity mask is set
 // The slot -> column map of sc_slot_map (sample_counts.h) into c->sc_slot2col (already sized by the caller), on the stream
 int32_t upload_slot2col(reo_ctx *c, const std::vector<int32_t> &map);
 // Every call that enqueues an asynchronous copy from or into CALLER memory (or a local) holds one of these: whatever way the call

@@ -212,10 +212,54 @@ def write_pairs_tsv(path, gene_names, pair_list) -> None:
                 f.write(f"{gname}\t{gene_names[int(j)]}\t{names[int(c)]}\n")
 
 
+def missing_plan(data, missing, valid, *, shard=(0, 1), contrasts=None, sample_scores=False, sample_tests=False, sample_calls=False,
+                 pair_support=False):
+    """The pairwise route of run_identify_degs, decided before any context is opened.  Pure: no library, no GPU.  Returns (data, mask):
+    mask None -- neither `missing` nor `valid` given -- and `data` as it came; otherwise the host matrix to upload and the bool G x S
+    validity mask.  missing="pairwise": a floating host matrix, valid = ~isnan, the NaN cells filled with 0 in a COPY (the caller's array
+    is untouched).  `valid`: an explicit mask for any host dtype; the matrix must then be free of NaN.  Raises DimensionMismatch, the
+    message naming the reason, for: `missing` other than None / "pairwise"; a sparse or device-resident `data`; shard[1] > 1;
+    `contrasts`, `sample_scores`, `sample_tests`, `sample_calls` or `pair_support` together with a mask; a mask of the wrong shape; an
+    integer matrix with missing="pairwise" and no `valid` (it cannot hold a NaN); NaN in the matrix beside an explicit `valid`."""
+    def bad(why):
+        return _ffi.DimensionMismatch(_ffi.REO_EINVAL, why)
+    if missing is not None and missing != "pairwise":
+        raise bad(f"missing = {missing!r}: None (a NaN is refused) or \"pairwise\" (pairs are compared in the samples where both genes exist)")
+    if missing is None and valid is None:
+        return data, None
+    if _ffi.is_sparse(data) or _ffi.is_device_sparse(data) or _ffi.is_device_tensor(data):
+        raise bad("missing values: a sparse or device-resident 'data' has no pairwise route (the validity mask is made from a dense host matrix)")
+    if shard[1] > 1:
+        raise bad(f"missing values: the masked build has no sharded form (shard = {tuple(shard)!r})")
+    for name, on in (("contrasts", contrasts is not None), ("sample_scores", sample_scores), ("sample_tests", sample_tests),
+                     ("sample_calls", sample_calls), ("pair_support", pair_support)):
+        if on:
+            raise bad(f"missing values: `{name}` compares on the whole matrix and would count the fillers under the validity mask; "
+                      "it is not available together with a mask")
+    X = np.asarray(data)
+    if X.ndim != 2:
+        raise bad("'data' must be a genes x samples matrix")
+    floating = np.issubdtype(X.dtype, np.floating)
+    nan = np.isnan(X) if floating else np.zeros(X.shape, dtype=bool)
+    if valid is not None:
+        mask = np.asarray(valid)
+        if mask.ndim != 2 or mask.shape != X.shape:
+            raise bad(f"valid mask has shape {tuple(mask.shape)}, 'data' is {tuple(X.shape)} (genes x samples)")
+        if nan.any():
+            raise bad("an explicit `valid` mask needs a matrix without NaN: write a filler under the invalid cells (or pass missing=\"pairwise\" alone)")
+        return X, mask != 0
+    if not floating:
+        raise bad(f"missing=\"pairwise\" derives the mask from NaN: 'data' of dtype {X.dtype} cannot hold one (pass `valid`)")
+    if nan.any():
+        X = X.copy()
+        X[nan] = 0
+    return X, ~nan
+
+
 def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref_gene, n_iter, n_conv, *,
                       seed: int = 0, device: int = -1, shard=(0, 1), allreduce=None, allgather=None, profile: bool = False,
                       pairs=None, sample_scores: bool = False, pair_support: bool = False, contrasts=None,
-                      sample_tests: bool = False, sample_calls: bool = False) -> DegRun:
+                      sample_tests: bool = False, sample_calls: bool = False, missing=None, valid=None, min_complete=None) -> DegRun:
     """identify_degs with the extras (trace, timings) kept.  `data` is a host matrix (numpy, anything np.asarray takes) or a torch
     tensor on a ROCm device, which is used in place (_ffi.device_matrix).  A column-major host matrix is read in place; a row-major one
     (numpy's default C order, column slices of a wider C-ordered array) is copied column-major on the host first, or, with REO_ROWMAJOR=1
@@ -251,8 +295,20 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
     contrast, in the order given, instead of the reference's: group ctrl against group treat ALONE (Context.build_contrast; with more than two
     groups every contrast is classified from the per-group counts of the first build, nothing is counted again).  Each comparison dict
     carries "ctrl" and "treat" (level names) besides today's keys, "k" is the control's index, and `res` has 1 + 16 len(contrasts) columns;
-    `pairs`, `sample_scores` and `pair_support` work per contrast.  None (the default): the reference's comparisons."""
+    `pairs`, `sample_scores` and `pair_support` work per contrast.  None (the default): the reference's comparisons.
+    `missing`, `valid`, `min_complete` (not in the reference, which drops every gene with a missing cell): missing="pairwise" takes a
+    floating host matrix with NaN -- valid = ~isnan, the NaN cells are filled with 0 in a copy, the caller's array is untouched --;
+    `valid` is an explicit boolean G x S mask for any host dtype and implies the pairwise route (the matrix must then be free of NaN).
+    Every comparison is then built by Context.build_pairs_masked: a pair is compared in the samples where both genes are valid, each side
+    against the threshold of that many samples, and a side with fewer than `min_complete` of them (None: per side min(side size, 8 at
+    pval_reo = 0.01); an int: both sides) is unstable.  The comparison dict gains "min_complete", and info["masked_build"] reads 1.
+    `pairs` works; `contrasts`, `sample_scores`, `sample_tests`, `sample_calls`, `pair_support`, a sparse or device-resident matrix and
+    shard[1] > 1 are refused together with a mask (missing_plan).  Defaults: nothing changes, and a NaN is refused as always."""
     need_pairs_for_support(pairs, pair_support)
+    data, mask = missing_plan(data, missing, valid, shard=shard, contrasts=contrasts, sample_scores=sample_scores, sample_tests=sample_tests,
+                              sample_calls=sample_calls, pair_support=pair_support)
+    if mask is not None:
+        _ffi.resolve_min_complete(min_complete, (1, 1), pval_reo)   # (its refusals, before a context is opened)
     # a torch tensor on a ROCm device: a strided one is used where it is, a sparse one is made dense there (its device is the context's)
     on_device = _ffi.is_device_sparse(data) or _ffi.is_device_tensor(data)
     if on_device:
@@ -276,7 +332,8 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
         # groups, thresholds and sharding BEFORE the matrix: reo_set_matrix then ranks the samples as their columns arrive and, on
         # one GPU with two groups, starts the pair kernel's first side while the second group is still crossing PCIe
         ctx.set_groups(gid, len(levels))
-        thr = ctx.compute_thresholds(pval_reo)
+        if mask is None:   # (the masked build has thresholds of its own: nothing is started on the fillers while the matrix arrives)
+            thr = ctx.compute_thresholds(pval_reo)
         if shard[1] > 1:
             ctx.set_shard(*shard)
             if allgather is not None:
@@ -287,8 +344,14 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
             ctx.set_matrix_tensor(data)   # (the context keeps the tensor alive until it is closed, behind the last build_pairs)
         else:
             ctx.set_matrix(data)
+        if mask is not None:
+            thr = ctx.compute_thresholds(pval_reo)   # (reported only: what the complete sides would be held to)
+            ctx.set_valid_mask(mask)
         for k, treat in plan:  # `for k=1:gnum ... if gnum==2 break` (:396,431-434), or the contrasts
-            cm = build_comparison(ctx, levels, k, treat)
+            if mask is not None:
+                cm = {"k": k, "min_complete": ctx.build_pairs_masked(k, pval_reo, min_complete)}
+            else:
+                cm = build_comparison(ctx, levels, k, treat)
             result, iters, trace = ctx.identify_degs(np.asarray(ref_gene, dtype=bool), pval_deg, padj_deg, n_iter, n_conv)
             cm.update({"result": result, "labels": label_genes(result, pval_deg, padj_deg), "iters_run": iters, "trace": trace})
             comps.append(cm)
