@@ -655,7 +655,11 @@ int32_t reo_get_timings(reo_ctx *ctx, double *ms, int32_t n);
  * build (0: no slot build; 1: one order for both sides; 2: an order per side, the default where the two sides together have at least
  * 16 sample blocks of 32 and a word form puts the columns back; REO_K1_SLOT_SIDES=1 or 2 in the environment asks for that one
  * everywhere; the table is the same bit for bit under both), 31 the resident class table came from reo_build_pairs_masked (1; any other
- * build, and no table: 0). */
+ * build, and no table: 0), 32 the operands of that slot build were sliced straight from the transform's 16-bit position rows into slot
+ * order (1, the default; 0: no slot build, or REO_K1_SLOT_SLICE=0 in the environment -- the gene-order bit planes are made and gathered;
+ * the table is the same bit for bit), 33 how many times the gene-order bit planes of the current transform were made on demand (a
+ * transform of tie-free data that a slot build can follow leaves them unmade; the first pair query, masked build or identity-order build
+ * makes them once: 0 or 1). */
 int32_t reo_get_info(reo_ctx *ctx, int64_t *info, int32_t n);
 
 #ifdef __cplusplus

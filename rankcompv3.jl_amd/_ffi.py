@@ -1058,8 +1058,8 @@ class Context:
                 "k2_full_launches": int(ms[9]), "k2_delta_ms": ms[10], "set_matrix_host_wall_ms": ms[11]}
 
     def info(self) -> dict:
-        w = np.zeros(32, dtype=np.int64)
-        check(self._L.reo_get_info(self._h, _ptr(w), 32))
+        w = np.zeros(34, dtype=np.int64)
+        check(self._L.reo_get_info(self._h, _ptr(w), 34))
         v = np.zeros(28, dtype=np.int64)   # fields 0-27 keep their places (tests/test_csc_device_cpu.py reads this line); 28 is appended
         v[:] = w[:28]
         return {"G": int(v[0]), "S": int(v[1]), "Gp": int(v[2]), "table_bytes": int(v[3]), "has_ties": int(v[4]),
@@ -1071,4 +1071,4 @@ class Context:
                 "csc_upload": int(v[22]), "csc_nnz": int(v[23]), "resident_dtype": int(v[24]),
                 "k1_slot_order": int(v[25]), "k1_half_tiles_separated": int(v[26]), "csc_device": int(v[27]),
                 "k1_unslot_form": int(w[28]), "contrast_treat": int(w[29]), "k1_slot_sides": int(w[30]),
-                "masked_build": int(w[31])}
+                "masked_build": int(w[31]), "k1_slot_slice": int(w[32]), "planes_on_demand": int(w[33])}

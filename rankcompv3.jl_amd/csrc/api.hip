@@ -346,6 +346,7 @@ static void invalidate(reo_ctx *c)
     drop_ref_mask(c, "the matrix or the groups changed after the last reo_identify_degs (reo_set_matrix_*, reo_filter_matrix, reo_set_groups): "
                      "the class table it ran on is gone");
     c->transformed = false;
+    c->planes_ready = false; c->planes_on_demand = 0; c->last_k1_slot_slice = 0;
     c->built_k = -1;
     c->built_treat = -1;
     c->built_masked = 0;
@@ -659,6 +660,7 @@ int32_t reo_create(reo_ctx **out, int32_t device, uint64_t seed)
     if (const char *e = getenv("REO_K1_QUEUE")) c->k1_queue = (e[0] != '0');
     if (const char *e = getenv("REO_K1_UNSLOT")) { const int v = atoi(e); c->k1_unslot = (v == 8 || v == 4) ? v : (e[0] == '0' ? 0 : -1); }
     if (const char *e = getenv("REO_K1_SLOT_SIDES")) { const int v = atoi(e); c->k1_slot_sides = (v == 1 || v == 2) ? v : 0; }
+    if (const char *e = getenv("REO_K1_SLOT_SLICE")) c->k1_slot_slice = atoi(e) != 0;
     if (const char *e = getenv("REO_K1_WORKERS")) c->k1_workers = std::max(1, atoi(e));
     if (const char *e = getenv("REO_K1_ORDER")) c->k1_order = std::max(0, std::min(2, atoi(e)));
     {
@@ -1621,15 +1623,16 @@ int32_t reo_get_info(reo_ctx *c, int64_t *info, int32_t n)
         int32_t rc = use(c);
         if (rc || (rc = launch_slot_separated(c, &separated))) return rc;
     }
-    const int64_t v[32] = {c->G, c->S, c->Gp, static_cast<int64_t>(c->table.n * sizeof(uint32_t)), c->has_ties,
+    const int64_t v[34] = {c->G, c->S, c->Gp, static_cast<int64_t>(c->table.n * sizeof(uint32_t)), c->has_ties,
                            c->tiles_owned, c->tiles_total, kTileI, c->k1_cj, c->k1_q, kUnitH,
                            c->goff32.empty() ? 0 : c->goff32.back(), c->last_k1_shared,
                            static_cast<int64_t>(c->gcounts.n * sizeof(uint16_t)), c->transform_in_lds, c->xcc_local,
                            c->it_cycle_period, c->it_cycle_at, c->it_cycle_skipped, c->narrowed_bytes, c->eager_range_launches, c->rowmajor_upload,
                            c->csc_upload, c->csc_nnz, c->dtype, c->last_k1_slots, separated, c->csc_device,
                            c->last_k1_slots ? c->last_k1_unslot : 0, c->built_k >= 0 ? c->built_treat : -1,
-                           c->last_k1_slots ? c->last_k1_slot_sides : 0, (c->built_k >= 0 && c->built_masked) ? 1 : 0};
-    for (int i = 0; i < n && i < 32; ++i) info[i] = v[i];
+                           c->last_k1_slots ? c->last_k1_slot_sides : 0, (c->built_k >= 0 && c->built_masked) ? 1 : 0,
+                           c->last_k1_slots ? c->last_k1_slot_slice : 0, c->transformed ? c->planes_on_demand : 0};
+    for (int i = 0; i < n && i < 34; ++i) info[i] = v[i];
     return REO_OK;
 }
 

@@ -299,6 +299,73 @@ inline void unslot_pair_model(uint32_t *table, int r0, int n_rows, int side, int
     }
 }
 
+// ---- the slot form's OPERANDS straight from the 16-bit position rows (kernels.hip, k1_slot_slice).  A slot build is tie-free, so
+// lo = pos in every sample: both operand sets of the pair kernel are the bit planes of pos[.][s2g[k]], in the two layouts of the gene-order
+// planes (transform.hip, t_slice):
+//   Ps [(b 4 + q) Gp + k]      planes 4q .. 4q + 3 of slot k in sample block b (16 bytes)
+//   ALs[(b Gp + k) 4 .. + 3]   the same 16 plane words as one 64-byte record, plane p in word (p + 15) % 16
+// Sample block b uses the map of the side that counts it: side 0 the blocks cb .. ce - 1, side 1 every other one (the launch's block
+// ranges, not group ids: comparison 1 swaps the groups).
+struct alignas(16) SlotQuad { uint32_t x, y, z, w; };   // 16 bytes that travel as one
+
+REO_SLOTS_HD int slot_slice_side(int b, int cb, int ce) { return (b >= cb && b < ce) ? 0 : 1; }
+REO_SLOTS_HD size_t slot_slice_pos_index(int b, int q, int k, int Gp) { return (static_cast<size_t>(b) * 4 + q) * Gp + k; }   // in quads
+REO_SLOTS_HD size_t slot_slice_rec_index(int b, int k, int Gp) { return (static_cast<size_t>(b) * Gp + k) * 4; }               // in quads
+REO_SLOTS_HD int slot_slice_rec_word(int plane) { return (plane + 15) & 15; }
+
+// Two genes of block b and their slots k0, k1: w[s] = the position of the first in sample 32 b + s | the second's << 16.  One 32 x 32
+// bit transpose makes the 16 planes of both (w[p], w[16 + p]), which leave in both layouts.
+REO_SLOTS_HD void slot_slice_store(uint32_t (&w)[32], int b, int k0, int k1, int Gp, SlotQuad *Ps, SlotQuad *ALs)
+{
+    unslot_transpose<32>(w);
+    REO_SLOTS_UNROLL
+    for (int h = 0; h < 2; ++h) {
+        const uint32_t *v = w + 16 * h;
+        const int k = h ? k1 : k0;
+        REO_SLOTS_UNROLL
+        for (int q = 0; q < 4; ++q) Ps[slot_slice_pos_index(b, q, k, Gp)] = SlotQuad{v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]};
+        SlotQuad *r = ALs + slot_slice_rec_index(b, k, Gp);
+        r[0] = SlotQuad{v[1], v[2], v[3], v[4]};
+        r[1] = SlotQuad{v[5], v[6], v[7], v[8]};
+        r[2] = SlotQuad{v[9], v[10], v[11], v[12]};
+        r[3] = SlotQuad{v[13], v[14], v[15], v[0]};
+    }
+}
+
+// The rule as a serial host model, by SLOTS: pos16 [32 nblk][Gp] (rows of padding slots and columns of padded genes hold zeros), s2g [2][Gp]
+inline void slot_slice_model(const uint16_t *pos16, const uint32_t *s2g, int Gp, int nblk, int cb, int ce, SlotQuad *Ps, SlotQuad *ALs)
+{
+    for (int b = 0; b < nblk; ++b) {
+        const uint32_t *map = s2g + static_cast<size_t>(slot_slice_side(b, cb, ce)) * Gp;
+        for (int k = 0; k < Gp; k += 2) {
+            uint32_t w[32];
+            for (int s = 0; s < 32; ++s) {
+                const uint16_t *row = pos16 + (static_cast<size_t>(b) * 32 + s) * Gp;
+                w[s] = static_cast<uint32_t>(row[map[k]]) | static_cast<uint32_t>(row[map[k + 1]]) << 16;
+            }
+            slot_slice_store(w, b, k, k + 1, Gp, Ps, ALs);
+        }
+    }
+}
+
+// The same by GENES (the form k1_slot_slice runs: coalesced reads of the rows, the 16-byte pieces scattered to their slots): two
+// neighbouring genes g (even), g + 1 go to the slots g2s[g], g2s[g + 1] of the block's side.  g2s [2][Gp] must be the inverse of s2g
+// over all Gp slots (padding genes map to themselves); a common order (sides == 1) fills its first half only.
+inline void slot_slice_scatter_model(const uint16_t *pos16, const uint32_t *g2s, int sides, int Gp, int nblk, int cb, int ce, SlotQuad *Ps, SlotQuad *ALs)
+{
+    for (int b = 0; b < nblk; ++b) {
+        const uint32_t *map = g2s + static_cast<size_t>(sides == 2 ? slot_slice_side(b, cb, ce) : 0) * Gp;
+        for (int g = 0; g < Gp; g += 2) {
+            uint32_t w[32];
+            for (int s = 0; s < 32; ++s) {
+                const uint16_t *row = pos16 + (static_cast<size_t>(b) * 32 + s) * Gp;
+                w[s] = static_cast<uint32_t>(row[g]) | static_cast<uint32_t>(row[g + 1]) << 16;
+            }
+            slot_slice_store(w, b, static_cast<int>(map[g]), static_cast<int>(map[g + 1]), Gp, Ps, ALs);
+        }
+    }
+}
+
 // ... and back: out bit k = in bit s2g[k] for slots k < G (what the pair kernel's slot-order row was)
 inline void slot_permute_row(const uint32_t *in, uint32_t *out, int W, const uint32_t *s2g, int G)
 {

@@ -863,6 +863,32 @@ __global__ __launch_bounds__(256) void k1_slot_gather(const uint4 *__restrict__ 
     }
 }
 
+// The same two operand sets straight from the 16-bit position rows, without the gene-order planes in between (k1_slots.h, slot_slice_*):
+// a slot build is tie-free, so lo = pos and ALs holds the bits of Ps in the record layout.  A thread takes two neighbouring GENES of one
+// sample block, reads them as t_slice does (32 coalesced 4-byte loads), makes their 2 x 16 plane words by one 32 x 32 bit transpose and
+// stores them at the genes' slots g2s[g], g2s[g + 1]: four 16-byte pieces and one 64-byte record per gene and block, scattered.  (The
+// form that took two neighbouring SLOTS and gathered their two-byte numbers through s2g, with contiguous stores, has 32 scattered
+// accesses per gene and block instead of 5: 83.7 us against 41.8 at config 3, profiles/slot_slice_forms.txt.)
+// Workgroups are dealt to the XCDs round-robin, so workgroup v of the (block, 512 genes) list runs as blockIdx.x = (v % per) 8 + v / per:
+// the workgroups of one sample block share an XCD, in whose L2 the pieces of a line meet (48.0 us without it; placement is for speed
+// only: every v is taken exactly once wherever it runs).
+// g2s: [2][Gp] with an order per side (map_sides == 2), else the common order's one map; Gp entries each, padding genes map to themselves.
+__global__ __launch_bounds__(256) void k1_slot_slice(const uint16_t *__restrict__ pos16, const uint32_t *__restrict__ g2s, int map_sides, int Gp, int nblk, int cb, int ce, int per,
+                                                     SlotQuad *__restrict__ Ps, SlotQuad *__restrict__ ALs)
+{
+    const int wpb = Gp >> 9;   // workgroups per sample block (Gp is a multiple of 1024)
+    const int v = static_cast<int>(blockIdx.x & 7u) * per + static_cast<int>(blockIdx.x >> 3);
+    if (v >= nblk * wpb) return;
+    const int b = v / wpb, g = ((v - b * wpb) * 256 + static_cast<int>(threadIdx.x)) * 2;
+    const uint2 k2 = *reinterpret_cast<const uint2 *>(g2s + static_cast<size_t>(map_sides == 2 ? slot_slice_side(b, cb, ce) : 0) * Gp + g);
+    const int k0 = static_cast<int>(min(k2.x, static_cast<uint32_t>(Gp - 1))), k1 = static_cast<int>(min(k2.y, static_cast<uint32_t>(Gp - 1)));   // (a map holds slots below Gp only)
+    const uint32_t *rows2 = reinterpret_cast<const uint32_t *>(pos16 + static_cast<size_t>(b) * 32 * Gp) + (g >> 1);   // gene g in the low half, g + 1 in the high half
+    uint32_t w[32];
+#pragma unroll
+    for (int s = 0; s < 32; ++s) w[s] = rows2[static_cast<size_t>(s) * (Gp >> 1)];
+    slot_slice_store(w, b, k0, k1, Gp, Ps, ALs);
+}
+
 // The table's columns back into gene order, in place: rows r0 .. r0 + nr - 1 of the table (whole rows: four planes of Wp words) go
 // into LDS as one uint4 per word index (the four planes side by side), then bit j of every (row, plane) = bit g2s[j] of what was
 // there, columns from G on zero.  A THREAD makes whole words: for each of its word's 32 columns it takes g2s[j] (eight 16-byte loads,
@@ -4491,8 +4517,15 @@ static int32_t k1_slots_front(reo_ctx *c, K1Args &a, int sides)
     }
     k1_slot_invert<<<dim3(static_cast<unsigned>(Gp / 256), zs), 256, 0, c->stream>>>(m.g2s, m.s2g, G, Gp, sides);
     k1_slot_ranges<<<dim3(static_cast<unsigned>(Gp / 256), 2), 256, 0, c->stream>>>(m.gmm, m.s2g, G, Gp, m.trng, m.crng);
-    k1_slot_gather<<<dim3(static_cast<unsigned>(Gp / 256), static_cast<unsigned>(nblk)), 256, 0, c->stream>>>(c->pos.p, c->lo.p, m.s2g, Gp, a.cb, a.ce, c->pos_s.p, c->lo_s.p);
+    if (c->k1_slot_slice) {   // the 16-bit position rows straight into both operand sets (k1_slots_wanted has looked at the rows' size)
+        const int per = (nblk * (Gp / 512) + 7) / 8;
+        SlotQuad *ps = reinterpret_cast<SlotQuad *>(c->pos_s.p), *als = reinterpret_cast<SlotQuad *>(c->lo_s.p);
+        k1_slot_slice<<<static_cast<unsigned>(per * 8), 256, 0, c->stream>>>(c->t_pos16.p, m.g2s, sides, Gp, nblk, a.cb, a.ce, per, ps, als);   // (the common order fills g2s[0] only)
+    } else {   // REO_K1_SLOT_SLICE=0: the gene-order planes (made by the transform), gathered
+        k1_slot_gather<<<dim3(static_cast<unsigned>(Gp / 256), static_cast<unsigned>(nblk)), 256, 0, c->stream>>>(c->pos.p, c->lo.p, m.s2g, Gp, a.cb, a.ce, c->pos_s.p, c->lo_s.p);
+    }
     REO_HIP_CHECK(hipGetLastError());
+    c->last_k1_slot_slice = c->k1_slot_slice ? 1 : 0;
     a.P = c->pos_s.p; a.AL = c->lo_s.p; a.AH = c->lo_s.p;   // (the tie-free form reads no hi planes)
     a.s2g = m.s2g; a.trng = m.trng; a.crng = m.crng;
     // the item queues start at zero for EVERY launch (a launch leaves each counter beyond its queue's length)
@@ -4599,7 +4632,7 @@ int32_t launch_k1(reo_ctx *c, int k, int sides, bool keep_table, const int32_t *
     if ((rc = upload_unit_map(c, units))) return rc;
     a.unit_map = c->unit_map.p;
     a.gate = gate;
-    if (!prepare) { c->last_k1_slots = 0; c->last_k1_slot_sides = 0; c->k1_slot_items = nullptr; c->k1_slot_items_n = 0; c->k1_slot_gp = 0; }
+    if (!prepare) { c->last_k1_slots = 0; c->last_k1_slot_sides = 0; c->last_k1_slot_slice = 0; c->k1_slot_items = nullptr; c->k1_slot_items_n = 0; c->k1_slot_gp = 0; }
     if ((range || prepare) && (sides != 1 && sides != 2)) { set_error("a range of sample blocks / a prepared launch: one side of the pair kernel"); return REO_EINVAL; }
     if (gate && (!pl.wave || pl.wide || pl.big)) { set_error("a gated launch of the pair kernel: wave form, at most 65535 genes and samples"); return REO_EINVAL; }
     c->x_pipelined = false;
@@ -4638,6 +4671,8 @@ int32_t launch_k1(reo_ctx *c, int k, int sides, bool keep_table, const int32_t *
         if (k1_slots_alloc(c) == REO_OK) pl.slots = true;
         else (void)hipGetLastError();
     }
+    // every other form reads the gene-order planes, which a transform of tie-free data may have left unmade (transform_ms, not k1_ms)
+    if (!(pl.slots && c->k1_slot_slice) && (rc = ensure_planes(c))) return rc;
     if (a.stamps) k_time_mark<<<1, 64, 0, c->stream>>>(a.stamps + c->k1_items_n * 4);
     tic(c, 1);
     // ... with an order per side where the build is long enough to pay for it (k1_slots.h, slot_sides_wanted); the bit form of the
@@ -4721,6 +4756,8 @@ int32_t launch_expand_units(reo_ctx *c, int m0, int mcnt, const uint32_t *recv, 
 
 int32_t launch_counts(reo_ctx *c, int64_t i0, int64_t i1, int64_t j0, int64_t j1, uint16_t *d_gt, uint16_t *d_eq)
 {
+    const int32_t rc = ensure_planes(c);
+    if (rc) return rc;
     dim3 grid(static_cast<unsigned>((j1 - j0 + 255) / 256), static_cast<unsigned>(i1 - i0));
     if (c->G > 65535)
         k1_counts_big<<<grid, 256, 0, c->stream>>>(c->pos.p, c->lo.p, c->hi.p, c->Gp, plane_bits(c->G), c->goff_dev.p, c->ngroups,

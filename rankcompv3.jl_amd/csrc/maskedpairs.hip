@@ -158,7 +158,7 @@ __global__ __launch_bounds__(256) void k_counts_masked(const uint4 *__restrict__
 
 int32_t need_planes(reo_ctx *c, const char *what)
 {
-    if (c->pos.p && c->lo.p && c->hi.p && c->goff_dev.p && !c->goff32.empty() && c->ngroups >= 1 && c->G <= kMpMaxGenes && c->vwords.p) return REO_OK;
+    if (c->pos.p && c->lo.p && c->hi.p && c->goff_dev.p && !c->goff32.empty() && c->ngroups >= 1 && c->G <= kMpMaxGenes && c->vwords.p) return ensure_planes(c);
     set_error("%s: no bit planes or no validity words", what);
     return REO_EINVAL;
 }

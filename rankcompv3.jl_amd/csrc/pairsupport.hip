@@ -115,6 +115,7 @@ int32_t launch_pair_support(reo_ctx *c, const PsItem *d_items, int64_t n_items, 
         set_error("reo_pair_support: no bit planes");
         return REO_EINVAL;
     }
+    if (const int32_t rp = ensure_planes(c)) return rp;
     if (n_items < 1 || n_items > (int64_t(1) << 24) || (d_outcome && !d_slot2col)) {
         set_error("reo_pair_support: a batch of %lld work items cannot be launched", (long long)n_items);
         return REO_EINVAL;

@@ -276,6 +276,13 @@ struct reo_ctx {
     reo::DevBuf<uint32_t> k1_slot_part; // [kSlotSplits][2][Gp] the sides' position ranges of every gene over a slice of the samples (min | max << 16)
     reo::DevBuf<uint32_t> k1_slot_maps; // [2][Gp] ranges per side, [2][Gp] keys, [2][Gp] g2s, [2][Gp] s2g, [2][Gp / 32] tile ranges, [2][Gp / 256] chunk ranges, [2] a count
     reo::DevBuf<uint4> pos_s, lo_s;     // the pos and lo planes in slot order (the layouts of pos and lo)
+    int k1_slot_slice = 1;              // REO_K1_SLOT_SLICE=0: a slot build makes the gene-order planes and gathers them (k1_slot_gather; A/B, tests) instead of
+                                        // slicing the 16-bit position rows straight into slot order (k1_slot_slice)
+    int last_k1_slot_slice = 0;         // reo_get_info 32: the last build's operands came from k1_slot_slice
+    // The gene-order planes (pos, lo, hi) on demand: a transform of tie-free data whose next build can be a slot build leaves them unmade,
+    // and whoever reads them calls ensure_planes first (transform.hip), which slices the 16-bit rows -- they live until the next transform.
+    bool planes_ready = false;          // pos, lo and hi hold the planes of the current transform (or their slicing is queued in front of every reader)
+    int planes_on_demand = 0;           // reo_get_info 33: how many times the current transform's planes were made by ensure_planes
     // item queues of the slot form (kernels.hip, k1w_pairs_slots; index rules: k1_queue.h): resident waves take items from eight counters
     int k1_queue = 1;                   // REO_K1_QUEUE=0: one workgroup per item, as the identity order's kernels (A/B, tests)
     int k1_workers = 0;                 // REO_K1_WORKERS=n (tests): workgroups of the launch instead of CUs x 4 SIMDs x 3 waves
@@ -387,6 +394,8 @@ namespace reo {
 
 // transform.hip
 int32_t run_transform(reo_ctx *c);
+// the gene-order planes of the current transform, made now (t_slice over the whole matrix on c->stream) if the transform left them unmade
+int32_t ensure_planes(reo_ctx *c);
 // host matrix -> HBM in chunks, ranked (and paired) as they arrive (host_i32: the host array is Int32, the resident matrix Int64)
 // how a host matrix lies: column-major (hld = leading dimension), row-major (genes x samples, hld = its pitch), or CSC (hX points at the
 // reo::CscSrc<element type> of upload_csc.h, hld unused)

@@ -168,6 +168,7 @@ int32_t launch_sample_counts(reo_ctx *c, const int32_t *d_genes, int64_t n_queri
         set_error("reo_sample_counts: no class table or no bit planes");
         return REO_EINVAL;
     }
+    if (const int32_t rp = ensure_planes(c)) return rp;
     ScArgs a;
     a.table = c->table.p; a.maskbits = d_maskbits; a.genes = d_genes; a.slot2col = d_slot2col;
     a.P = c->pos.p; a.AL = c->lo.p; a.AH = c->hi.p;

@@ -1310,10 +1310,12 @@ int32_t transform_impl(reo_ctx *c)
         REO_HIP_CHECK(hipMemsetAsync(c->hi.p, 0, static_cast<size_t>(nblk) * Gp * 8 * sizeof(uint4), st));
     }
     const T *X = static_cast<const T *>(c->dX);
+    c->planes_ready = false; c->planes_on_demand = 0;
     auto slice = [&]() -> int32_t {
         if (big) t_slice_big<<<dim3(Gp / 256, nblk), 256, 0, st>>>(c->t_pos32.p, c->t_lo32.p, c->t_hi32.p, Gp, c->pos.p, c->lo.p, c->hi.p);
         else t_slice<<<dim3(Gp / 512, nblk), 256, 0, st>>>(c->t_pos16.p, c->t_lo16.p, c->t_hi16.p, Gp, c->pos.p, c->lo.p, c->hi.p, 0);
         REO_HIP_CHECK(hipGetLastError());
+        c->planes_ready = true;
         return REO_OK;
     };
     auto finish = [&](int has_ties, bool sliced) -> int32_t {
@@ -1322,6 +1324,10 @@ int32_t transform_impl(reo_ctx *c)
         c->transformed = true;
         return REO_OK;
     };
+    // The next build can still be a slot build (kernels.hip, k1_slots_wanted -- as far as it is known here; ties are not yet): that build
+    // slices the 16-bit rows straight into slot order (k1_slot_slice) and reads no gene-order planes, so they wait until the flags say
+    // "ties" or somebody asks for them (ensure_planes).  This function is never the pipelined upload, which slices group by group.
+    const bool planes_can_wait = c->k1_slots && c->k1_slot_slice && c->k1_wave && !big && S <= 65535 && c->ngroups == 2 && c->world == 1 && !c->in_multi;
 
     // first choice: every sample ranked inside one workgroup's LDS -- t_sample's histograms for Int64 keys of at most 24
     // varying bits, t_sample_wide's buckets for everything else (Float64; wider keys; a crowded lossy bucket)
@@ -1337,8 +1343,8 @@ int32_t transform_impl(reo_ctx *c)
         for (int attempt = 0; attempt < 2; ++attempt) {
             if ((rc = launch_lds_ranking<T>(c, X, SampleList{d_order.p, c->t_slots.p, S, S32}, d_flags.p, wide))) return rc;
             // the slicing is enqueued before the host looks at the flags (it runs while the host wakes up; if the flags send
-            // the data elsewhere it is simply done again)
-            if ((rc = slice())) return rc;
+            // the data elsewhere it is simply done again) -- unless the planes can wait for the flags (above)
+            if (!planes_can_wait && (rc = slice())) return rc;
             // The host waits for the flags only (an event behind their copy into pinned memory); behind that event the clearing
             // of the class table is already queued, so the GPU has work while the host wakes up and launches the pair kernel.
             REO_HIP_CHECK(hipMemcpyAsync(fl, d_flags.p, 6 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -1369,6 +1375,9 @@ int32_t transform_impl(reo_ctx *c)
             }
             if (!fl[4] && !fl[5]) {
                 c->transform_in_lds = wide ? 2 : 1;
+                // planes that waited: ties rule the slot order out, so they are sliced at once (behind the table's clearing, which the GPU
+                // had while the host woke up); tie-free data leaves them unmade
+                if (planes_can_wait && fl[1] && (rc = slice())) return rc;
                 return finish(fl[1], true);
             }
             REO_HIP_CHECK(hipMemsetAsync(d_flags.p, 0, 6 * sizeof(int32_t), st));
@@ -2304,6 +2313,7 @@ int32_t eager_upload_impl(reo_ctx *c, const H *hX, int64_t hld, bool with_k1, bo
     const bool wide = !kCountingPath<T>;
     c->transform_in_lds = 0;
     c->table_prezeroed = false;
+    c->planes_ready = true; c->planes_on_demand = 0;   // (every group's blocks are sliced below, in front of whatever reads them)
     if (with_k1) {
         // the pair kernel's unit map and both sides' item lists go up NOW, while the context's stream is still empty: launch_k1 uploads
         // them with a host wait on that stream, which behind a side's WaitEvent would block the host until that group is ranked (and no
@@ -2589,6 +2599,25 @@ int32_t eager_upload(reo_ctx *c, const void *hX, int64_t hld, bool with_k1, bool
     if (c->dtype == 3) return eager_upload_impl<float>(c, static_cast<const float *>(hX), hld, with_k1, rowmajor);
     if (host_i32) return eager_upload_impl<int64_t, int32_t>(c, static_cast<const int32_t *>(hX), hld, with_k1, rowmajor);
     return eager_upload_impl<int64_t>(c, static_cast<const int64_t *>(hX), hld, with_k1, rowmajor);
+}
+
+int32_t ensure_planes(reo_ctx *c)
+{
+    if (c->planes_ready || !c->transformed) return REO_OK;
+    // (only the 16-bit layout is ever left unsliced: transform_impl, planes_can_wait)
+    const int nblk = c->goff32.empty() ? 0 : c->goff32.back() / 32;
+    const size_t n = static_cast<size_t>(nblk) * 32 * c->Gp, nq = static_cast<size_t>(nblk) * c->Gp * 4;
+    if (c->G > 65535 || !nblk || !c->t_pos16.p || c->t_pos16.n < n || c->t_lo16.n < n || c->t_hi16.n < n || c->pos.n < nq || c->lo.n < nq || c->hi.n < nq) {
+        set_error("the gene-order planes are unmade and the transform's 16-bit rows are gone: internal error");
+        return REO_EHIP;
+    }
+    tic(c, 0);
+    t_slice<<<dim3(c->Gp / 512, nblk), 256, 0, c->stream>>>(c->t_pos16.p, c->t_lo16.p, c->t_hi16.p, c->Gp, c->pos.p, c->lo.p, c->hi.p, 0);
+    toc(c);
+    REO_HIP_CHECK(hipGetLastError());
+    c->planes_ready = true;
+    ++c->planes_on_demand;
+    return REO_OK;
 }
 
 int32_t run_transform(reo_ctx *c)
