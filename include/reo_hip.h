@@ -421,6 +421,42 @@ int32_t reo_set_valid_mask(reo_ctx *ctx, const uint8_t *valid, int64_t G, int64_
 int32_t reo_build_pairs_masked(reo_ctx *ctx, int32_t k, double pval_reo, const int32_t *min_complete /* 2 */);
 int32_t reo_pair_counts_masked(reo_ctx *ctx, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int32_t *n_gt, int32_t *n_eq, int32_t *n_avail);
 
+/* Label-permutation null: how many of the calls would there be if the labels meant nothing?  The reference has no such output (one
+ * permutation is one whole build there).  The context holds a matrix, groups and thresholds; no validity mask may be set.  For comparison
+ * k, side A of the observed data is group k (n1 samples), side B every other sample (n2 = S - n1).  A permutation is a row of S bytes in
+ * the caller's column order, 1 = side A, 0 = side B, with exactly n1 ones; the caller supplies the rows (shuffled freely, or within
+ * batches or patients: the library has no shuffling rule).  The sizes are kept, so the context's thresholds m1 = thr[0, k], m2 = thr[1, k]
+ * hold unchanged.  For permutation p and every i < j:  a = n_gt_A + coins(seed, i, j, 0, n_eq_A),  b = n_gt_B + coins(seed, i, j, 1, n_eq_B)
+ * -- the keyed coin stream of reo_build_pairs, keyed by SIDE 0 and 1, never by the context's group ids --,  ic = 3 if a >= m1, else 1 if
+ * n1 - a >= m1, else 2;  `it` likewise from b, n2, m2;  the code of (i, j) is 3(ic-1)+(it-1), that of (j, i) 8 minus it.  The table of
+ * permutation p therefore equals, byte for byte and ties included, the reo_build_pairs(0) table of a two-group context with the same
+ * seed, thresholds and group ids 1 - row.  With a context of more than two groups the permuted tables are still two-group tables, one coin
+ * stream per side.  The sample ranks do not depend on the labels: all tables of a batch come from ONE walk over the bit planes.
+ *
+ * reo_perm_null works in batches of P tables (as many as fit half of the free device memory, at most 64; REO_PERM_BATCH=n in the
+ * environment, read at every call, asks for at most n; reo_get_info 34 reports P) and answers REO_ENOMEM with the byte count if not even
+ * one table fits beside the resident one.  It needs the resident class table of comparison k (reo_build_pairs(k)), and first runs on it
+ * what reo_identify_degs(ref0 = ref_mask, n_iter = 1) runs: delta1_obs[i] is that pass's delta1.  Per permuted table it runs the same
+ * tally and pass, unchanged, with the same ref_mask (the null holds the reference set fixed and does not iterate), then
+ *   n_ge[i] += |delta1_p(i)| >= |delta1_obs(i)| (as doubles; equality counts, 0 against 0 too),
+ *   n_up[p] / n_down[p] = the genes with pval <= pval_deg && padj <= padj_deg and z1 > 0 / z1 < 0,  se_null[p] = the pass's trimmed
+ *   standard deviation,  delta1_null[p * G + i] = delta1_p(i) (NULL: not delivered).
+ * All arrays are host memory.  The resident class table is intact after the call (reo_get_codes gives the same bytes); the iteration's
+ * buffers are used, so reo_get_ref_mask is refused afterwards exactly as after reo_tally.
+ * reo_perm_codes is the parity hook: the class codes of ONE permutation's table in the layout of reo_get_codes; it needs no resident table.
+ * (REO_PERM_CODES_SLOT=q in the environment, for tests: the table is built as table q of a batch of q + 1, q < 64, and read from there.)
+ * REO_EINVAL, each with its own message, before anything is touched: a null argument (delta1_null excepted); a row whose number of ones
+ * is not n1, or with a byte other than 0 / 1; n_perm < 1; k outside the groups; no thresholds; (reo_perm_null) no resident table of
+ * comparison k built by reo_build_pairs; a validity mask set; a sharded context (more than one shard) or a reo_create_multi context;
+ * S > 65535 or G > 65535 (the 16-plane layout only). */
+int32_t reo_perm_null(reo_ctx *ctx, int32_t k, const uint8_t *side_a /* [n_perm][S] */, int64_t n_perm,
+                      const uint8_t *ref_mask /* G bytes, required */, double pval_deg, double padj_deg,
+                      double *delta1_obs /* G */, int32_t *n_ge /* G */,
+                      int32_t *n_up /* n_perm */, int32_t *n_down /* n_perm */, double *se_null /* n_perm */,
+                      double *delta1_null /* [n_perm][G], may be NULL */);
+int32_t reo_perm_codes(reo_ctx *ctx, int32_t k, const uint8_t *side_a /* [S], one permutation */,
+                       int64_t i0, int64_t i1, int64_t j0, int64_t j1, uint8_t *code);
+
 /* Sample tests: is gene i UP OR DOWN IN ONE SAMPLE?  The tallies call a gene over the groups; this call tests one sample's orderings of
  * the gene against the pairs that are stable in the control group, with Fisher's exact test -- the individual-level question of the
  * RankComp family.  The reference has no such output.
@@ -659,7 +695,8 @@ int32_t reo_get_timings(reo_ctx *ctx, double *ms, int32_t n);
  * order (1, the default; 0: no slot build, or REO_K1_SLOT_SLICE=0 in the environment -- the gene-order bit planes are made and gathered;
  * the table is the same bit for bit), 33 how many times the gene-order bit planes of the current transform were made on demand (a
  * transform of tie-free data that a slot build can follow leaves them unmade; the first pair query, masked build or identity-order build
- * makes them once: 0 or 1). */
+ * makes them once: 0 or 1), 34 the tables per batch of the last reo_perm_null, 35 the microseconds that its launches of the permuted pair
+ * kernel took in all (HIP events around each launch). */
 int32_t reo_get_info(reo_ctx *ctx, int64_t *info, int32_t n);
 
 #ifdef __cplusplus

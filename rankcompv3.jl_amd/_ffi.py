@@ -35,6 +35,7 @@ SYMBOLS = [
     "reo_set_matrix_pseudobulk_dense_f64", "reo_set_matrix_pseudobulk_dense_i64", "reo_set_matrix_pseudobulk_csc_f64", "reo_set_matrix_pseudobulk_csc_i64",
     "reo_filter_matrix", "reo_get_matrix", "reo_get_ref_mask", "reo_pair_list", "reo_sample_counts", "reo_pair_support",
     "reo_sample_tests", "reo_sample_calls", "reo_set_valid_mask", "reo_build_pairs_masked", "reo_pair_counts_masked",
+    "reo_perm_null", "reo_perm_codes",
 ] +[f"reo_set_matrix_{form}_{t}" for form in ("csc_dev", "pseudobulk_csc_dev", "pseudobulk_dense_dev") for t in ("f64", "i64", "f32", "i32")]
 
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p)
@@ -147,6 +148,8 @@ def lib() -> ctypes.CDLL:
         "reo_set_valid_mask": (i32, [vp, vp, i64, i64, i64]),
         "reo_build_pairs_masked": (i32, [vp, i32, f64, vp]),
         "reo_pair_counts_masked": (i32, [vp, i64, i64, i64, i64, vp, vp, vp]),
+        "reo_perm_null": (i32, [vp, i32, vp, i64, vp, f64, f64, vp, vp, vp, vp, vp, vp]),
+        "reo_perm_codes": (i32, [vp, i32, vp, i64, i64, i64, i64, vp]),
     }
     for t in ("f64", "i64", "f32", "i32"):   # SPARSE ON THE DEVICE
         sig["reo_set_matrix_csc_dev_" + t] = (i32, [vp, i64, i64, i64, vp, vp, i32, vp])
@@ -507,6 +510,96 @@ class SampleCalls(NamedTuple):
     n_down: np.ndarray   # int32, S: rows of the column called -1
 
 
+class PermNull(NamedTuple):
+    """Context.permutation_null: the label-permutation null of one comparison over B permutations.  delta1_obs[i]: Δ1 of gene i in one pass
+    on the observed table with the reference set held fixed; n_ge[i]: permutations whose |Δ1| of gene i reaches the observed one (equality
+    counts); n_up[p] / n_down[p]: genes that permutation p calls up / down under the run's pval_deg and padj_deg; se_null[p]: its pass's
+    trimmed standard deviation; delta1_null: B x G, every permutation's Δ1 (None unless keep_null=True)."""
+    delta1_obs: np.ndarray
+    n_ge: np.ndarray
+    n_up: np.ndarray
+    n_down: np.ndarray
+    se_null: np.ndarray
+    delta1_null: object = None
+
+    @property
+    def n_perm(self) -> int:
+        return int(self.n_up.size)
+
+    @property
+    def p_perm(self) -> np.ndarray:
+        """(1 + n_ge) / (1 + B): the empirical p-value with the observed labelling counted among the permutations."""
+        return (1.0 + self.n_ge) / (1.0 + self.n_perm)
+
+    def expected_false_calls(self) -> float:
+        """The mean number of genes a permutation calls (n_up + n_down)."""
+        return float(np.mean(self.n_up + self.n_down))
+
+    def fdr_hat(self, n_called_obs: int) -> float:
+        """expected_false_calls() / max(1, n_called_obs), clipped to 1."""
+        return float(min(1.0, self.expected_false_calls() / max(1, int(n_called_obs))))
+
+
+def side_a_rows(side_a, S: int) -> np.ndarray:
+    """Label rows as the B x S uint8 array (1 = side A) that the library reads; a single row becomes 1 x S.  Values other than 0 / 1 (or
+    False / True) are kept as they are for the library to refuse."""
+    rows = np.asarray(side_a)
+    if rows.dtype == bool:
+        rows = rows.astype(np.uint8)
+    if rows.ndim == 1:
+        rows = rows.reshape(1, -1)
+    if rows.ndim != 2 or rows.shape[1] != S:
+        raise DimensionMismatch(REO_EINVAL, f"side_a has shape {tuple(np.shape(side_a))}, label rows are B x S = B x {S}")
+    if rows.size and (rows.min() < 0 or rows.max() > 255):
+        raise DimensionMismatch(REO_EINVAL, "side_a: label rows hold 0 (side B) and 1 (side A)")
+    return np.ascontiguousarray(rows, dtype=np.uint8)
+
+
+def permuted_labels(group_ids, k: int, n_perm: int, seed: int = 0, strata=None, include_observed: bool = False) -> np.ndarray:
+    """n_perm label rows for Context.permutation_null: uint8 n_perm x S, 1 = side A.  The observed row is group_ids == k; every other row
+    shuffles it with numpy's Generator(PCG64(seed)) -- over all samples, or, with `strata` (one label per sample: batch, patient), within
+    each stratum, which keeps every stratum's count of ones.  The count of ones is kept in every row, the same seed gives the same rows,
+    and a row is never the observed labelling nor a repeat of an earlier row (drawn again; ValueError when the labels do not have that many
+    distinct arrangements).  include_observed=True makes row 0 the observed labelling itself (the identity)."""
+    gid = np.asarray(group_ids).reshape(-1)
+    obs = (gid == k).astype(np.uint8)
+    S = obs.size
+    if n_perm < 1:
+        raise ValueError("n_perm must be at least 1")
+    if obs.sum() == 0 or obs.sum() == S:
+        raise ValueError(f"group {k!r} holds {int(obs.sum())} of {S} samples: nothing to permute")
+    if strata is None:
+        blocks = [np.arange(S)]
+    else:
+        st = np.asarray(strata).reshape(-1)
+        if st.size != S:
+            raise ValueError(f"strata has {st.size} labels for {S} samples")
+        blocks = [np.flatnonzero(st == v) for v in sorted(set(st.tolist()), key=repr)]
+    rng = np.random.Generator(np.random.PCG64(int(seed)))
+    rows = np.empty((n_perm, S), dtype=np.uint8)
+    seen = {obs.tobytes()}
+    start = 0
+    if include_observed:
+        rows[0] = obs
+        start = 1
+    misses = 0
+    p = start
+    while p < n_perm:
+        row = obs.copy()
+        for idx in blocks:
+            row[idx] = rng.permutation(obs[idx])
+        key = row.tobytes()
+        if key in seen:
+            misses += 1
+            if misses > 1000 + 100 * n_perm:
+                raise ValueError(f"the labels have fewer than {n_perm} distinct arrangements besides the observed one")
+            continue
+        seen.add(key)
+        rows[p] = row
+        p += 1
+    return rows
+
+
 class SampleScores(NamedTuple):
     """Per DEG (row) and sample (column): of the gene's n_pairs reversed pairs (n13 and n31 against the partner set), how many show the
     order of the non-control side in that sample (treat_like), how many the control's (ctrl_like), how many are tied."""
@@ -800,6 +893,40 @@ class Context:
         check(self._L.reo_pair_counts_masked(self._h, i0, i1, j0, j1, _ptr(gt), _ptr(eq), _ptr(av)))
         return gt, eq, av
 
+    # -- label-permutation null ---------------------------------------------------
+    def perm_codes(self, side_a, k: int = 0, i0: int = 0, i1: int | None = None, j0: int = 0, j1: int | None = None) -> np.ndarray:
+        """reo_perm_codes (parity hook): the class codes of ONE permutation's table (side_a: S labels, 1 = side A) in the layout of
+        get_codes; equals get_codes of a two-group context with the same seed and thresholds and group ids 1 - side_a."""
+        i1 = self.G if i1 is None else i1
+        j1 = self.G if j1 is None else j1
+        row = side_a_rows(side_a, self.S)
+        if row.shape[0] != 1:
+            raise DimensionMismatch(REO_EINVAL, "perm_codes takes one label row")
+        code = np.zeros((max(i1 - i0, 0), max(j1 - j0, 0)), dtype=np.uint8)
+        check(self._L.reo_perm_codes(self._h, int(k), _ptr(row), i0, i1, j0, j1, _ptr(code) if code.size else None))
+        return code
+
+    def permutation_null(self, side_a, k: int = 0, ref_mask=None, pval_deg: float = 1.0, padj_deg: float = 0.05, keep_null: bool = False) -> PermNull:
+        """reo_perm_null: the label-permutation null of comparison k, whose class table must be the resident one (build_pairs(k)).
+        side_a: B x S label rows (1 = side A, exactly as many ones per row as group k has samples; permuted_labels makes them).
+        ref_mask: the reference set every pass holds fixed; None fetches ref_mask() -- the set of the last identify_degs -- before the
+        call.  One pass per permuted table with the run's pval_deg / padj_deg; all B tables of a batch come from one walk over the bit
+        planes.  The resident table is intact afterwards; ref_mask() is refused until the next identify_degs."""
+        rows = side_a_rows(side_a, self.S)
+        B = rows.shape[0]
+        ref = self.ref_mask() if ref_mask is None else np.asarray(ref_mask)
+        ref = np.ascontiguousarray(ref != 0, dtype=np.uint8)
+        if ref.size != self.G:
+            raise DimensionMismatch(REO_EINVAL, "reference mask length != number of genes")
+        d_obs = np.zeros(self.G, dtype=np.float64)
+        n_ge = np.zeros(self.G, dtype=np.int32)
+        n_up, n_down = np.zeros(max(B, 1), dtype=np.int32), np.zeros(max(B, 1), dtype=np.int32)
+        se = np.zeros(max(B, 1), dtype=np.float64)
+        null = np.zeros((B, self.G), dtype=np.float64) if keep_null else None
+        check(self._L.reo_perm_null(self._h, int(k), _ptr(rows) if rows.size else None, B, _ptr(ref), float(pval_deg), float(padj_deg), _ptr(d_obs), _ptr(n_ge),
+                                    _ptr(n_up), _ptr(n_down), _ptr(se), _opt(null)))
+        return PermNull(d_obs, n_ge, n_up[:B], n_down[:B], se[:B], null)
+
     def get_codes(self, i0: int, i1: int, j0: int, j1: int) -> np.ndarray:
         code = np.zeros((i1 - i0, j1 - j0), dtype=np.uint8)
         check(self._L.reo_get_codes(self._h, i0, i1, j0, j1, _ptr(code)))
@@ -1058,8 +1185,8 @@ class Context:
                 "k2_full_launches": int(ms[9]), "k2_delta_ms": ms[10], "set_matrix_host_wall_ms": ms[11]}
 
     def info(self) -> dict:
-        w = np.zeros(34, dtype=np.int64)
-        check(self._L.reo_get_info(self._h, _ptr(w), 34))
+        w = np.zeros(36, dtype=np.int64)
+        check(self._L.reo_get_info(self._h, _ptr(w), 36))
         v = np.zeros(28, dtype=np.int64)   # fields 0-27 keep their places (tests/test_csc_device_cpu.py reads this line); 28 is appended
         v[:] = w[:28]
         return {"G": int(v[0]), "S": int(v[1]), "Gp": int(v[2]), "table_bytes": int(v[3]), "has_ties": int(v[4]),
@@ -1071,4 +1198,5 @@ class Context:
                 "csc_upload": int(v[22]), "csc_nnz": int(v[23]), "resident_dtype": int(v[24]),
                 "k1_slot_order": int(v[25]), "k1_half_tiles_separated": int(v[26]), "csc_device": int(v[27]),
                 "k1_unslot_form": int(w[28]), "contrast_treat": int(w[29]), "k1_slot_sides": int(w[30]),
-                "masked_build": int(w[31]), "k1_slot_slice": int(w[32]), "planes_on_demand": int(w[33])}
+                "masked_build": int(w[31]), "k1_slot_slice": int(w[32]), "planes_on_demand": int(w[33]),
+                "perm_batch": int(w[34]), "perm_kernel_us": int(w[35])}

@@ -16,6 +16,7 @@
 #include "reo_internal.h"
 #include "contrast.h"
 #include "masked_pairs.h"
+#include "perm_null.h"
 #include "sample_counts.h"
 #include "upload_csc.h"
 
@@ -1569,6 +1570,185 @@ int32_t reo_get_ref_mask(reo_ctx *c, uint8_t *ref_mask, int32_t *nref)
     return REO_OK;
 }
 
+// ---- label-permutation null (kernels: permpairs.hip; rules and checks: perm_null.h) ----
+
+namespace {
+
+PnState pn_state(reo_ctx *c)
+{
+    PnState st{};
+    st.multi = c->in_multi || !c->peers.empty();
+    st.world = c->world;
+    st.G = c->dtype ? c->G : 0; st.S = c->dtype ? c->S : 0;
+    st.ngroups = c->ngroups;
+    st.n_labels = static_cast<int64_t>(c->group_id.size());
+    st.has_mask = mask_in_force(c);
+    st.thr_set = c->thr_set && c->thr.size() == 2 * static_cast<size_t>(c->ngroups);
+    st.built_k = c->built_k;
+    st.plain_table = c->built_k >= 0 && c->built_treat < 0 && !c->built_masked && c->table_complete;
+    return st;
+}
+
+// The pass kernels and the decoder read the class table through c->table.p: while one of these lives they read a permuted table instead,
+// and whatever way the call ends the resident table is the context's again.
+struct TableLoan {
+    reo_ctx *c;
+    uint32_t *resident;
+    explicit TableLoan(reo_ctx *ctx) : c(ctx), resident(ctx->table.p) {}
+    TableLoan(const TableLoan &) = delete;
+    TableLoan &operator=(const TableLoan &) = delete;
+    void lend(uint32_t *t) { c->table.p = t; }
+    void back() { c->table.p = resident; }
+    ~TableLoan() { back(); }
+};
+
+// The slot -> column map of the current groups on the device (c->sc_slot2col), behind ensure_transform.
+int32_t pn_slot_map(reo_ctx *c, const char *what)
+{
+    std::vector<int32_t> map;
+    if (!sc_slot_map(c->group_id.data(), c->S, c->ngroups, map) || c->goff32.empty() || static_cast<int64_t>(map.size()) != c->goff32.back()) {
+        set_error("%s: the sample slots of the bit planes do not match the group labels", what);
+        return REO_EHIP;
+    }
+    int32_t rc = c->sc_slot2col.ensure(map.size());
+    return rc ? rc : upload_slot2col(c, map);
+}
+
+int32_t pn_side_size(const reo_ctx *c, int32_t k)
+{
+    int32_t n1 = 0;
+    for (int32_t g : c->group_id) n1 += g == k;
+    return n1;
+}
+
+}  // namespace
+
+int32_t reo_perm_codes(reo_ctx *c, int32_t k, const uint8_t *side_a, int64_t i0, int64_t i1, int64_t j0, int64_t j1, uint8_t *code)
+{
+    int32_t rc = use(c);
+    if (rc) return rc;
+    const PnState st = pn_state(c);
+    char msg[320];
+    const int32_t n1 = (k >= 0 && k < c->ngroups) ? pn_side_size(c, k) : 0;
+    if (pn_check_codes_args(st, k, side_a, n1, i0, i1, j0, j1, code, msg, sizeof msg)) { set_error("%s", msg); return REO_EINVAL; }
+    if ((rc = ensure_transform(c)) || (rc = pn_slot_map(c, "reo_perm_codes"))) return rc;
+    const int nblk = c->goff32.back() / 32;
+    const size_t table_words = static_cast<size_t>(c->G) * kPlanes * c->Wp, n = static_cast<size_t>(i1 - i0) * (j1 - j0);
+    // REO_PERM_CODES_SLOT=q (tests): the permutation sits in table q of a batch of q + 1 -- the other tables get rotations of the row, which
+    // keep its count of ones -- so that the codes of a table behind the first, and behind the first launch group, can be looked at whole
+    const char *env = getenv("REO_PERM_CODES_SLOT");
+    int slot = env ? atoi(env) : 0;
+    if (slot < 0 || slot >= kPermBatchCap) slot = 0;
+    const int np = slot + 1;
+    const size_t S = static_cast<size_t>(c->S);
+    std::vector<uint8_t> rep(static_cast<size_t>(np) * S);
+    for (int t = 0; t < np; ++t)
+        for (size_t s = 0; s < S; ++s) rep[static_cast<size_t>(t) * S + s] = side_a[t == slot ? s : (s + static_cast<size_t>(t) + 1) % S];
+    DevBuf<uint32_t> d_table, d_aw, d_live;
+    DevBuf<uint8_t> d_side, d_code;
+    if ((rc = d_table.ensure(static_cast<size_t>(np) * table_words)) || (rc = d_aw.ensure(pn_word_count(np, nblk))) || (rc = d_live.ensure(nblk)) ||
+        (rc = d_side.ensure(rep.size())) || (rc = d_code.ensure(n)))
+        return rc;
+    TableLoan loan(c);      // (after the buffers: the table pointer is the context's again before they go)
+    DrainOnExit drain(c);   // the rows in, code out
+    REO_HIP_CHECK(hipMemcpyAsync(d_side.p, rep.data(), rep.size(), hipMemcpyHostToDevice, c->stream));
+    REO_HIP_CHECK(hipMemsetAsync(d_table.p, 0, static_cast<size_t>(np) * table_words * sizeof(uint32_t), c->stream));
+    if ((rc = launch_perm_words(c, d_side.p, np, c->sc_slot2col.p, d_aw.p, d_live.p)) ||
+        (rc = launch_pairs_permuted(c, d_aw.p, d_live.p, np, n1, static_cast<int>(c->S) - n1, c->thr[2 * k], c->thr[2 * k + 1], d_table.p)))
+        return rc;
+    loan.lend(d_table.p + static_cast<size_t>(slot) * table_words);
+    rc = launch_decode(c, i0, i1, j0, j1, d_code.p);
+    loan.back();
+    if (rc) return rc;
+    REO_HIP_CHECK(hipMemcpyAsync(code, d_code.p, n, hipMemcpyDeviceToHost, c->stream));
+    REO_HIP_CHECK(hipStreamSynchronize(c->stream));
+    drain.dismiss();
+    return REO_OK;
+}
+
+int32_t reo_perm_null(reo_ctx *c, int32_t k, const uint8_t *side_a, int64_t n_perm, const uint8_t *ref_mask, double pval_deg, double padj_deg,
+                      double *delta1_obs, int32_t *n_ge, int32_t *n_up, int32_t *n_down, double *se_null, double *delta1_null)
+{
+    int32_t rc = use(c);
+    if (rc) return rc;
+    // every refusal first: a refused call leaves the table, the reference mask and the iteration's buffers as they were
+    const PnState st = pn_state(c);
+    char msg[320];
+    const int32_t n1 = (k >= 0 && k < c->ngroups) ? pn_side_size(c, k) : 0;
+    if (pn_check_null_args(st, k, side_a, n_perm, n1, ref_mask, pval_deg, padj_deg, delta1_obs, n_ge, n_up, n_down, se_null, msg, sizeof msg)) {
+        set_error("%s", msg);
+        return REO_EINVAL;
+    }
+    if ((rc = need_complete_table(c)) || (rc = ensure_transform(c))) return rc;
+    if ((rc = wait_or_drop_table(c))) return rc;   // (the resident table's own build, if it is still running)
+    const int64_t G = c->G, S = c->S;
+    const int nblk = c->goff32.back() / 32;
+    const size_t table_words = static_cast<size_t>(G) * kPlanes * c->Wp;
+    size_t free_b = 0, total_b = 0;
+    REO_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+    const char *env = getenv("REO_PERM_BATCH");
+    const int64_t P = pn_batch_tables(free_b, table_words * sizeof(uint32_t), n_perm, env ? atoll(env) : 0);
+    if (P < 1) {
+        set_error("reo_perm_null: one permuted class table needs %zu bytes of device memory beside the resident one, %zu are free", table_words * sizeof(uint32_t),
+                  free_b);
+        return REO_ENOMEM;
+    }
+    c->perm_batch = P; c->perm_kernel_us = 0;
+    DevBuf<uint32_t> d_tables, d_aw, d_live;
+    DevBuf<uint8_t> d_side;
+    DevBuf<double> d_obs, d_se;
+    DevBuf<int32_t> d_nge, d_cnt;   // d_cnt: n_up [n_perm], then n_down [n_perm]
+    if ((rc = d_tables.ensure(static_cast<size_t>(P) * table_words)) || (rc = d_aw.ensure(pn_word_count(P, nblk))) || (rc = d_live.ensure(nblk)) ||
+        (rc = d_side.ensure(static_cast<size_t>(P) * S)) || (rc = d_obs.ensure(G)) || (rc = d_se.ensure(n_perm)) || (rc = d_nge.ensure(G)) ||
+        (rc = d_cnt.ensure(2 * static_cast<size_t>(n_perm))) || (rc = pn_slot_map(c, "reo_perm_null")))
+        return rc;
+    std::vector<double> host_res(static_cast<size_t>(15) * G);
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    REO_HIP_CHECK(hipEventCreate(&ev[0]));
+    if (hipEventCreate(&ev[1]) != hipSuccess) { (void)hipEventDestroy(ev[0]); set_error("reo_perm_null: no event"); return REO_EHIP; }
+    struct EventPair { hipEvent_t *e; ~EventPair() { (void)hipEventDestroy(e[0]); (void)hipEventDestroy(e[1]); } } ev_guard{ev};
+    TableLoan loan(c);      // (after the buffers: the table pointer is the context's again before they go)
+    DrainOnExit drain(c);   // the caller's arrays in and out
+    // the observed pass: what reo_identify_degs(ref_mask, n_iter = 1) gives on the resident table
+    int32_t iters = 0;
+    if ((rc = reo_identify_degs(c, ref_mask, pval_deg, padj_deg, 1, 0, host_res.data(), &iters, nullptr))) return rc;
+    memcpy(delta1_obs, host_res.data() + 11 * G, sizeof(double) * G);
+    REO_HIP_CHECK(hipMemcpyAsync(d_obs.p, c->result.p + 11 * G, sizeof(double) * G, hipMemcpyDeviceToDevice, c->stream));
+    REO_HIP_CHECK(hipMemsetAsync(d_nge.p, 0, sizeof(int32_t) * G, c->stream));
+    REO_HIP_CHECK(hipMemsetAsync(d_cnt.p, 0, sizeof(int32_t) * 2 * n_perm, c->stream));
+    REO_HIP_CHECK(hipMemsetAsync(d_tables.p, 0, static_cast<size_t>(P) * table_words * sizeof(uint32_t), c->stream));   // (once: see permpairs.hip)
+    for (int64_t p0 = 0; p0 < n_perm; p0 += P) {
+        const int np = static_cast<int>(std::min<int64_t>(P, n_perm - p0));
+        REO_HIP_CHECK(hipMemcpyAsync(d_side.p, side_a + p0 * S, static_cast<size_t>(np) * S, hipMemcpyHostToDevice, c->stream));
+        if ((rc = launch_perm_words(c, d_side.p, np, c->sc_slot2col.p, d_aw.p, d_live.p))) return rc;
+        REO_HIP_CHECK(hipEventRecord(ev[0], c->stream));
+        if ((rc = launch_pairs_permuted(c, d_aw.p, d_live.p, np, n1, static_cast<int>(S) - n1, c->thr[2 * k], c->thr[2 * k + 1], d_tables.p))) return rc;
+        REO_HIP_CHECK(hipEventRecord(ev[1], c->stream));
+        for (int q = 0; q < np; ++q) {
+            const int64_t p = p0 + q;
+            loan.lend(d_tables.p + static_cast<size_t>(q) * table_words);
+            rc = reo_identify_degs(c, ref_mask, pval_deg, padj_deg, 1, 0, host_res.data(), &iters, nullptr);
+            loan.back();
+            if (rc) return rc;
+            if (q == 0) {   // (the pass has waited for the stream: both events have happened)
+                float ms = 0.f;
+                REO_HIP_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+                c->perm_kernel_us += static_cast<int64_t>(ms * 1000.0f + 0.5f);
+            }
+            if ((rc = launch_perm_accumulate(c, d_obs.p, pval_deg, padj_deg, d_nge.p, d_cnt.p + p, d_cnt.p + n_perm + p, d_se.p + p))) return rc;
+            if (delta1_null) memcpy(delta1_null + p * G, host_res.data() + 11 * G, sizeof(double) * G);
+        }
+    }
+    REO_HIP_CHECK(hipMemcpyAsync(n_ge, d_nge.p, sizeof(int32_t) * G, hipMemcpyDeviceToHost, c->stream));
+    REO_HIP_CHECK(hipMemcpyAsync(n_up, d_cnt.p, sizeof(int32_t) * n_perm, hipMemcpyDeviceToHost, c->stream));
+    REO_HIP_CHECK(hipMemcpyAsync(n_down, d_cnt.p + n_perm, sizeof(int32_t) * n_perm, hipMemcpyDeviceToHost, c->stream));
+    REO_HIP_CHECK(hipMemcpyAsync(se_null, d_se.p, sizeof(double) * n_perm, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = wait_or_drop_table(c))) return rc;
+    drain.dismiss();
+    drop_ref_mask(c, "reo_perm_null has run since the last reo_identify_degs: its passes use the iteration's buffers");
+    return REO_OK;
+}
+
 int32_t reo_mccullagh(reo_ctx *c, const int32_t *cont, int64_t n, double *out)
 {
     int32_t rc = use(c);
@@ -1623,7 +1803,7 @@ int32_t reo_get_info(reo_ctx *c, int64_t *info, int32_t n)
         int32_t rc = use(c);
         if (rc || (rc = launch_slot_separated(c, &separated))) return rc;
     }
-    const int64_t v[34] = {c->G, c->S, c->Gp, static_cast<int64_t>(c->table.n * sizeof(uint32_t)), c->has_ties,
+    const int64_t v[36] = {c->G, c->S, c->Gp, static_cast<int64_t>(c->table.n * sizeof(uint32_t)), c->has_ties,
                            c->tiles_owned, c->tiles_total, kTileI, c->k1_cj, c->k1_q, kUnitH,
                            c->goff32.empty() ? 0 : c->goff32.back(), c->last_k1_shared,
                            static_cast<int64_t>(c->gcounts.n * sizeof(uint16_t)), c->transform_in_lds, c->xcc_local,
@@ -1631,8 +1811,8 @@ int32_t reo_get_info(reo_ctx *c, int64_t *info, int32_t n)
                            c->csc_upload, c->csc_nnz, c->dtype, c->last_k1_slots, separated, c->csc_device,
                            c->last_k1_slots ? c->last_k1_unslot : 0, c->built_k >= 0 ? c->built_treat : -1,
                            c->last_k1_slots ? c->last_k1_slot_sides : 0, (c->built_k >= 0 && c->built_masked) ? 1 : 0,
-                           c->last_k1_slots ? c->last_k1_slot_slice : 0, c->transformed ? c->planes_on_demand : 0};
-    for (int i = 0; i < n && i < 34; ++i) info[i] = v[i];
+                           c->last_k1_slots ? c->last_k1_slot_slice : 0, c->transformed ? c->planes_on_demand : 0, c->perm_batch, c->perm_kernel_us};
+    for (int i = 0; i < n && i < 36; ++i) info[i] = v[i];
     return REO_OK;
 }
 

@@ -337,6 +337,9 @@ struct reo_ctx {
     double mp_thr_pval = -1.0;          // ... and this pval_reo
     const int32_t *mp_thr_uploaded = nullptr;   // ... and in which allocation
     int built_masked = 0;               // reo_get_info 31: the resident class table came from reo_build_pairs_masked
+    // label-permutation null (reo_perm_null; permpairs.hip, perm_null.h)
+    int64_t perm_batch = 0;             // reo_get_info 34: tables per batch of the last reo_perm_null
+    int64_t perm_kernel_us = 0;         // reo_get_info 35: microseconds its launches of k_pairs_permuted took in all (HIP events)
     reo::DevBuf<int32_t> raw;           // [G][8]
     reo::DevBuf<uint32_t> delta_list;   // [2][Gp] changed genes (gene << 1 | added) per pass parity
     reo::DevBuf<int32_t> cont;          // [G][9]
@@ -484,6 +487,17 @@ int32_t launch_pair_support(reo_ctx *c, const PsItem *d_items, int64_t n_items, 
 int32_t launch_valid_words(reo_ctx *c, const int32_t *d_slot2col);
 int32_t launch_pairs_masked(reo_ctx *c, int k, const int32_t *d_m1, int n1, const int32_t *d_m2, int n2, int min_complete1, int min_complete2);
 int32_t launch_counts_masked(reo_ctx *c, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int32_t *d_gt, int32_t *d_eq, int32_t *d_avail);
+
+// permpairs.hip: the kernels of reo_perm_null / reo_perm_codes (shared arithmetic and host checks: perm_null.h).  launch_perm_words: the label
+// rows d_side ([n_perm][S] bytes, checked by the caller) and d_slot2col ([32 * sample blocks], -1 for padding) into the A-words d_aw
+// (pn_word_count(n_perm, blocks) words, cleared here) and the live words d_live ([blocks]).  launch_pairs_permuted: the class tables of
+// permutations 0 .. np - 1 of those words into d_tables ([np][G][4][Wp]; the caller has cleared it once), sides of n1 / n2 samples held to
+// m1 / m2.  launch_perm_accumulate: the pass result in c->result against d_obs ([G] observed delta1) into d_n_ge ([G]) and the
+// permutation's own d_n_up, d_n_down, d_se ([1] each)
+int32_t launch_perm_words(reo_ctx *c, const uint8_t *d_side, int64_t n_perm, const int32_t *d_slot2col, uint32_t *d_aw, uint32_t *d_live);
+int32_t launch_pairs_permuted(reo_ctx *c, const uint32_t *d_aw, const uint32_t *d_live, int np, int n1, int n2, int m1, int m2, uint32_t *d_tables);
+int32_t launch_perm_accumulate(reo_ctx *c, const double *d_obs, double pval_deg, double padj_deg, int32_t *d_n_ge, int32_t *d_n_up, int32_t *d_n_down,
+                               double *d_se);
 
 // pseudobulk.hip: the checks, upload and kernels of reo_pseudobulk_*, the G x n_out sums left in c->dX_owned (ld = G) instead of a host array
 int32_t pseudobulk_resident_dense(reo_ctx *c, const void *X, bool is_int, int64_t G, int64_t C, int64_t ld, const int32_t *order,

@@ -15,7 +15,7 @@ from typing import NamedTuple
 import numpy as np
 
 from . import _ffi, synth
-from ._ffi import PairList, PairSupport, SampleCalls, SampleCounts, SampleScores, SampleTests, class_mask  # noqa: F401
+from ._ffi import PairList, PairSupport, PermNull, SampleCalls, SampleCounts, SampleScores, SampleTests, class_mask, permuted_labels  # noqa: F401
 
 HEADER = ["pval", "padj", "n11", "n12", "n13", "n21", "n22", "n23", "n31", "n32", "n33",
           "Δ1", "Δ2", "se", "z1", "up_down"]  # src/RankCompV3.jl:665
@@ -212,6 +212,50 @@ def write_pairs_tsv(path, gene_names, pair_list) -> None:
                 f.write(f"{gname}\t{gene_names[int(j)]}\t{names[int(c)]}\n")
 
 
+def perm_plan(permutations, *, contrasts=None, masked=False, shard=(0, 1)) -> None:
+    """The refusals of `permutations`, raised before any context is opened: a count below 1, and the routes that have no permutation
+    null -- `contrasts`, a validity mask (missing="pairwise" / `valid`) and shard[1] > 1."""
+    if permutations is None:
+        return
+
+    def bad(why):
+        return _ffi.DimensionMismatch(_ffi.REO_EINVAL, why)
+    if int(permutations) < 1:
+        raise bad(f"permutations = {permutations!r}: None (no permutation null) or a count of at least 1")
+    if contrasts is not None:
+        raise bad("permutations: the label-permutation null shuffles a comparison's two sides; it is not available together with `contrasts`")
+    if masked:
+        raise bad("permutations: the label-permutation null compares on the whole matrix and would count the fillers under the validity "
+                  "mask; it is not available together with missing=\"pairwise\" or `valid`")
+    if shard[1] > 1:
+        raise bad(f"permutations: the permuted build has no sharded form (shard = {tuple(shard)!r})")
+
+
+def deg_perm_null(ctx, gid, k, permutations, perm_seed, perm_strata, pval_deg, padj_deg) -> dict:
+    """{"perm_null"} of the comparison whose identify_degs has just returned on `ctx`: the PermNull of `permutations` shuffles of its two
+    sides (permuted_labels: seed perm_seed + k, within perm_strata if given), the reference set held at that of the run's last pass.
+    Taken LAST among a comparison's read-outs: afterwards Context.ref_mask is refused until the next identify_degs."""
+    rows = permuted_labels(gid, k, int(permutations), seed=int(perm_seed) + int(k), strata=perm_strata)
+    return {"perm_null": ctx.permutation_null(rows, k=k, ref_mask=ctx.ref_mask(), pval_deg=pval_deg, padj_deg=padj_deg)}
+
+
+def write_perm_null_tsv(path, gene_names, perm_null) -> None:
+    """gene<TAB>delta1<TAB>n_ge<TAB>p_perm, one row per gene in gene order; a header line, "\n" line ends, like the result writers."""
+    pp = perm_null.p_perm
+    with open(path, "w") as f:
+        f.write("gene\tdelta1\tn_ge\tp_perm\n")
+        for i, g in enumerate(gene_names):
+            f.write(f"{g}\t{float(perm_null.delta1_obs[i])!r}\t{int(perm_null.n_ge[i])}\t{float(pp[i])!r}\n")
+
+
+def write_perm_summary_tsv(path, perm_null) -> None:
+    """perm<TAB>n_up<TAB>n_down<TAB>se, one row per permutation in the order of its label rows; a header line and no trailer."""
+    with open(path, "w") as f:
+        f.write("perm\tn_up\tn_down\tse\n")
+        for p in range(perm_null.n_perm):
+            f.write(f"{p}\t{int(perm_null.n_up[p])}\t{int(perm_null.n_down[p])}\t{float(perm_null.se_null[p])!r}\n")
+
+
 def missing_plan(data, missing, valid, *, shard=(0, 1), contrasts=None, sample_scores=False, sample_tests=False, sample_calls=False,
                  pair_support=False):
     """The pairwise route of run_identify_degs, decided before any context is opened.  Pure: no library, no GPU.  Returns (data, mask):
@@ -259,7 +303,8 @@ def missing_plan(data, missing, valid, *, shard=(0, 1), contrasts=None, sample_s
 def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref_gene, n_iter, n_conv, *,
                       seed: int = 0, device: int = -1, shard=(0, 1), allreduce=None, allgather=None, profile: bool = False,
                       pairs=None, sample_scores: bool = False, pair_support: bool = False, contrasts=None,
-                      sample_tests: bool = False, sample_calls: bool = False, missing=None, valid=None, min_complete=None) -> DegRun:
+                      sample_tests: bool = False, sample_calls: bool = False, missing=None, valid=None, min_complete=None,
+                      permutations=None, perm_seed: int = 0, perm_strata=None) -> DegRun:
     """identify_degs with the extras (trace, timings) kept.  `data` is a host matrix (numpy, anything np.asarray takes) or a torch
     tensor on a ROCm device, which is used in place (_ffi.device_matrix).  A column-major host matrix is read in place; a row-major one
     (numpy's default C order, column slices of a wider C-ordered array) is copied column-major on the host first, or, with REO_ROWMAJOR=1
@@ -303,10 +348,16 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
     against the threshold of that many samples, and a side with fewer than `min_complete` of them (None: per side min(side size, 8 at
     pval_reo = 0.01); an int: both sides) is unstable.  The comparison dict gains "min_complete", and info["masked_build"] reads 1.
     `pairs` works; `contrasts`, `sample_scores`, `sample_tests`, `sample_calls`, `pair_support`, a sparse or device-resident matrix and
-    shard[1] > 1 are refused together with a mask (missing_plan).  Defaults: nothing changes, and a NaN is refused as always."""
+    shard[1] > 1 are refused together with a mask (missing_plan).  Defaults: nothing changes, and a NaN is refused as always.
+    `permutations`, `perm_seed`, `perm_strata` (not in the reference): permutations=B adds "perm_null" to every comparison dict, the
+    PermNull of B label shuffles of the comparison's two sides (Context.permutation_null; rows from permuted_labels with seed perm_seed + k,
+    shuffled within perm_strata -- one label per sample -- when given), the reference set held at that of the run's last pass; taken after
+    every other read-out of the comparison.  Refused with `contrasts`, with a mask and with shard[1] > 1 (perm_plan).  None (the default):
+    no further call, no new key."""
     need_pairs_for_support(pairs, pair_support)
     data, mask = missing_plan(data, missing, valid, shard=shard, contrasts=contrasts, sample_scores=sample_scores, sample_tests=sample_tests,
                               sample_calls=sample_calls, pair_support=pair_support)
+    perm_plan(permutations, contrasts=contrasts, masked=mask is not None, shard=shard)
     if mask is not None:
         _ffi.resolve_min_complete(min_complete, (1, 1), pval_reo)   # (its refusals, before a context is opened)
     # a torch tensor on a ROCm device: a strided one is used where it is, a sparse one is made dense there (its device is the context's)
@@ -365,6 +416,8 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
                 comps[-1]["sample_tests"] = ctx.sample_tests()   # all genes, against the reference set of this comparison's tallies
             if sample_calls:
                 comps[-1]["sample_calls"] = ctx.sample_calls(pval_deg, padj_deg)   # all genes, the run's thresholds, the same reference set
+            if permutations is not None:   # last: it uses the iteration's buffers (ref_mask is refused behind it)
+                comps[-1].update(deg_perm_null(ctx, gid, k, permutations, perm_seed, perm_strata, pval_deg, padj_deg))
         timings = ctx.timings() if profile else {}
         info = ctx.info()
     first = comps[0]
@@ -404,7 +457,8 @@ class CellsDegRun(NamedTuple):
 def identify_degs_cells(cells, cell_group, gene_names, n_pseudo, pval_reo, pval_deg, padj_deg, ref_gene, n_iter, n_conv, *,
                         min_profiles: int = 0, min_features: int = 0, ref_gene_max: int = 3000, seed: int = 0, device: int = 0,
                         profile: bool = False, pairs=None, sample_scores: bool = False, pair_support: bool = False,
-                        contrasts=None, sample_tests: bool = False, sample_calls: bool = False) -> CellsDegRun:
+                        contrasts=None, sample_tests: bool = False, sample_calls: bool = False,
+                        permutations=None, perm_seed: int = 0, perm_strata=None) -> CellsDegRun:
     """Cells to DEGs without a host trip for the profiles: `cells` is a genes x cells matrix (scipy.sparse, anything np.asarray takes, or
     a torch tensor on a ROCm device -- sparse or strided -- which is read where it is: reo_set_matrix_pseudobulk_*_dev_*),
     cell_group one label per cell.  cells_partition -> the pseudo-bulk sums written into the context's matrix (set_matrix_pseudobulk) ->
@@ -414,8 +468,10 @@ def identify_degs_cells(cells, cell_group, gene_names, n_pseudo, pval_reo, pval_
     run_identify_degs on the same seed.  (reoa() keeps its host route: its writers want the profile matrix on the host.)
     `pairs`, `sample_scores`, `pair_support`, `sample_tests`, `sample_calls`: as in run_identify_degs; gene indices are those of the KEPT genes (run.gene_names), columns
     the kept profiles.  `contrasts`: as in run_identify_degs, over the group levels of the cells (checked against the levels of cell_group
-    before any context is opened, and again against those of the kept profiles)."""
+    before any context is opened, and again against those of the kept profiles).  `permutations`, `perm_seed`, `perm_strata`: as in
+    run_identify_degs; perm_strata has one label per pseudo-bulk PROFILE of cells_partition (the kept ones are used)."""
     need_pairs_for_support(pairs, pair_support)
+    perm_plan(permutations, contrasts=contrasts)
     on_device = _ffi.is_device_sparse(cells) or _ffi.is_device_tensor(cells)
     if on_device:   # a torch tensor on a ROCm device, sparse or strided: summed where it is, on its own device
         device = cells.device.index if cells.device.index is not None else -1
@@ -463,6 +519,9 @@ def identify_degs_cells(cells, cell_group, gene_names, n_pseudo, pval_reo, pval_
                 comps[-1]["sample_tests"] = ctx.sample_tests()   # all genes, against the reference set of this comparison's tallies
             if sample_calls:
                 comps[-1]["sample_calls"] = ctx.sample_calls(pval_deg, padj_deg)   # all genes, the run's thresholds, the same reference set
+            if permutations is not None:   # last: it uses the iteration's buffers (ref_mask is refused behind it)
+                strata = None if perm_strata is None else np.asarray(perm_strata)[np.asarray(profile_kept, dtype=bool)]
+                comps[-1].update(deg_perm_null(ctx, gid, k, permutations, perm_seed, strata, pval_deg, padj_deg))
         timings = ctx.timings() if profile else {}
         info = ctx.info()
     first = comps[0]
