@@ -7,8 +7,11 @@
 //   - sc_slot_map for interleaved labels (33 / 37), for groups of 1, 31, 32 and 33 samples, and for a label out of range;
 //   - sc_batch_rows, and every argument check of sample_counts_check_args with its number and message.
 // Prints "adds <n> <planes>" per case and "ok <checks>"; anything on stderr is a failure.
+// With the arguments "map <ngroups> <S>" it reads S group ids from stdin instead, checks sc_slot_map on them as above and prints the map
+// (tests/test_wide_sample_cases_cpu.py compares it with the numpy restatement of tests/perm_null_cases.py on layouts of 13 and 17 blocks).
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -137,10 +140,28 @@ void run_checks()
     expect(reo::sc_batch_rows(8, reo::kScBudgetBytes, -2) == 1, "at least one row");
 }
 
+// "map <ngroups> <S>" and S group ids on stdin: the structural checks of check_map on that layout, then sc_slot_map's slots on one line
+int print_map(int ngroups, long S)
+{
+    if (ngroups < 1 || S < 1 || S > (1 << 20)) { fprintf(stderr, "map: bad sizes\n"); return 2; }
+    std::vector<int32_t> gid(static_cast<size_t>(S)), map;
+    for (long s = 0; s < S; ++s) {
+        long v = -1;
+        if (scanf("%ld", &v) != 1 || v < 0 || v >= ngroups) { fprintf(stderr, "map: bad group id at %ld\n", s); return 2; }
+        gid[static_cast<size_t>(s)] = static_cast<int32_t>(v);
+    }
+    check_map(gid, ngroups);
+    if (g_fail || !reo::sc_slot_map(gid.data(), S, ngroups, map)) { fprintf(stderr, "%ld failures\n", g_fail); return 1; }
+    for (size_t t = 0; t < map.size(); ++t) printf(t ? " %d" : "%d", map[t]);
+    printf("\nok %ld\n", g_checks);
+    return 0;
+}
+
 }  // namespace
 
-int main()
+int main(int argc, char **argv)
 {
+    if (argc == 4 && !strcmp(argv[1], "map")) return print_map(atoi(argv[2]), atol(argv[3]));
     for (int n : {1, 2, 63, 64, 65, 127}) {
         for (int kind = 0; kind < 3; ++kind) run_adds(n, kind);
         printf("adds %d %d\n", n, reo::sc_counter_planes(n));
