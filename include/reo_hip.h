@@ -388,6 +388,43 @@ int32_t reo_pair_support(reo_ctx *ctx, const int32_t *genes, int64_t n_genes,
                          int32_t *n_gt, int32_t *n_eq /* entries x ngroups, row-major; n_eq may be NULL */,
                          uint8_t *outcome /* entries x S, row-major, caller's column order; may be NULL */);
 
+/* Top-scoring pairs: WHICH few gene pairs, out of all G (G - 1) / 2, separate two sides best?  Every other read-out starts from a gene that
+ * the tallies already call; this one is the search of Geman's top-scoring pair and of Tan's k-TSP: it finds the two-gene signature that
+ * reo_pair_support takes as input.  The reference has no such output.
+ * Sides: A = the samples of group a, B = those of group b, or, with b = -1, every sample not in a (the two sides of reo_build_pairs with
+ * k = a); S_A and S_B their sizes.  Per pair and side, by the comparator of the resident element type exactly as reo_pair_support counts:
+ * gt = samples with x_i above x_j and not tied, eq = tied samples, lt = S_side - gt - eq; no tie coin is drawn.
+ *     w(side) = gt - lt        N_ij = w(A) S_B - w(B) S_A   (int64, antisymmetric)        score = |N| / (2 S_A S_B)  in [0, 1]
+ * On tie-free data the score is |gt_A / S_A - gt_B / S_B|, Geman's Delta; in general N / (S_A S_B) = 2 delta + eq_A / S_A - eq_B / S_B with
+ * delta = gt_A / S_A - gt_B / S_B: ties count half to each side.  Equal |N| are ordered by the rank shift, as TSP does: per gene
+ *     W_i(side) = sum over the side's samples of (genes that i lies above, untied) - (genes that i lies below, untied)
+ *     D_i = W_i(A) S_B - W_i(B) S_A        Gamma_ij = |D_i - D_j|        (tie-free: Gamma / (2 S_A S_B) is Tan's gamma)
+ * reo_rank_shift delivers D (G values, host).  The order over the unordered pairs i < j with both genes inside gene_mask (NULL: all
+ * genes): |N| descending, then Gamma descending, then i ascending, then j ascending -- a total order -- and reo_top_pairs returns its first
+ * n_want elements in that order: gene_i < gene_j, counts[4 e ..] = gt_A, eq_A, gt_B, eq_B of "gene_i above gene_j", key[2 e] = N (signed),
+ * key[2 e + 1] = Gamma, *n_found = min(n_want, eligible pairs).  The result does not depend on the launch geometry, on the arrival order of
+ * atomics or on the candidate capacity.  With G, S <= 65535: |N| < 2^31, |D| <= 2^47, Gamma <= 2^48.
+ * Needs the matrix, the groups and the transform (run here if need be); no class table, no thresholds, no reference set.  Reads and writes
+ * none of the iteration's buffers: the resident table, reo_get_ref_mask and a following reo_identify_degs behave as if the call had not
+ * happened.  Host arrays only, allocated by the caller; no stage timer of its own.
+ * Selection without a score per pair (csrc/toppairs.hip, csrc/top_pairs.h): the key (|N|, Gamma, 2^32 - 1 - (i G + j)) is one number of
+ * 111 bits; a radix select over its 12-bit digits RECOUNTS all pairs in every pass -- the pair kernel's O(G^2 S) work on the resident bit
+ * planes, histogrammed per workgroup in LDS --, the host reads 4098 counters back, picks the bin of the n_want-th key and extends the prefix,
+ * skipping the digits that 2 S_A S_B and max D - min D prove zero.  As soon as the keys above the prefix and those that share it fit the
+ * candidate buffer -- max(4 n_want, 2^18) records; REO_TOP_PAIRS_CAP in the environment, read per call, lowers it, never below n_want
+ * (tests of deep refinement) -- one emit pass appends them and the host sorts by the full key.  *passes_run (may be NULL) = histogram
+ * passes; reo_get_info 36 and 37 = microseconds of the histogram passes and of the emit pass of the last call (HIP events).  Device
+ * temporaries: the histogram, D, the mask bits, the candidates; nothing scales with G^2.
+ * REO_EINVAL, each with its own message, all checked on the host before anything is uploaded, and a refused call writes nothing: a
+ * reo_create_multi context; a sharded context; a validity mask set; G or S above 65535 (the 16-plane layout only); n_want outside
+ * [1, 2^20]; a or b outside the groups; b == a; a gene_mask byte other than 0 or 1; a NULL output other than passes_run. */
+int32_t reo_rank_shift(reo_ctx *ctx, int32_t a, int32_t b /* -1: every other sample */, int64_t *D /* G */);
+int32_t reo_top_pairs(reo_ctx *ctx, int32_t a, int32_t b, const uint8_t *gene_mask /* G bytes 0/1, or NULL */,
+                      int64_t n_want, int32_t *gene_i, int32_t *gene_j,
+                      int32_t *counts /* [n_want][4]: gt_A, eq_A, gt_B, eq_B of (gene_i above gene_j) */,
+                      int64_t *key /* [n_want][2]: N (signed), Gamma */,
+                      int64_t *n_found, int32_t *passes_run /* may be NULL */);
+
 /* Missing values: pair classes from the samples where BOTH genes were observed.  The reference drops every gene with a missing cell
  * (dropmissing!, src/RankCompV3.jl:601) and the library refuses a NaN; with a validity mask V beside the resident matrix a pair (i, j) is
  * compared in the samples where both values exist, and its stability is judged against the threshold of that many samples.
@@ -404,7 +441,8 @@ int32_t reo_pair_support(reo_ctx *ctx, const int32_t *genes, int64_t n_genes,
  * the resident matrix's.  NULL clears the mask.  The bytes are kept on the device, so a later reo_set_groups needs nothing from the
  * caller; a matrix of another shape drops the mask.  The matrix cell under an invalid byte is ignored, but it must still be a number
  * the library accepts: NaN stays refused, the caller writes a filler.
- * While a mask is set, reo_sample_counts, reo_sample_tests, reo_sample_calls, reo_pair_support and reo_build_pairs_contrast are refused
+ * While a mask is set, reo_sample_counts, reo_sample_tests, reo_sample_calls, reo_pair_support, reo_rank_shift, reo_top_pairs and
+ * reo_build_pairs_contrast are refused
  * (REO_EINVAL, a message that names the mask): they compare on the planes of the whole matrix and would count the fillers.  With no mask
  * set, no call behaves differently.
  *

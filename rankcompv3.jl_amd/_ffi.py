@@ -35,7 +35,7 @@ SYMBOLS = [
     "reo_set_matrix_pseudobulk_dense_f64", "reo_set_matrix_pseudobulk_dense_i64", "reo_set_matrix_pseudobulk_csc_f64", "reo_set_matrix_pseudobulk_csc_i64",
     "reo_filter_matrix", "reo_get_matrix", "reo_get_ref_mask", "reo_pair_list", "reo_sample_counts", "reo_pair_support",
     "reo_sample_tests", "reo_sample_calls", "reo_set_valid_mask", "reo_build_pairs_masked", "reo_pair_counts_masked",
-    "reo_perm_null", "reo_perm_codes",
+    "reo_perm_null", "reo_perm_codes", "reo_rank_shift", "reo_top_pairs",
 ] +[f"reo_set_matrix_{form}_{t}" for form in ("csc_dev", "pseudobulk_csc_dev", "pseudobulk_dense_dev") for t in ("f64", "i64", "f32", "i32")]
 
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p)
@@ -150,6 +150,8 @@ def lib() -> ctypes.CDLL:
         "reo_pair_counts_masked": (i32, [vp, i64, i64, i64, i64, vp, vp, vp]),
         "reo_perm_null": (i32, [vp, i32, vp, i64, vp, f64, f64, vp, vp, vp, vp, vp, vp]),
         "reo_perm_codes": (i32, [vp, i32, vp, i64, i64, i64, i64, vp]),
+        "reo_rank_shift": (i32, [vp, i32, i32, vp]),
+        "reo_top_pairs": (i32, [vp, i32, i32, vp, i64, vp, vp, vp, vp, vp, vp]),
     }
     for t in ("f64", "i64", "f32", "i32"):   # SPARSE ON THE DEVICE
         sig["reo_set_matrix_csc_dev_" + t] = (i32, [vp, i64, i64, i64, vp, vp, i32, vp])
@@ -446,6 +448,67 @@ class PairSupport(NamedTuple):
         d = np.abs(self.delta(k))
         order = np.lexsort((self.partner, self.entry_genes, -d))   # (the last key is the primary one)
         return order[: max(int(n), 0)]
+
+
+class TopPairs(NamedTuple):
+    """reo_top_pairs: the n best of all gene pairs i < j for side A (group a) against side B (group b, or every other sample for b None),
+    in the order |num| descending, rank_num descending, gene_i ascending, gene_j ascending.  Per pair and side, n_gt = samples with gene_i
+    above gene_j and not tied, n_eq = tied samples; with w = n_gt - n_lt per side, num = w_A S_B - w_B S_A and score = |num| / (2 S_A S_B)
+    (tie-free: |gt_A / S_A - gt_B / S_B|, Geman's Delta; in general num / (S_A S_B) = 2 delta + eq_A / S_A - eq_B / S_B, ties count half to
+    each side).  rank_num = |D_i - D_j| of Context.rank_shift breaks equal scores (tie-free: rank_score is Tan's gamma)."""
+    gene_i: np.ndarray       # int32, gene_i < gene_j
+    gene_j: np.ndarray       # int32
+    n_gt: np.ndarray         # int32, n x 2: side A, side B
+    n_eq: np.ndarray         # int32, n x 2
+    num: np.ndarray          # int64, N (signed)
+    rank_num: np.ndarray     # int64, Gamma
+    side_sizes: np.ndarray   # int64, 2: S_A, S_B
+    a: int
+    b: int | None
+    passes: int              # histogram passes of the selection
+
+    @property
+    def score(self) -> np.ndarray:
+        """|num| / (2 S_A S_B), float64 in [0, 1]."""
+        return np.abs(self.num).astype(np.float64) / (2.0 * float(self.side_sizes[0]) * float(self.side_sizes[1]))
+
+    @property
+    def rank_score(self) -> np.ndarray:
+        """rank_num / (2 S_A S_B), float64."""
+        return self.rank_num.astype(np.float64) / (2.0 * float(self.side_sizes[0]) * float(self.side_sizes[1]))
+
+    @property
+    def direction(self) -> np.ndarray:
+        """int8: +1 where gene_i lies above gene_j more often in A than in B, -1 the other way, 0 at num = 0."""
+        return np.sign(self.num).astype(np.int8)
+
+    def disjoint(self, k: int) -> np.ndarray:
+        """The indices of the greedy k-TSP selection: the list in order, a pair taken when neither of its genes is used yet, up to k pairs."""
+        used: set = set()
+        out = []
+        for e, (i, j) in enumerate(zip(self.gene_i.tolist(), self.gene_j.tolist())):
+            if len(out) >= int(k):
+                break
+            if i in used or j in used:
+                continue
+            used.update((i, j))
+            out.append(e)
+        return np.asarray(out, dtype=np.int64)
+
+    def csr(self):
+        """The (genes, rowptr, partner) triple that Context.pair_support takes: one row per pair, gene_i against gene_j, in list order."""
+        n = self.gene_i.size
+        return self.gene_i.astype(np.int32), np.arange(n + 1, dtype=np.int64), self.gene_j.astype(np.int32)
+
+    def votes(self, support) -> np.ndarray:
+        """Per sample, the sum over the pairs of direction * (outcome - 1), int32: positive means A-like.  `support` is the PairSupport of
+        csr() made with outcomes=True."""
+        if support.outcome is None:
+            raise DimensionMismatch(REO_EINVAL, "votes needs the outcome of every sample: call pair_support(csr(), outcomes=True)")
+        out = np.asarray(support.outcome)
+        if out.shape[0] != self.gene_i.size:
+            raise DimensionMismatch(REO_EINVAL, f"votes: the support lists {out.shape[0]} pairs, this object {self.gene_i.size}")
+        return (self.direction.astype(np.int32)[:, None] * (out.astype(np.int32) - 1)).sum(axis=0, dtype=np.int64).astype(np.int32)
 
 
 def bh_columns(p: np.ndarray) -> np.ndarray:
@@ -863,7 +926,8 @@ class Context:
     def set_valid_mask(self, valid) -> None:
         """reo_set_valid_mask: a G x S validity mask (nonzero / True = observed) beside the resident matrix, in the caller's column
         order; None clears it.  The cell under an invalid entry is ignored by build_pairs_masked but must still be a number (NaN stays
-        refused).  While a mask is set, sample_counts, sample_tests, sample_calls, pair_support and build_contrast are refused."""
+        refused).  While a mask is set, sample_counts, sample_tests, sample_calls, pair_support, rank_shift, top_pairs and build_contrast are
+        refused."""
         if valid is None:
             check(self._L.reo_set_valid_mask(self._h, None, 0, 0, 0))
             return
@@ -1083,6 +1147,45 @@ class Context:
         sizes = np.bincount(np.asarray(self._group_id, dtype=np.int64), minlength=ng)[:ng].astype(np.int64)
         return PairSupport(g, rp, pa, code, n_gt, n_eq, None if outcome is None else outcome[:, : self.S], sizes)
 
+    def _sides(self, a, b):
+        """(a, b as the library takes it, (S_A, S_B)) of a search: b None = every sample not in group a."""
+        a = int(a)
+        gid = self._group_id
+        s_a = int(np.count_nonzero(gid == a))
+        s_b = int(gid.size) - s_a if b is None else int(np.count_nonzero(gid == int(b)))
+        return a, (-1 if b is None else int(b)), np.array([s_a, s_b], dtype=np.int64)
+
+    def rank_shift(self, a: int = 0, b=None) -> np.ndarray:
+        """reo_rank_shift: D, int64 of length G.  D_i = W_i(A) S_B - W_i(B) S_A with W_i(side) the sum over the side's samples of (genes
+        that i lies above) - (genes that i lies below), untied; side A = group a, side B = group b or, for None, every other sample."""
+        a, b, _ = self._sides(a, b)
+        D = np.zeros(max(self.G, 1), dtype=np.int64)
+        check(self._L.reo_rank_shift(self._h, a, b, _ptr(D)))
+        return D[: self.G]
+
+    def top_pairs(self, n: int, a: int = 0, b=None, gene_mask=None) -> TopPairs:
+        """Which pairs (reo_top_pairs): the n best of all gene pairs i < j -- both genes inside gene_mask (bool over the genes) when one
+        is given -- for group a against group b (None: against every other sample), as a TopPairs in its order.  Fewer than n eligible
+        pairs: all of them.  Needs the matrix and the groups, no class table; refused under a validity mask, on a sharded context and on
+        n_gpus contexts, and above 65 535 genes or samples."""
+        n = int(n)
+        a, b, sizes = self._sides(a, b)
+        gm = None
+        if gene_mask is not None:
+            gm = np.asarray(gene_mask)
+            if gm.shape != (self.G,):
+                raise DimensionMismatch(REO_EINVAL, f"top_pairs: gene_mask has shape {tuple(gm.shape)}, the matrix has {self.G} genes")
+            gm = np.ascontiguousarray(gm if gm.dtype == np.uint8 else gm != 0, dtype=np.uint8)
+        m = min(max(n, 1), 1 << 20)   # (the library refuses n outside [1, 2^20] before it writes)
+        gi, gj = np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int32)
+        counts, key = np.zeros((m, 4), dtype=np.int32), np.zeros((m, 2), dtype=np.int64)
+        found, passes = ctypes.c_int64(0), ctypes.c_int32(0)
+        check(self._L.reo_top_pairs(self._h, a, b, _opt(gm), n, _ptr(gi), _ptr(gj), _ptr(counts), _ptr(key), ctypes.addressof(found),
+                                    ctypes.addressof(passes)))
+        k = int(found.value)
+        return TopPairs(gi[:k].copy(), gj[:k].copy(), counts[:k, 0::2].copy(), counts[:k, 1::2].copy(), key[:k, 0].copy(), key[:k, 1].copy(),
+                        sizes, a, None if b < 0 else b, int(passes.value))
+
     def mccullagh(self, cont) -> np.ndarray:
         cont = np.ascontiguousarray(cont, dtype=np.int32).reshape(-1, 9)
         out = np.zeros((cont.shape[0], 5), dtype=np.float64)
@@ -1185,8 +1288,8 @@ class Context:
                 "k2_full_launches": int(ms[9]), "k2_delta_ms": ms[10], "set_matrix_host_wall_ms": ms[11]}
 
     def info(self) -> dict:
-        w = np.zeros(36, dtype=np.int64)
-        check(self._L.reo_get_info(self._h, _ptr(w), 36))
+        w = np.zeros(38, dtype=np.int64)
+        check(self._L.reo_get_info(self._h, _ptr(w), 38))
         v = np.zeros(28, dtype=np.int64)   # fields 0-27 keep their places (tests/test_csc_device_cpu.py reads this line); 28 is appended
         v[:] = w[:28]
         return {"G": int(v[0]), "S": int(v[1]), "Gp": int(v[2]), "table_bytes": int(v[3]), "has_ties": int(v[4]),
@@ -1199,4 +1302,5 @@ class Context:
                 "k1_slot_order": int(v[25]), "k1_half_tiles_separated": int(v[26]), "csc_device": int(v[27]),
                 "k1_unslot_form": int(w[28]), "contrast_treat": int(w[29]), "k1_slot_sides": int(w[30]),
                 "masked_build": int(w[31]), "k1_slot_slice": int(w[32]), "planes_on_demand": int(w[33]),
-                "perm_batch": int(w[34]), "perm_kernel_us": int(w[35])}
+                "perm_batch": int(w[34]), "perm_kernel_us": int(w[35]),
+                "top_pairs_hist_us": int(w[36]), "top_pairs_emit_us": int(w[37])}

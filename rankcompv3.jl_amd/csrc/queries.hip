@@ -1,8 +1,9 @@
 // The query entry points of the C ABI (include/reo_hip.h): reo_pair_list, reo_sample_counts, reo_sample_tests, reo_sample_calls,
-// reo_pair_support.  Host code only; the kernels are in pairlist.hip, samplecounts.hip, sampletests.hip, samplecalls.hip and pairsupport.hip.
-// What the five share stands once, in front.
+// reo_pair_support, reo_rank_shift, reo_top_pairs.  Host code only; the kernels are in pairlist.hip, samplecounts.hip, sampletests.hip,
+// samplecalls.hip, pairsupport.hip and toppairs.hip.  What they share stands once, in front.
 #include <algorithm>
 #include <cstdlib>
+#include <utility>
 
 #include "pair_list.h"
 #include "reo_internal.h"
@@ -10,6 +11,7 @@
 #include "sample_tests.h"
 #include "sample_calls.h"
 #include "pair_support.h"
+#include "top_pairs.h"
 
 namespace reo {
 namespace {
@@ -72,6 +74,72 @@ int32_t copy_back(reo_ctx *c, T *host, size_t at, const T *dev, size_t n)
     if (host) REO_HIP_CHECK(hipMemcpyAsync(host + at, dev, n * sizeof(T), hipMemcpyDeviceToHost, c->stream));
     return REO_OK;
 }
+
+// How reo_rank_shift and reo_top_pairs begin: a context, its device, and -- on one GPU -- a matrix and groups of one size (the refusals of
+// ensure_transform: nothing runs).  The context checks proper are tp_check_context's.
+int32_t top_begin(reo_ctx *c, const char *what)
+{
+    int32_t rc = use(c);
+    if (rc) return rc;
+    if (!c->in_multi && (c->dtype == 0 || c->group_id.empty() || static_cast<int64_t>(c->group_id.size()) != c->S)) return ensure_transform(c);
+    return REO_OK;
+}
+
+TpState top_state(reo_ctx *c)
+{
+    TpState st;
+    st.multi = c->in_multi; st.world = c->world; st.has_mask = mask_in_force(c); st.G = c->G; st.S = c->S; st.ngroups = c->ngroups;
+    return st;
+}
+
+// Two timing events around a launch; the elapsed time is read behind a wait for the stream.  Declared in FRONT of the call's DrainOnExit:
+// the events are destroyed behind its wait.
+struct TimedPair {
+    hipEvent_t a = nullptr, b = nullptr;
+    TimedPair() = default;
+    TimedPair(const TimedPair &) = delete;
+    TimedPair &operator=(const TimedPair &) = delete;
+    ~TimedPair()
+    {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+    }
+    int32_t make()
+    {
+        REO_HIP_CHECK(hipEventCreate(&a));
+        REO_HIP_CHECK(hipEventCreate(&b));
+        return REO_OK;
+    }
+    int32_t start(reo_ctx *c) { REO_HIP_CHECK(hipEventRecord(a, c->stream)); return REO_OK; }
+    int32_t stop(reo_ctx *c) { REO_HIP_CHECK(hipEventRecord(b, c->stream)); return REO_OK; }
+    int32_t add_us(int64_t *sum)
+    {
+        float ms = 0.f;
+        REO_HIP_CHECK(hipEventElapsedTime(&ms, a, b));
+        *sum += static_cast<int64_t>(ms * 1000.0f + 0.5f);
+        return REO_OK;
+    }
+};
+
+// The two sides of a search: group a against group b, or against every other sample (b = -1); a and b have passed tp_check_context.
+struct TopSides {
+    std::vector<int32_t> gside;   // per group: 0 side A, 1 side B, 2 neither
+    int s_a = 0, s_b = 0;
+    int32_t make(reo_ctx *c, const char *what, int32_t a, int32_t b)
+    {
+        gside.assign(static_cast<size_t>(c->ngroups), 2);
+        for (int g = 0; g < c->ngroups; ++g) gside[static_cast<size_t>(g)] = g == a ? 0 : ((b < 0 || g == b) ? 1 : 2);
+        s_a = s_b = 0;
+        for (const int32_t g : c->group_id) {
+            if (g < 0 || g >= c->ngroups) continue;
+            if (gside[static_cast<size_t>(g)] == 0) ++s_a;
+            else if (gside[static_cast<size_t>(g)] == 1) ++s_b;
+        }
+        if (s_a > 0 && s_b > 0) return REO_OK;
+        set_error("%s: side A has %d samples and side B %d, both sides need at least one", what, s_a, s_b);
+        return REO_EINVAL;
+    }
+};
 
 }  // namespace
 }  // namespace reo
@@ -358,6 +426,129 @@ int32_t reo_pair_support(reo_ctx *c, const int32_t *genes, int64_t n_genes, cons
         if ((rc = wait_or_drop_table(c))) return rc;   // the next batch reuses the buffers and the item list
     }
     drain.dismiss();
+    return REO_OK;
+}
+
+// The rank shift of every gene (include/reo_hip.h): the checks, the sides, one launch of k_rank_shift, G values back.
+int32_t reo_rank_shift(reo_ctx *c, int32_t a, int32_t b, int64_t *D)
+{
+    int32_t rc = top_begin(c, "reo_rank_shift");
+    if (rc) return rc;
+    char msg[320];
+    if (tp_check_shift_args(top_state(c), a, b, D, msg, sizeof msg)) { set_error("%s", msg); return REO_EINVAL; }
+    TopSides sides;
+    DevBuf<int32_t> d_gside;
+    DevBuf<int64_t> d_D;
+    if ((rc = sides.make(c, "reo_rank_shift", a, b)) || (rc = ensure_transform(c)) || (rc = d_gside.ensure(sides.gside.size())) ||
+        (rc = d_D.ensure(static_cast<size_t>(c->Gp))))
+        return rc;
+    DrainOnExit drain(c);   // the sides in, D out (declared after the buffers: the wait comes before their release)
+    REO_HIP_CHECK(hipMemcpyAsync(d_gside.p, sides.gside.data(), sides.gside.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    if ((rc = launch_rank_shift(c, d_gside.p, sides.s_a, sides.s_b, d_D.p)) || (rc = copy_back(c, D, 0, d_D.p, static_cast<size_t>(c->G))) ||
+        (rc = wait_or_drop_table(c)))
+        return rc;
+    drain.dismiss();
+    return REO_OK;
+}
+
+// The best n_want of all pairs (include/reo_hip.h): every check on the host first (top_pairs.h), then D, the pass loop of tp_select with
+// k_top_pairs<HIST> as its histogram, one emit pass, and the host sort of the candidates by the full key.  Reads the bit planes of the
+// transform and nothing of the class table or the iteration; writes none of them.
+int32_t reo_top_pairs(reo_ctx *c, int32_t a, int32_t b, const uint8_t *gene_mask, int64_t n_want, int32_t *gene_i, int32_t *gene_j,
+                      int32_t *counts, int64_t *key, int64_t *n_found, int32_t *passes_run)
+{
+    int32_t rc = top_begin(c, "reo_top_pairs");
+    if (rc) return rc;
+    char msg[320];
+    if (tp_check_args(top_state(c), a, b, gene_mask, n_want, gene_i, gene_j, counts, key, n_found, msg, sizeof msg)) { set_error("%s", msg); return REO_EINVAL; }
+    TopSides sides;
+    if ((rc = sides.make(c, "reo_top_pairs", a, b)) || (rc = ensure_transform(c))) return rc;
+    const int G = static_cast<int>(c->G);
+    const int64_t capacity = tp_capacity(n_want, env_batch("REO_TOP_PAIRS_CAP"));
+    std::vector<uint32_t> bits;
+    if (gene_mask) {
+        bits.assign(static_cast<size_t>(c->Wp), 0u);
+        for (int g = 0; g < G; ++g)
+            if (gene_mask[g]) bits[static_cast<size_t>(g) >> 5] |= 1u << (g & 31);
+    }
+    DevBuf<int32_t> d_gside;
+    DevBuf<int64_t> d_D;
+    DevBuf<uint32_t> d_bits, d_cand_n;
+    DevBuf<unsigned long long> d_hist;
+    DevBuf<TpRec> d_cand;
+    if ((rc = d_gside.ensure(sides.gside.size())) || (rc = d_D.ensure(static_cast<size_t>(c->Gp))) || (gene_mask && (rc = d_bits.ensure(bits.size()))) ||
+        (rc = d_hist.ensure(kTpHistWords)) || (rc = d_cand.ensure(static_cast<size_t>(capacity))) || (rc = d_cand_n.ensure(1)))
+        return rc;
+    TimedPair ev;   // (reo_get_info 36, 37: what the passes cost on the device)
+    if ((rc = ev.make())) return rc;
+    std::vector<int64_t> D(static_cast<size_t>(G));
+    std::vector<unsigned long long> hist(kTpHistWords);
+    std::vector<TpRec> cand;
+    uint32_t n_cand = 0;
+    DrainOnExit drain(c);   // the sides and the mask in, D, histograms and candidates out (declared after the buffers: the wait comes before their release)
+    REO_HIP_CHECK(hipMemcpyAsync(d_gside.p, sides.gside.data(), sides.gside.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    if (gene_mask) REO_HIP_CHECK(hipMemcpyAsync(d_bits.p, bits.data(), bits.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    const uint32_t *maskbits = gene_mask ? d_bits.p : nullptr;
+    if ((rc = launch_rank_shift(c, d_gside.p, sides.s_a, sides.s_b, d_D.p)) || (rc = copy_back(c, D.data(), 0, d_D.p, D.size())) ||
+        (rc = wait_or_drop_table(c)))
+        return rc;
+    const auto mm = std::minmax_element(D.begin(), D.end());
+    const uint64_t n_max = 2 * static_cast<uint64_t>(sides.s_a) * static_cast<uint64_t>(sides.s_b), g_max = static_cast<uint64_t>(*mm.second - *mm.first);
+    if (n_max >> 31 || g_max >> kTpGammaBits) {
+        set_error("reo_top_pairs: the rank shifts span %llu and 2 S_A S_B is %llu: more than the key's 48 and 31 bits hold", (unsigned long long)g_max,
+                  (unsigned long long)n_max);
+        return REO_EHIP;
+    }
+    c->top_hist_us = 0; c->top_emit_us = 0;
+    int32_t hist_rc = REO_OK;
+    const auto run_hist = [&](const TpKey &prefix, int shift, uint64_t *out) -> int {
+        if (hipMemsetAsync(d_hist.p, 0, kTpHistWords * sizeof(unsigned long long), c->stream) != hipSuccess) { set_error("reo_top_pairs: the histogram could not be cleared"); hist_rc = REO_EHIP; return 1; }
+        if ((hist_rc = ev.start(c)) || (hist_rc = launch_top_hist(c, d_gside.p, sides.s_a, sides.s_b, d_D.p, maskbits, prefix, shift, d_hist.p)) ||
+            (hist_rc = ev.stop(c)) || (hist_rc = copy_back(c, hist.data(), 0, d_hist.p, hist.size())) || (hist_rc = wait_or_drop_table(c)) ||
+            (hist_rc = ev.add_us(&c->top_hist_us)))
+            return 1;
+        for (int w = 0; w < kTpHistWords; ++w) out[w] = hist[static_cast<size_t>(w)];
+        return 0;
+    };
+    TpSelect sel;
+    const int src = tp_select(run_hist, tp_bound_mask(n_max, g_max), static_cast<uint64_t>(n_want), static_cast<uint64_t>(capacity), &sel);
+    if (src > 0) return hist_rc;
+    if (src < 0 || sel.n_cand > static_cast<uint64_t>(capacity)) {
+        set_error("reo_top_pairs: pass %d counted other pairs above its prefix than the passes before it (%llu candidates for %lld records)", sel.passes,
+                  (unsigned long long)sel.n_cand, (long long)capacity);
+        return REO_EHIP;
+    }
+    if (sel.n_cand > 0) {
+        cand.resize(static_cast<size_t>(sel.n_cand));
+        REO_HIP_CHECK(hipMemsetAsync(d_cand_n.p, 0, sizeof(uint32_t), c->stream));
+        if ((rc = ev.start(c)) || (rc = launch_top_emit(c, d_gside.p, sides.s_a, sides.s_b, d_D.p, maskbits, sel.cut, sel.shift, d_cand.p, capacity, d_cand_n.p)) ||
+            (rc = ev.stop(c)) || (rc = copy_back(c, &n_cand, 0, d_cand_n.p, 1)) || (rc = copy_back(c, cand.data(), 0, d_cand.p, cand.size())) ||
+            (rc = wait_or_drop_table(c)) || (rc = ev.add_us(&c->top_emit_us)))
+            return rc;
+    }
+    drain.dismiss();
+    if (n_cand != sel.n_cand) {
+        set_error("reo_top_pairs: the emit pass found %u candidates, the histogram passes counted %llu; nothing was written", n_cand,
+                  (unsigned long long)sel.n_cand);
+        return REO_EHIP;
+    }
+    std::vector<std::pair<TpKey, uint32_t>> order(cand.size());
+    for (size_t e = 0; e < cand.size(); ++e) {
+        const TpRec &r = cand[e];
+        if (r.i < 0 || r.i >= r.j || r.j >= G) { set_error("reo_top_pairs: candidate %zu is the pair (%d, %d) with %d genes; nothing was written", e, r.i, r.j, G); return REO_EHIP; }
+        order[e] = {tp_rec_key(r, D.data(), G, sides.s_a, sides.s_b), static_cast<uint32_t>(e)};
+    }
+    std::sort(order.begin(), order.end(), [](const std::pair<TpKey, uint32_t> &x, const std::pair<TpKey, uint32_t> &y) { return tp_before(x.first, y.first); });
+    const size_t n_out = std::min(order.size(), static_cast<size_t>(n_want));
+    for (size_t e = 0; e < n_out; ++e) {
+        const TpRec &r = cand[order[e].second];
+        gene_i[e] = r.i; gene_j[e] = r.j;
+        counts[4 * e] = r.gt_a; counts[4 * e + 1] = r.eq_a; counts[4 * e + 2] = r.gt_b; counts[4 * e + 3] = r.eq_b;
+        key[2 * e] = tp_num(r.gt_a, r.eq_a, r.gt_b, r.eq_b, sides.s_a, sides.s_b);
+        key[2 * e + 1] = static_cast<int64_t>(tp_gamma(D[static_cast<size_t>(r.i)], D[static_cast<size_t>(r.j)]));
+    }
+    *n_found = static_cast<int64_t>(n_out);
+    if (passes_run) *passes_run = sel.passes;
     return REO_OK;
 }
 

@@ -340,6 +340,9 @@ struct reo_ctx {
     // label-permutation null (reo_perm_null; permpairs.hip, perm_null.h)
     int64_t perm_batch = 0;             // reo_get_info 34: tables per batch of the last reo_perm_null
     int64_t perm_kernel_us = 0;         // reo_get_info 35: microseconds its launches of k_pairs_permuted took in all (HIP events)
+    // top-scoring pairs (reo_top_pairs; toppairs.hip, top_pairs.h)
+    int64_t top_hist_us = 0;            // reo_get_info 36: microseconds the histogram passes of the last reo_top_pairs took in all (HIP events)
+    int64_t top_emit_us = 0;            // reo_get_info 37: microseconds of its emit pass
     reo::DevBuf<int32_t> raw;           // [G][8]
     reo::DevBuf<uint32_t> delta_list;   // [2][Gp] changed genes (gene << 1 | added) per pass parity
     reo::DevBuf<int32_t> cont;          // [G][9]
@@ -479,6 +482,19 @@ int32_t launch_call_emit(reo_ctx *c, int64_t n_genes, const uint32_t *d_words, c
 struct PsItem;
 int32_t launch_pair_support(reo_ctx *c, const PsItem *d_items, int64_t n_items, const int32_t *d_partner, const int32_t *d_slot2col,
                             int32_t *d_gt, int32_t *d_eq, uint8_t *d_outcome);
+
+// toppairs.hip: the kernels of reo_rank_shift / reo_top_pairs (the key, the pass loop and the host checks: top_pairs.h).  d_gside: [ngroups]
+// the side of every group (0: A, 1: B, 2: neither); d_D: [Gp] the rank shifts, which launch_rank_shift fills (0 for genes >= G);
+// d_maskbits: [Wp] the gene mask as bits, or null for every gene.  launch_top_hist adds the histogram of one pass (prefix, digit at bit
+// `shift`) into d_hist ([kTpHistWords], cleared by the caller); launch_top_emit appends every pair with key >> shift >= cut to d_cand
+// ([capacity] records) and counts them all in d_cand_n ([1], cleared by the caller)
+struct TpKey;
+struct TpRec;
+int32_t launch_rank_shift(reo_ctx *c, const int32_t *d_gside, int s_a, int s_b, int64_t *d_D);
+int32_t launch_top_hist(reo_ctx *c, const int32_t *d_gside, int s_a, int s_b, const int64_t *d_D, const uint32_t *d_maskbits, const TpKey &prefix,
+                        int shift, unsigned long long *d_hist);
+int32_t launch_top_emit(reo_ctx *c, const int32_t *d_gside, int s_a, int s_b, const int64_t *d_D, const uint32_t *d_maskbits, const TpKey &cut,
+                        int shift, TpRec *d_cand, int64_t capacity, uint32_t *d_cand_n);
 
 // maskedpairs.hip: the kernels of reo_set_valid_mask / reo_build_pairs_masked / reo_pair_counts_masked (shared arithmetic and host checks:
 // masked_pairs.h).  launch_valid_words: c->vmask and d_slot2col ([32 * sample blocks], -1 for padding) into c->vwords (sized by the

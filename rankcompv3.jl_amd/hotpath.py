@@ -15,7 +15,7 @@ from typing import NamedTuple
 import numpy as np
 
 from . import _ffi, synth
-from ._ffi import PairList, PairSupport, PermNull, SampleCalls, SampleCounts, SampleScores, SampleTests, class_mask, permuted_labels  # noqa: F401
+from ._ffi import PairList, PairSupport, PermNull, SampleCalls, SampleCounts, SampleScores, SampleTests, TopPairs, class_mask, permuted_labels  # noqa: F401
 
 HEADER = ["pval", "padj", "n11", "n12", "n13", "n21", "n22", "n23", "n31", "n32", "n33",
           "Δ1", "Δ2", "se", "z1", "up_down"]  # src/RankCompV3.jl:665
@@ -256,6 +256,41 @@ def write_perm_summary_tsv(path, perm_null) -> None:
             f.write(f"{p}\t{int(perm_null.n_up[p])}\t{int(perm_null.n_down[p])}\t{float(perm_null.se_null[p])!r}\n")
 
 
+def top_pairs_plan(top_pairs, *, masked=False, shard=(0, 1)) -> None:
+    """The refusals of `top_pairs`, raised before any context is opened: a count outside [1, 2^20], and the routes that have no search --
+    a validity mask (missing="pairwise" / `valid`) and shard[1] > 1."""
+    if top_pairs is None:
+        return
+
+    def bad(why):
+        return _ffi.DimensionMismatch(_ffi.REO_EINVAL, why)
+    if isinstance(top_pairs, bool) or not isinstance(top_pairs, (int, np.integer)) or not 1 <= int(top_pairs) <= 1 << 20:
+        raise bad(f"top_pairs = {top_pairs!r}: None (no search) or a number of pairs between 1 and 2^20")
+    if masked:
+        raise bad("top_pairs: the search compares on the whole matrix and would count the fillers under the validity mask; it is not "
+                  "available together with missing=\"pairwise\" or `valid`")
+    if shard[1] > 1:
+        raise bad(f"top_pairs: the search has no sharded form (shard = {tuple(shard)!r})")
+
+
+def deg_top_pairs(ctx, k, treat, top_pairs) -> dict:
+    """{"top_pairs"} of one comparison on `ctx`: the TopPairs of group k against the contrast's treatment group, or against every other
+    sample for the reference's comparisons (treat None)."""
+    return {"top_pairs": ctx.top_pairs(int(top_pairs), a=k, b=treat)}
+
+
+def write_top_pairs_tsv(path, gene_names, top) -> None:
+    """gene_i, gene_j, direction, score, rank_score, gt_A, eq_A, gt_B, eq_B: one line per pair in the list's own order, names from
+    gene_names, floats by repr; a header line, "\n" line ends, like the result writers of reoa."""
+    score, rank_score, direction = top.score, top.rank_score, top.direction
+    with open(path, "w") as f:
+        f.write("gene_i\tgene_j\tdirection\tscore\trank_score\tgt_A\teq_A\tgt_B\teq_B\n")
+        for e in range(top.gene_i.size):
+            f.write("\t".join([str(gene_names[int(top.gene_i[e])]), str(gene_names[int(top.gene_j[e])]), str(int(direction[e])),
+                               repr(float(score[e])), repr(float(rank_score[e])), str(int(top.n_gt[e, 0])), str(int(top.n_eq[e, 0])),
+                               str(int(top.n_gt[e, 1])), str(int(top.n_eq[e, 1]))]) + "\n")
+
+
 def missing_plan(data, missing, valid, *, shard=(0, 1), contrasts=None, sample_scores=False, sample_tests=False, sample_calls=False,
                  pair_support=False):
     """The pairwise route of run_identify_degs, decided before any context is opened.  Pure: no library, no GPU.  Returns (data, mask):
@@ -304,7 +339,7 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
                       seed: int = 0, device: int = -1, shard=(0, 1), allreduce=None, allgather=None, profile: bool = False,
                       pairs=None, sample_scores: bool = False, pair_support: bool = False, contrasts=None,
                       sample_tests: bool = False, sample_calls: bool = False, missing=None, valid=None, min_complete=None,
-                      permutations=None, perm_seed: int = 0, perm_strata=None) -> DegRun:
+                      permutations=None, perm_seed: int = 0, perm_strata=None, top_pairs=None) -> DegRun:
     """identify_degs with the extras (trace, timings) kept.  `data` is a host matrix (numpy, anything np.asarray takes) or a torch
     tensor on a ROCm device, which is used in place (_ffi.device_matrix).  A column-major host matrix is read in place; a row-major one
     (numpy's default C order, column slices of a wider C-ordered array) is copied column-major on the host first, or, with REO_ROWMAJOR=1
@@ -353,11 +388,16 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
     PermNull of B label shuffles of the comparison's two sides (Context.permutation_null; rows from permuted_labels with seed perm_seed + k,
     shuffled within perm_strata -- one label per sample -- when given), the reference set held at that of the run's last pass; taken after
     every other read-out of the comparison.  Refused with `contrasts`, with a mask and with shard[1] > 1 (perm_plan).  None (the default):
-    no further call, no new key."""
+    no further call, no new key.
+    `top_pairs` (not in the reference): an int K adds "top_pairs" to every comparison dict, the TopPairs of the K best of ALL gene pairs
+    (Context.top_pairs: the top-scoring-pair search) for the comparison's group k against the contrast's treatment group, or against every
+    other sample for the reference's comparisons; taken after the other read-outs and before the permutation null.  Refused with a mask and
+    with shard[1] > 1 (top_pairs_plan).  None (the default): no further call, no new key."""
     need_pairs_for_support(pairs, pair_support)
     data, mask = missing_plan(data, missing, valid, shard=shard, contrasts=contrasts, sample_scores=sample_scores, sample_tests=sample_tests,
                               sample_calls=sample_calls, pair_support=pair_support)
     perm_plan(permutations, contrasts=contrasts, masked=mask is not None, shard=shard)
+    top_pairs_plan(top_pairs, masked=mask is not None, shard=shard)
     if mask is not None:
         _ffi.resolve_min_complete(min_complete, (1, 1), pval_reo)   # (its refusals, before a context is opened)
     # a torch tensor on a ROCm device: a strided one is used where it is, a sparse one is made dense there (its device is the context's)
@@ -416,6 +456,8 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
                 comps[-1]["sample_tests"] = ctx.sample_tests()   # all genes, against the reference set of this comparison's tallies
             if sample_calls:
                 comps[-1]["sample_calls"] = ctx.sample_calls(pval_deg, padj_deg)   # all genes, the run's thresholds, the same reference set
+            if top_pairs is not None:
+                comps[-1].update(deg_top_pairs(ctx, k, treat, top_pairs))
             if permutations is not None:   # last: it uses the iteration's buffers (ref_mask is refused behind it)
                 comps[-1].update(deg_perm_null(ctx, gid, k, permutations, perm_seed, perm_strata, pval_deg, padj_deg))
         timings = ctx.timings() if profile else {}
@@ -458,7 +500,7 @@ def identify_degs_cells(cells, cell_group, gene_names, n_pseudo, pval_reo, pval_
                         min_profiles: int = 0, min_features: int = 0, ref_gene_max: int = 3000, seed: int = 0, device: int = 0,
                         profile: bool = False, pairs=None, sample_scores: bool = False, pair_support: bool = False,
                         contrasts=None, sample_tests: bool = False, sample_calls: bool = False,
-                        permutations=None, perm_seed: int = 0, perm_strata=None) -> CellsDegRun:
+                        permutations=None, perm_seed: int = 0, perm_strata=None, top_pairs=None) -> CellsDegRun:
     """Cells to DEGs without a host trip for the profiles: `cells` is a genes x cells matrix (scipy.sparse, anything np.asarray takes, or
     a torch tensor on a ROCm device -- sparse or strided -- which is read where it is: reo_set_matrix_pseudobulk_*_dev_*),
     cell_group one label per cell.  cells_partition -> the pseudo-bulk sums written into the context's matrix (set_matrix_pseudobulk) ->
@@ -469,9 +511,11 @@ def identify_degs_cells(cells, cell_group, gene_names, n_pseudo, pval_reo, pval_
     `pairs`, `sample_scores`, `pair_support`, `sample_tests`, `sample_calls`: as in run_identify_degs; gene indices are those of the KEPT genes (run.gene_names), columns
     the kept profiles.  `contrasts`: as in run_identify_degs, over the group levels of the cells (checked against the levels of cell_group
     before any context is opened, and again against those of the kept profiles).  `permutations`, `perm_seed`, `perm_strata`: as in
-    run_identify_degs; perm_strata has one label per pseudo-bulk PROFILE of cells_partition (the kept ones are used)."""
+    run_identify_degs; perm_strata has one label per pseudo-bulk PROFILE of cells_partition (the kept ones are used).  `top_pairs`: as in
+    run_identify_degs."""
     need_pairs_for_support(pairs, pair_support)
     perm_plan(permutations, contrasts=contrasts)
+    top_pairs_plan(top_pairs)
     on_device = _ffi.is_device_sparse(cells) or _ffi.is_device_tensor(cells)
     if on_device:   # a torch tensor on a ROCm device, sparse or strided: summed where it is, on its own device
         device = cells.device.index if cells.device.index is not None else -1
@@ -519,6 +563,8 @@ def identify_degs_cells(cells, cell_group, gene_names, n_pseudo, pval_reo, pval_
                 comps[-1]["sample_tests"] = ctx.sample_tests()   # all genes, against the reference set of this comparison's tallies
             if sample_calls:
                 comps[-1]["sample_calls"] = ctx.sample_calls(pval_deg, padj_deg)   # all genes, the run's thresholds, the same reference set
+            if top_pairs is not None:
+                comps[-1].update(deg_top_pairs(ctx, k, treat, top_pairs))
             if permutations is not None:   # last: it uses the iteration's buffers (ref_mask is refused behind it)
                 strata = None if perm_strata is None else np.asarray(perm_strata)[np.asarray(profile_kept, dtype=bool)]
                 comps[-1].update(deg_perm_null(ctx, gid, k, permutations, perm_seed, strata, pval_deg, padj_deg))
