@@ -425,6 +425,42 @@ int32_t reo_top_pairs(reo_ctx *ctx, int32_t a, int32_t b, const uint8_t *gene_ma
                       int64_t *key /* [n_want][2]: N (signed), Gamma */,
                       int64_t *n_found, int32_t *passes_run /* may be NULL */);
 
+/* Label-permutation null of the best score: is the winning score of reo_top_pairs larger than the best score that meaningless labels
+ * produce?  Geman's top-scoring-pair paper and the k-TSP applications answer that with a permutation test of the maximum; the reference has
+ * no such output.
+ * Sides A and B are those of reo_top_pairs(a, b), with the context's sizes S_A and S_B.  A label row has S bytes in the caller's column
+ * order: 1 = side A, 0 = side B, 2 = takes no part.  A row holds exactly S_A ones and S_B zeros, and the columns that carry a 2 are, in
+ * every row, exactly the samples of the groups on neither side (with b = -1 there are none); the caller supplies the rows (shuffled freely,
+ * or within batches or patients: the library has no shuffling rule).  So the sizes, and with them the denominator 2 S_A S_B, are the same
+ * under every permutation, and which sample slots take part is the same for all of them.
+ * Per permutation p, for every pair i < j with both genes inside gene_mask (NULL: all genes): gt and eq per side exactly as reo_top_pairs
+ * counts them (no tie coin), side B being "the samples that take part, minus A", and N_p(i, j) = w(A) S_B - w(B) S_A as above.  Then
+ *     max_n[p] = max |N_p|,   (arg_i[p], arg_j[p]) = the pair that attains it, the smallest (i, j) among equals,
+ *     n_reach[p * n_cuts + t] = the number of eligible pairs with |N_p| >= cuts[t];
+ * with no eligible pair max_n[p] = -1, arg_i[p] = arg_j[p] = -1 and n_reach = 0.  The rank shift Gamma is NOT a tie-break here: it depends
+ * on the labels and would need a D per permutation.  A row that repeats the observed labels gives max_n = |key[0]| of reo_top_pairs(n_want
+ * = 1).  All results are exact integers, independent of the launch geometry, of the batch size and of the arrival order of atomics.
+ * Needs the matrix, the groups and the transform (run here if need be); no class table, no thresholds, no reference set.  Reads and writes
+ * none of the iteration's buffers.  Host arrays only, allocated by the caller.
+ * One walk over the bit planes serves 16 permutations (csrc/toppairsnull.hip, csrc/top_pairs_null.h): the lt / le words of a pair and a
+ * block of 32 sample slots do not depend on the labels, a permutation costs one and + popcount per counter, only the tiles with i < j are
+ * walked, and per permutation one 63-bit key (|N|, 2^32 - 1 - (i G + j)) and n_cuts counters leave the device; no class table and no
+ * candidates are written.  One launch handles at most 64 permutations (REO_TOP_NULL_BATCH=n in the environment, read per call, asks for at
+ * most n); reo_get_info 38 = the permutations per launch of the last call, 39 = the microseconds of its kernel launches in all (HIP
+ * events).  No other info entry is touched.
+ * REO_EINVAL, each with its own message, all checked on the host before anything is uploaded, and a refused call writes nothing:
+ * everything reo_top_pairs refuses of the context and of a, b (a reo_create_multi context; a sharded context; a validity mask set; G or S
+ * above 65535; a or b outside the groups; b == a); n_perm outside [1, 2^20]; n_cuts outside [0, 8]; a negative cut; a row byte above 2; a
+ * row whose 2-columns differ from the samples of neither side (the message names row and column); a row whose count of ones and zeros
+ * differs from S_A and S_B (the message names the row, the counts and the sizes); a gene_mask byte other than 0 or 1; a NULL output, except
+ * cuts and n_reach with n_cuts == 0. */
+int32_t reo_top_pairs_null(reo_ctx *ctx, int32_t a, int32_t b /* -1: every other sample */,
+                           const uint8_t *sides /* [n_perm][S], caller's column order */, int64_t n_perm,
+                           const uint8_t *gene_mask /* G bytes 0/1, or NULL */,
+                           const int64_t *cuts /* n_cuts values of |N|, may be NULL when n_cuts == 0 */, int32_t n_cuts,
+                           int64_t *max_n /* n_perm */, int32_t *arg_i, int32_t *arg_j /* n_perm each */,
+                           int64_t *n_reach /* [n_perm][n_cuts]; may be NULL when n_cuts == 0 */);
+
 /* Missing values: pair classes from the samples where BOTH genes were observed.  The reference drops every gene with a missing cell
  * (dropmissing!, src/RankCompV3.jl:601) and the library refuses a NaN; with a validity mask V beside the resident matrix a pair (i, j) is
  * compared in the samples where both values exist, and its stability is judged against the threshold of that many samples.
@@ -734,6 +770,8 @@ int32_t reo_get_timings(reo_ctx *ctx, double *ms, int32_t n);
  * the table is the same bit for bit), 33 how many times the gene-order bit planes of the current transform were made on demand (a
  * transform of tie-free data that a slot build can follow leaves them unmade; the first pair query, masked build or identity-order build
  * makes them once: 0 or 1), 34 the tables per batch of the last reo_perm_null, 35 the microseconds that its launches of the permuted pair
+ * kernel took in all (HIP events around each launch), 36 and 37 the microseconds of the histogram passes and of the emit pass of the
+ * last reo_top_pairs, 38 the permutations per launch of the last reo_top_pairs_null, 39 the microseconds that its launches of the null
  * kernel took in all (HIP events around each launch). */
 int32_t reo_get_info(reo_ctx *ctx, int64_t *info, int32_t n);
 

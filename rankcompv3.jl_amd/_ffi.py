@@ -35,7 +35,7 @@ SYMBOLS = [
     "reo_set_matrix_pseudobulk_dense_f64", "reo_set_matrix_pseudobulk_dense_i64", "reo_set_matrix_pseudobulk_csc_f64", "reo_set_matrix_pseudobulk_csc_i64",
     "reo_filter_matrix", "reo_get_matrix", "reo_get_ref_mask", "reo_pair_list", "reo_sample_counts", "reo_pair_support",
     "reo_sample_tests", "reo_sample_calls", "reo_set_valid_mask", "reo_build_pairs_masked", "reo_pair_counts_masked",
-    "reo_perm_null", "reo_perm_codes", "reo_rank_shift", "reo_top_pairs",
+    "reo_perm_null", "reo_perm_codes", "reo_rank_shift", "reo_top_pairs", "reo_top_pairs_null",
 ] +[f"reo_set_matrix_{form}_{t}" for form in ("csc_dev", "pseudobulk_csc_dev", "pseudobulk_dense_dev") for t in ("f64", "i64", "f32", "i32")]
 
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p)
@@ -152,6 +152,7 @@ def lib() -> ctypes.CDLL:
         "reo_perm_codes": (i32, [vp, i32, vp, i64, i64, i64, i64, vp]),
         "reo_rank_shift": (i32, [vp, i32, i32, vp]),
         "reo_top_pairs": (i32, [vp, i32, i32, vp, i64, vp, vp, vp, vp, vp, vp]),
+        "reo_top_pairs_null": (i32, [vp, i32, i32, vp, i64, vp, vp, i32, vp, vp, vp, vp]),
     }
     for t in ("f64", "i64", "f32", "i32"):   # SPARSE ON THE DEVICE
         sig["reo_set_matrix_csc_dev_" + t] = (i32, [vp, i64, i64, i64, vp, vp, i32, vp])
@@ -511,6 +512,38 @@ class TopPairs(NamedTuple):
         return (self.direction.astype(np.int32)[:, None] * (out.astype(np.int32) - 1)).sum(axis=0, dtype=np.int64).astype(np.int32)
 
 
+class TopPairsNull(NamedTuple):
+    """reo_top_pairs_null: per label permutation (row of `sides`) the best score that the labelling reaches over all gene pairs -- the null of
+    the maximum of Context.top_pairs for side A (group a) against side B (group b, or every other sample for b None).  max_num[p] = max |N_p|
+    over the eligible pairs, (arg_i[p], arg_j[p]) the pair that attains it (the smallest (i, j) among equals; the rank shift is no
+    tie-break here), n_reach[p, t] = the pairs with |N_p| >= cuts[t]; -1, -1, -1 and 0 when no pair is eligible."""
+    max_num: np.ndarray      # int64, B
+    arg_i: np.ndarray        # int32, B
+    arg_j: np.ndarray        # int32, B
+    n_reach: np.ndarray      # int64, B x len(cuts)
+    cuts: np.ndarray         # int64
+    side_sizes: np.ndarray   # int64, 2: S_A, S_B
+    a: int
+    b: int | None
+
+    @property
+    def max_score(self) -> np.ndarray:
+        """max_num / (2 S_A S_B), float64: the best score of every permutation."""
+        return self.max_num.astype(np.float64) / (2.0 * float(self.side_sizes[0]) * float(self.side_sizes[1]))
+
+    def p_max(self, tp) -> np.ndarray:
+        """(1 + #{p : max_num[p] >= |tp.num[e]|}) / (1 + B) per pair e of a TopPairs: the single-step maxT (Westfall-Young) adjusted
+        p-value, the observed labelling counted among the permutations.  Non-decreasing down the list, because |num| is non-increasing."""
+        obs = np.abs(np.asarray(tp.num, dtype=np.int64))
+        ge = (self.max_num[None, :] >= obs[:, None]).sum(axis=1)
+        return (1.0 + ge) / (1.0 + self.max_num.size)
+
+    def expected_reach(self) -> np.ndarray:
+        """The mean of n_reach over the permutations, one value per cut: with cuts = |tp.num[n - 1]| the expected number of chance pairs at
+        least as good as the n-th listed one."""
+        return self.n_reach.astype(np.float64).mean(axis=0) if self.n_reach.shape[0] else np.zeros(self.cuts.size)
+
+
 def bh_columns(p: np.ndarray) -> np.ndarray:
     """Benjamini-Hochberg down every column of p (rows x columns, float64): p * n / rank in ascending order (a stable sort), the reverse
     cumulative minimum, clamped to 1 -- the rule of the reference's BenjaminiHochberg call (src/RankCompV3.jl:413), restated in numpy.
@@ -638,6 +671,55 @@ def permuted_labels(group_ids, k: int, n_perm: int, seed: int = 0, strata=None, 
         if st.size != S:
             raise ValueError(f"strata has {st.size} labels for {S} samples")
         blocks = [np.flatnonzero(st == v) for v in sorted(set(st.tolist()), key=repr)]
+    rng = np.random.Generator(np.random.PCG64(int(seed)))
+    rows = np.empty((n_perm, S), dtype=np.uint8)
+    seen = {obs.tobytes()}
+    start = 0
+    if include_observed:
+        rows[0] = obs
+        start = 1
+    misses = 0
+    p = start
+    while p < n_perm:
+        row = obs.copy()
+        for idx in blocks:
+            row[idx] = rng.permutation(obs[idx])
+        key = row.tobytes()
+        if key in seen:
+            misses += 1
+            if misses > 1000 + 100 * n_perm:
+                raise ValueError(f"the labels have fewer than {n_perm} distinct arrangements besides the observed one")
+            continue
+        seen.add(key)
+        rows[p] = row
+        p += 1
+    return rows
+
+
+def permuted_sides(group_ids, a: int, b=None, n_perm: int = 1000, seed: int = 0, strata=None, include_observed: bool = False) -> np.ndarray:
+    """n_perm label rows for Context.top_pairs_null: uint8 n_perm x S, 1 = side A (group a), 0 = side B (group b, or every other sample for
+    b None), 2 = the samples of groups on neither side, which keep their 2 in every row.  The observed row is shuffled with numpy's
+    Generator(PCG64(seed)) among the samples of A and B only -- freely, or, with `strata` (one label per sample: batch, patient), within
+    each stratum, which keeps every stratum's count of ones.  The counts of ones and zeros are kept in every row, the same seed gives the
+    same rows, and a row is never the observed labelling nor a repeat of an earlier row (drawn again; ValueError when the labels do not
+    have that many distinct arrangements).  include_observed=True makes row 0 the observed labelling itself (the identity)."""
+    gid = np.asarray(group_ids).reshape(-1)
+    if b is not None and b == a:
+        raise ValueError(f"b == a == {a!r}: the two sides must differ")
+    obs = np.where(gid == a, 1, 0 if b is None else np.where(gid == b, 0, 2)).astype(np.uint8)
+    S = obs.size
+    if n_perm < 1:
+        raise ValueError("n_perm must be at least 1")
+    if (obs == 1).sum() == 0 or (obs == 0).sum() == 0:
+        raise ValueError(f"side A holds {int((obs == 1).sum())} and side B {int((obs == 0).sum())} of {S} samples: nothing to permute")
+    part = obs != 2
+    if strata is None:
+        blocks = [np.flatnonzero(part)]
+    else:
+        st = np.asarray(strata).reshape(-1)
+        if st.size != S:
+            raise ValueError(f"strata has {st.size} labels for {S} samples")
+        blocks = [np.flatnonzero((st == v) & part) for v in sorted(set(st.tolist()), key=repr)]
     rng = np.random.Generator(np.random.PCG64(int(seed)))
     rows = np.empty((n_perm, S), dtype=np.uint8)
     seen = {obs.tobytes()}
@@ -1186,6 +1268,36 @@ class Context:
         return TopPairs(gi[:k].copy(), gj[:k].copy(), counts[:k, 0::2].copy(), counts[:k, 1::2].copy(), key[:k, 0].copy(), key[:k, 1].copy(),
                         sizes, a, None if b < 0 else b, int(passes.value))
 
+    def top_pairs_null(self, sides, a: int = 0, b=None, gene_mask=None, cuts=None) -> TopPairsNull:
+        """The null of the best score (reo_top_pairs_null): for every label row of `sides` (B x S, 1 = side A, 0 = side B, 2 = the samples of
+        groups on neither side; permuted_sides makes them) the largest |N| over all gene pairs i < j -- both genes inside gene_mask when
+        one is given --, the pair that attains it, and per value of `cuts` (up to 8 values of |N|) how many pairs reach it, as a
+        TopPairsNull.  Sides and refusals as in top_pairs; one walk over the bit planes serves 16 rows."""
+        a, b, sizes = self._sides(a, b)
+        rows = np.asarray(sides)
+        if rows.ndim == 1:
+            rows = rows.reshape(1, -1)
+        if rows.ndim != 2 or rows.shape[1] != self.S:
+            raise DimensionMismatch(REO_EINVAL, f"top_pairs_null: sides has shape {tuple(np.shape(sides))}, label rows are B x S = B x {self.S}")
+        if rows.size and (rows.min() < 0 or rows.max() > 255):
+            raise DimensionMismatch(REO_EINVAL, "top_pairs_null: label rows hold 0 (side B), 1 (side A) and 2 (takes no part)")
+        rows = np.ascontiguousarray(rows, dtype=np.uint8)
+        gm = None
+        if gene_mask is not None:
+            gm = np.asarray(gene_mask)
+            if gm.shape != (self.G,):
+                raise DimensionMismatch(REO_EINVAL, f"top_pairs_null: gene_mask has shape {tuple(gm.shape)}, the matrix has {self.G} genes")
+            gm = np.ascontiguousarray(gm if gm.dtype == np.uint8 else gm != 0, dtype=np.uint8)
+        ct = np.zeros(0, dtype=np.int64) if cuts is None else np.ascontiguousarray(np.asarray(cuts, dtype=np.int64).reshape(-1))
+        B = rows.shape[0]
+        m = min(max(B, 1), 1 << 20)   # (the library refuses n_perm outside [1, 2^20] before it writes)
+        nc = min(ct.size, 8)
+        max_n, gi, gj = np.zeros(m, dtype=np.int64), np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int32)
+        reach = np.zeros((m, nc), dtype=np.int64)
+        check(self._L.reo_top_pairs_null(self._h, a, b, _ptr(rows) if rows.size else None, B, _opt(gm), _ptr(ct) if ct.size else None, ct.size,
+                                         _ptr(max_n), _ptr(gi), _ptr(gj), _ptr(reach) if reach.size else None))
+        return TopPairsNull(max_n[:B], gi[:B], gj[:B], reach[:B], ct, sizes, a, None if b < 0 else b)
+
     def mccullagh(self, cont) -> np.ndarray:
         cont = np.ascontiguousarray(cont, dtype=np.int32).reshape(-1, 9)
         out = np.zeros((cont.shape[0], 5), dtype=np.float64)
@@ -1288,8 +1400,8 @@ class Context:
                 "k2_full_launches": int(ms[9]), "k2_delta_ms": ms[10], "set_matrix_host_wall_ms": ms[11]}
 
     def info(self) -> dict:
-        w = np.zeros(38, dtype=np.int64)
-        check(self._L.reo_get_info(self._h, _ptr(w), 38))
+        w = np.zeros(40, dtype=np.int64)
+        check(self._L.reo_get_info(self._h, _ptr(w), 40))
         v = np.zeros(28, dtype=np.int64)   # fields 0-27 keep their places (tests/test_csc_device_cpu.py reads this line); 28 is appended
         v[:] = w[:28]
         return {"G": int(v[0]), "S": int(v[1]), "Gp": int(v[2]), "table_bytes": int(v[3]), "has_ties": int(v[4]),
@@ -1303,4 +1415,5 @@ class Context:
                 "k1_unslot_form": int(w[28]), "contrast_treat": int(w[29]), "k1_slot_sides": int(w[30]),
                 "masked_build": int(w[31]), "k1_slot_slice": int(w[32]), "planes_on_demand": int(w[33]),
                 "perm_batch": int(w[34]), "perm_kernel_us": int(w[35]),
-                "top_pairs_hist_us": int(w[36]), "top_pairs_emit_us": int(w[37])}
+                "top_pairs_hist_us": int(w[36]), "top_pairs_emit_us": int(w[37]),
+                "top_pairs_null_batch": int(w[38]), "top_pairs_null_us": int(w[39])}

@@ -1,6 +1,6 @@
 // The query entry points of the C ABI (include/reo_hip.h): reo_pair_list, reo_sample_counts, reo_sample_tests, reo_sample_calls,
-// reo_pair_support, reo_rank_shift, reo_top_pairs.  Host code only; the kernels are in pairlist.hip, samplecounts.hip, sampletests.hip,
-// samplecalls.hip, pairsupport.hip and toppairs.hip.  What they share stands once, in front.
+// reo_pair_support, reo_rank_shift, reo_top_pairs, reo_top_pairs_null.  Host code only; the kernels are in pairlist.hip, samplecounts.hip,
+// sampletests.hip, samplecalls.hip, pairsupport.hip, toppairs.hip and toppairsnull.hip.  What they share stands once, in front.
 #include <algorithm>
 #include <cstdlib>
 #include <utility>
@@ -12,6 +12,7 @@
 #include "sample_calls.h"
 #include "pair_support.h"
 #include "top_pairs.h"
+#include "top_pairs_null.h"
 
 namespace reo {
 namespace {
@@ -549,6 +550,79 @@ int32_t reo_top_pairs(reo_ctx *c, int32_t a, int32_t b, const uint8_t *gene_mask
     }
     *n_found = static_cast<int64_t>(n_out);
     if (passes_run) *passes_run = sel.passes;
+    return REO_OK;
+}
+
+// The null of the best score (include/reo_hip.h): every check on the host first (top_pairs_null.h), then per batch of at most 64 label
+// rows the A-words, one launch of k_top_pairs_null and the batch's keys and counters back.  Reads the bit planes of the transform and
+// nothing of the class table or the iteration; writes none of them.  The caller's arrays are written once every batch has run.
+int32_t reo_top_pairs_null(reo_ctx *c, int32_t a, int32_t b, const uint8_t *sides, int64_t n_perm, const uint8_t *gene_mask, const int64_t *cuts,
+                           int32_t n_cuts, int64_t *max_n, int32_t *arg_i, int32_t *arg_j, int64_t *n_reach)
+{
+    const char *what = "reo_top_pairs_null";
+    int32_t rc = top_begin(c, what);
+    if (rc) return rc;
+    char msg[320];
+    int64_t s_a = 0, s_b = 0;
+    if (tn_check_args(top_state(c), c->group_id.data(), a, b, sides, n_perm, gene_mask, cuts, n_cuts, max_n, arg_i, arg_j, n_reach, &s_a, &s_b, msg,
+                      sizeof msg)) {
+        set_error("%s", msg);
+        return REO_EINVAL;
+    }
+    std::vector<int32_t> map;
+    if ((rc = ensure_transform(c)) || (rc = query_slot_map(c, what, map))) return rc;
+    const int G = static_cast<int>(c->G);
+    const size_t S = static_cast<size_t>(c->S);
+    const int nblk = c->goff32.back() / 32;
+    const int64_t P = tn_batch(n_perm, env_batch("REO_TOP_NULL_BATCH"));
+    std::vector<uint32_t> bits;
+    if (gene_mask) {
+        bits.assign(static_cast<size_t>(c->Wp), 0u);
+        for (int g = 0; g < G; ++g)
+            if (gene_mask[g]) bits[static_cast<size_t>(g) >> 5] |= 1u << (g & 31);
+    }
+    DevBuf<uint8_t> d_side;
+    DevBuf<uint32_t> d_aw, d_live, d_bits;
+    DevBuf<unsigned long long> d_keys, d_reach;
+    if ((rc = d_side.ensure(static_cast<size_t>(P) * S)) || (rc = d_aw.ensure(pn_word_count(P, nblk))) || (rc = d_live.ensure(static_cast<size_t>(nblk))) ||
+        (gene_mask && (rc = d_bits.ensure(bits.size()))) || (rc = d_keys.ensure(kTnBatchCap)) || (rc = d_reach.ensure(kTnBatchCap * kTnMaxCuts)) ||
+        (rc = c->sc_slot2col.ensure(map.size())))
+        return rc;
+    TimedPair ev;   // (reo_get_info 39: what the launches cost on the device)
+    if ((rc = ev.make())) return rc;
+    std::vector<unsigned long long> keys(static_cast<size_t>(n_perm)), reach(static_cast<size_t>(n_perm) * kTnMaxCuts);
+    DrainOnExit drain(c);   // the rows and the mask in, keys and counters out (declared after the buffers: the wait comes before their release)
+    if ((rc = upload_slot2col(c, map))) return rc;
+    if (gene_mask) REO_HIP_CHECK(hipMemcpyAsync(d_bits.p, bits.data(), bits.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    c->top_null_batch = P; c->top_null_us = 0;
+    for (int64_t p0 = 0; p0 < n_perm; p0 += P) {
+        const int np = static_cast<int>(std::min<int64_t>(P, n_perm - p0));
+        REO_HIP_CHECK(hipMemcpyAsync(d_side.p, sides + static_cast<size_t>(p0) * S, static_cast<size_t>(np) * S, hipMemcpyHostToDevice, c->stream));
+        REO_HIP_CHECK(hipMemsetAsync(d_keys.p, 0, kTnBatchCap * sizeof(unsigned long long), c->stream));
+        REO_HIP_CHECK(hipMemsetAsync(d_reach.p, 0, kTnBatchCap * kTnMaxCuts * sizeof(unsigned long long), c->stream));
+        if ((rc = launch_top_null_words(c, d_side.p, np, c->sc_slot2col.p, d_aw.p, d_live.p)) || (rc = ev.start(c)) ||
+            (rc = launch_top_pairs_null(c, d_aw.p, d_live.p, np, static_cast<int>(s_a), static_cast<int>(s_b), gene_mask ? d_bits.p : nullptr, cuts, n_cuts,
+                                        d_keys.p, d_reach.p)) ||
+            (rc = ev.stop(c)) || (rc = copy_back(c, keys.data(), static_cast<size_t>(p0), d_keys.p, static_cast<size_t>(np))) ||
+            (rc = copy_back(c, reach.data(), static_cast<size_t>(p0) * kTnMaxCuts, d_reach.p, static_cast<size_t>(np) * kTnMaxCuts)) ||
+            (rc = wait_or_drop_table(c)) || (rc = ev.add_us(&c->top_null_us)))   // (the next batch reuses the buffers)
+            return rc;
+    }
+    drain.dismiss();
+    for (int64_t p = 0; p < n_perm; ++p) {
+        int64_t m = -1;
+        int32_t gi = -1, gj = -1;
+        tn_unpack(keys[static_cast<size_t>(p)], G, &m, &gi, &gj);
+        if (m >= 0 && !(gi >= 0 && gi < gj && gj < G && m <= 2 * s_a * s_b)) {
+            set_error("%s: permutation %lld reduced to the pair (%d, %d) with |N| = %lld of %d genes; nothing was written", what, (long long)p, gi, gj,
+                      (long long)m, G);
+            return REO_EHIP;
+        }
+    }
+    for (int64_t p = 0; p < n_perm; ++p) {
+        tn_unpack(keys[static_cast<size_t>(p)], G, &max_n[p], &arg_i[p], &arg_j[p]);
+        for (int t = 0; t < n_cuts; ++t) n_reach[p * n_cuts + t] = static_cast<int64_t>(reach[static_cast<size_t>(p) * kTnMaxCuts + static_cast<size_t>(t)]);
+    }
     return REO_OK;
 }
 

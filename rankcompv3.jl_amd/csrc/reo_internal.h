@@ -343,6 +343,8 @@ struct reo_ctx {
     // top-scoring pairs (reo_top_pairs; toppairs.hip, top_pairs.h)
     int64_t top_hist_us = 0;            // reo_get_info 36: microseconds the histogram passes of the last reo_top_pairs took in all (HIP events)
     int64_t top_emit_us = 0;            // reo_get_info 37: microseconds of its emit pass
+    int64_t top_null_batch = 0;         // reo_get_info 38: permutations per launch of the last reo_top_pairs_null
+    int64_t top_null_us = 0;            // reo_get_info 39: microseconds its launches of k_top_pairs_null took in all (HIP events)
     reo::DevBuf<int32_t> raw;           // [G][8]
     reo::DevBuf<uint32_t> delta_list;   // [2][Gp] changed genes (gene << 1 | added) per pass parity
     reo::DevBuf<int32_t> cont;          // [G][9]
@@ -495,6 +497,15 @@ int32_t launch_top_hist(reo_ctx *c, const int32_t *d_gside, int s_a, int s_b, co
                         int shift, unsigned long long *d_hist);
 int32_t launch_top_emit(reo_ctx *c, const int32_t *d_gside, int s_a, int s_b, const int64_t *d_D, const uint32_t *d_maskbits, const TpKey &cut,
                         int shift, TpRec *d_cand, int64_t capacity, uint32_t *d_cand_n);
+
+// toppairsnull.hip: the kernels of reo_top_pairs_null (the key, the word packing and the host checks: top_pairs_null.h).
+// launch_top_null_words: the label rows d_side ([n_perm][S] bytes 0 / 1 / 2, checked by the caller, n_perm <= kTnBatchCap) and d_slot2col
+// into the A-words d_aw (pn_word_count(n_perm, blocks) words, cleared here) and the live words d_live ([blocks]: the slots of the two
+// sides).  launch_top_pairs_null: for permutations 0 .. np - 1 of those words the largest key into d_keys ([kTnBatchCap], atomicMax) and
+// the pairs with |N| >= cuts[t] into d_reach ([kTnBatchCap][kTnMaxCuts], atomicAdd); the caller has cleared both; cuts: HOST, n_cuts values
+int32_t launch_top_null_words(reo_ctx *c, const uint8_t *d_side, int64_t n_perm, const int32_t *d_slot2col, uint32_t *d_aw, uint32_t *d_live);
+int32_t launch_top_pairs_null(reo_ctx *c, const uint32_t *d_aw, const uint32_t *d_live, int np, int s_a, int s_b, const uint32_t *d_maskbits,
+                              const int64_t *cuts, int n_cuts, unsigned long long *d_keys, unsigned long long *d_reach);
 
 // maskedpairs.hip: the kernels of reo_set_valid_mask / reo_build_pairs_masked / reo_pair_counts_masked (shared arithmetic and host checks:
 // masked_pairs.h).  launch_valid_words: c->vmask and d_slot2col ([32 * sample blocks], -1 for padding) into c->vwords (sized by the

@@ -15,7 +15,7 @@ from typing import NamedTuple
 import numpy as np
 
 from . import _ffi, synth
-from ._ffi import PairList, PairSupport, PermNull, SampleCalls, SampleCounts, SampleScores, SampleTests, TopPairs, class_mask, permuted_labels  # noqa: F401
+from ._ffi import PairList, PairSupport, PermNull, SampleCalls, SampleCounts, SampleScores, SampleTests, TopPairs, TopPairsNull, class_mask, permuted_labels, permuted_sides  # noqa: F401
 
 HEADER = ["pval", "padj", "n11", "n12", "n13", "n21", "n22", "n23", "n31", "n32", "n33",
           "Δ1", "Δ2", "se", "z1", "up_down"]  # src/RankCompV3.jl:665
@@ -291,6 +291,43 @@ def write_top_pairs_tsv(path, gene_names, top) -> None:
                                str(int(top.n_gt[e, 1])), str(int(top.n_eq[e, 1]))]) + "\n")
 
 
+def top_pairs_null_plan(top_pairs, top_pairs_permutations) -> None:
+    """The refusals of `top_pairs_permutations`, raised before any context is opened (ValueError): given without `top_pairs`, or no number
+    of permutations between 1 and 2^20."""
+    B = top_pairs_permutations
+    if B is None:
+        return
+    if top_pairs is None:
+        raise ValueError("top_pairs_permutations needs top_pairs: the null is that of the best score of the listed pairs")
+    if isinstance(B, bool) or not isinstance(B, (int, np.integer)) or not 1 <= int(B) <= 1 << 20:
+        raise ValueError(f"top_pairs_permutations = {B!r}: None (no null) or a number of permutations between 1 and 2^20")
+
+
+def top_pairs_null_cuts(top) -> np.ndarray:
+    """The cuts of a comparison's null: |N| of the list's entries 1, 10, 100 and its last, where they exist (int64, each entry once)."""
+    at = sorted({e for e in (0, 9, 99, top.num.size - 1) if 0 <= e < top.num.size})
+    return np.abs(top.num[at]).astype(np.int64)
+
+
+def deg_top_pairs_null(ctx, gid, k, treat, top, permutations, perm_seed, perm_strata) -> dict:
+    """{"top_pairs_null"} of one comparison on `ctx`: the TopPairsNull of `permutations` label shuffles of the two sides of its "top_pairs"
+    (permuted_sides: seed perm_seed + k, within perm_strata if given; the samples of other groups take no part), with the cuts of
+    top_pairs_null_cuts."""
+    rows = permuted_sides(gid, k, treat, int(permutations), seed=int(perm_seed) + int(k), strata=perm_strata)
+    return {"top_pairs_null": ctx.top_pairs_null(rows, a=k, b=treat, cuts=top_pairs_null_cuts(top))}
+
+
+def write_top_pairs_null_tsv(path, gene_names, top, null) -> None:
+    """The pair columns of write_top_pairs_tsv plus p_max (TopPairsNull.p_max, by repr): one line per pair in the list's own order."""
+    score, rank_score, direction, p_max = top.score, top.rank_score, top.direction, null.p_max(top)
+    with open(path, "w") as f:
+        f.write("gene_i\tgene_j\tdirection\tscore\trank_score\tgt_A\teq_A\tgt_B\teq_B\tp_max\n")
+        for e in range(top.gene_i.size):
+            f.write("\t".join([str(gene_names[int(top.gene_i[e])]), str(gene_names[int(top.gene_j[e])]), str(int(direction[e])),
+                               repr(float(score[e])), repr(float(rank_score[e])), str(int(top.n_gt[e, 0])), str(int(top.n_eq[e, 0])),
+                               str(int(top.n_gt[e, 1])), str(int(top.n_eq[e, 1])), repr(float(p_max[e]))]) + "\n")
+
+
 def missing_plan(data, missing, valid, *, shard=(0, 1), contrasts=None, sample_scores=False, sample_tests=False, sample_calls=False,
                  pair_support=False):
     """The pairwise route of run_identify_degs, decided before any context is opened.  Pure: no library, no GPU.  Returns (data, mask):
@@ -339,7 +376,7 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
                       seed: int = 0, device: int = -1, shard=(0, 1), allreduce=None, allgather=None, profile: bool = False,
                       pairs=None, sample_scores: bool = False, pair_support: bool = False, contrasts=None,
                       sample_tests: bool = False, sample_calls: bool = False, missing=None, valid=None, min_complete=None,
-                      permutations=None, perm_seed: int = 0, perm_strata=None, top_pairs=None) -> DegRun:
+                      permutations=None, perm_seed: int = 0, perm_strata=None, top_pairs=None, top_pairs_permutations=None) -> DegRun:
     """identify_degs with the extras (trace, timings) kept.  `data` is a host matrix (numpy, anything np.asarray takes) or a torch
     tensor on a ROCm device, which is used in place (_ffi.device_matrix).  A column-major host matrix is read in place; a row-major one
     (numpy's default C order, column slices of a wider C-ordered array) is copied column-major on the host first, or, with REO_ROWMAJOR=1
@@ -392,12 +429,18 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
     `top_pairs` (not in the reference): an int K adds "top_pairs" to every comparison dict, the TopPairs of the K best of ALL gene pairs
     (Context.top_pairs: the top-scoring-pair search) for the comparison's group k against the contrast's treatment group, or against every
     other sample for the reference's comparisons; taken after the other read-outs and before the permutation null.  Refused with a mask and
-    with shard[1] > 1 (top_pairs_plan).  None (the default): no further call, no new key."""
+    with shard[1] > 1 (top_pairs_plan).  None (the default): no further call, no new key.
+    `top_pairs_permutations` (not in the reference): an int B, together with `top_pairs`, adds "top_pairs_null" to every comparison dict,
+    the TopPairsNull of B label shuffles of the search's two sides (Context.top_pairs_null; rows from permuted_sides with seed
+    perm_seed + k, shuffled within perm_strata when given; cuts: |N| of the list's entries 1, 10, 100 and K) -- .p_max(top_pairs) is the
+    single-step maxT adjusted p-value of every listed pair.  Works for the reference's comparisons and for contrasts.  Without `top_pairs`:
+    ValueError.  None (the default): no further call, no new key."""
     need_pairs_for_support(pairs, pair_support)
     data, mask = missing_plan(data, missing, valid, shard=shard, contrasts=contrasts, sample_scores=sample_scores, sample_tests=sample_tests,
                               sample_calls=sample_calls, pair_support=pair_support)
     perm_plan(permutations, contrasts=contrasts, masked=mask is not None, shard=shard)
     top_pairs_plan(top_pairs, masked=mask is not None, shard=shard)
+    top_pairs_null_plan(top_pairs, top_pairs_permutations)
     if mask is not None:
         _ffi.resolve_min_complete(min_complete, (1, 1), pval_reo)   # (its refusals, before a context is opened)
     # a torch tensor on a ROCm device: a strided one is used where it is, a sparse one is made dense there (its device is the context's)
@@ -458,6 +501,8 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
                 comps[-1]["sample_calls"] = ctx.sample_calls(pval_deg, padj_deg)   # all genes, the run's thresholds, the same reference set
             if top_pairs is not None:
                 comps[-1].update(deg_top_pairs(ctx, k, treat, top_pairs))
+                if top_pairs_permutations is not None:
+                    comps[-1].update(deg_top_pairs_null(ctx, gid, k, treat, comps[-1]["top_pairs"], top_pairs_permutations, perm_seed, perm_strata))
             if permutations is not None:   # last: it uses the iteration's buffers (ref_mask is refused behind it)
                 comps[-1].update(deg_perm_null(ctx, gid, k, permutations, perm_seed, perm_strata, pval_deg, padj_deg))
         timings = ctx.timings() if profile else {}
@@ -500,7 +545,8 @@ def identify_degs_cells(cells, cell_group, gene_names, n_pseudo, pval_reo, pval_
                         min_profiles: int = 0, min_features: int = 0, ref_gene_max: int = 3000, seed: int = 0, device: int = 0,
                         profile: bool = False, pairs=None, sample_scores: bool = False, pair_support: bool = False,
                         contrasts=None, sample_tests: bool = False, sample_calls: bool = False,
-                        permutations=None, perm_seed: int = 0, perm_strata=None, top_pairs=None) -> CellsDegRun:
+                        permutations=None, perm_seed: int = 0, perm_strata=None, top_pairs=None,
+                        top_pairs_permutations=None) -> CellsDegRun:
     """Cells to DEGs without a host trip for the profiles: `cells` is a genes x cells matrix (scipy.sparse, anything np.asarray takes, or
     a torch tensor on a ROCm device -- sparse or strided -- which is read where it is: reo_set_matrix_pseudobulk_*_dev_*),
     cell_group one label per cell.  cells_partition -> the pseudo-bulk sums written into the context's matrix (set_matrix_pseudobulk) ->
@@ -511,11 +557,12 @@ def identify_degs_cells(cells, cell_group, gene_names, n_pseudo, pval_reo, pval_
     `pairs`, `sample_scores`, `pair_support`, `sample_tests`, `sample_calls`: as in run_identify_degs; gene indices are those of the KEPT genes (run.gene_names), columns
     the kept profiles.  `contrasts`: as in run_identify_degs, over the group levels of the cells (checked against the levels of cell_group
     before any context is opened, and again against those of the kept profiles).  `permutations`, `perm_seed`, `perm_strata`: as in
-    run_identify_degs; perm_strata has one label per pseudo-bulk PROFILE of cells_partition (the kept ones are used).  `top_pairs`: as in
-    run_identify_degs."""
+    run_identify_degs; perm_strata has one label per pseudo-bulk PROFILE of cells_partition (the kept ones are used).  `top_pairs`,
+    `top_pairs_permutations`: as in run_identify_degs."""
     need_pairs_for_support(pairs, pair_support)
     perm_plan(permutations, contrasts=contrasts)
     top_pairs_plan(top_pairs)
+    top_pairs_null_plan(top_pairs, top_pairs_permutations)
     on_device = _ffi.is_device_sparse(cells) or _ffi.is_device_tensor(cells)
     if on_device:   # a torch tensor on a ROCm device, sparse or strided: summed where it is, on its own device
         device = cells.device.index if cells.device.index is not None else -1
@@ -565,6 +612,9 @@ def identify_degs_cells(cells, cell_group, gene_names, n_pseudo, pval_reo, pval_
                 comps[-1]["sample_calls"] = ctx.sample_calls(pval_deg, padj_deg)   # all genes, the run's thresholds, the same reference set
             if top_pairs is not None:
                 comps[-1].update(deg_top_pairs(ctx, k, treat, top_pairs))
+                if top_pairs_permutations is not None:
+                    strata = None if perm_strata is None else np.asarray(perm_strata)[np.asarray(profile_kept, dtype=bool)]
+                    comps[-1].update(deg_top_pairs_null(ctx, gid, k, treat, comps[-1]["top_pairs"], top_pairs_permutations, perm_seed, strata))
             if permutations is not None:   # last: it uses the iteration's buffers (ref_mask is refused behind it)
                 strata = None if perm_strata is None else np.asarray(perm_strata)[np.asarray(profile_kept, dtype=bool)]
                 comps[-1].update(deg_perm_null(ctx, gid, k, permutations, perm_seed, strata, pval_deg, padj_deg))
