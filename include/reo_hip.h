@@ -461,6 +461,44 @@ int32_t reo_top_pairs_null(reo_ctx *ctx, int32_t a, int32_t b /* -1: every other
                            int64_t *max_n /* n_perm */, int32_t *arg_i, int32_t *arg_j /* n_perm each */,
                            int64_t *n_reach /* [n_perm][n_cuts]; may be NULL when n_cuts == 0 */);
 
+/* Leave-one-out cross-validation of the k-TSP classifier: what Geman et al. report for the top-scoring pair and what Tan et al. choose k
+ * by.  The reference has no such output.
+ * Sides A and B are those of reo_top_pairs(a, b).  A FOLD is one sample s of side A or of side B; its training set is both sides without s,
+ * so its sizes are (S_A - 1, S_B) or (S_A, S_B - 1).  Samples of groups on neither side are no folds.  In fold s, with the sizes and
+ * counts of the training set: N(s) = w(A) S_B - w(B) S_A as above, D(s) the rank shift over the training samples, Gamma(s) =
+ * |D(s)_i - D(s)_j|, and the pairs i < j with both genes inside gene_mask (NULL: all genes) are ordered exactly as reo_top_pairs orders
+ * them: |N(s)| descending, Gamma(s) descending, i ascending, j ascending.  The fold's selection is the greedy disjoint one of k-TSP: walk
+ * that order and take a pair when neither of its genes is used yet, up to kmax pairs.  It is nested: the first k picks are the k-TSP of
+ * every k <= kmax.  For pick r the held-out sample has an outcome o: +1 gene_i above gene_j, 0 tied, -1 below, under the comparator of
+ * the matrix's element type (ties are reported as ties); its vote is sign(N(s)) o, positive = A-like.
+ * By definition the result of fold s equals what a context gives in which s is moved into a group on neither side and reo_top_pairs(every
+ * pair, a, b), the greedy disjoint selection of kmax pairs and reo_pair_support with outcomes are run.  All results are exact integers,
+ * independent of the launch geometry, of buffer sizes and of the order in which the candidates are stored.
+ * Row s of the outputs is the caller's column s.  gene_i, gene_j: -1 where the fold has fewer disjoint pairs, and in the rows of samples
+ * that are no folds (num, rank_num and outcome are 0 there).  side[s]: 1 = A, 0 = B, 2 = neither.  stats: the cut T, the number of
+ * candidates, the histogram passes spent finding T, the number of folds.
+ * The route (csrc/top_pairs_loo.h has the proof, csrc/toppairsloo.hip the kernels): removing one sample moves |N| of a pair by at most
+ * 2 max(S_A, S_B), so every pick of every fold lies in a band below the full-data winners.  (1) reo_top_pairs' own selection with a list
+ * that doubles from 1 024 to 2^20 pairs until its greedy disjoint walk yields 2 kmax pairs, the last with |N| = v; T = max(v - 4 max(S_A,
+ * S_B), 0), or 0 when they do not exist.  (2) One emit pass of the search's kernel leaves every pair with |N| >= T on the device (a second
+ * one when the first buffer of 2^18 records was too small).  (3) k_loo_words compares the candidates once on the bit planes: per block of
+ * 32 sample slots a gt word and an eq word.  (4) k_loo_select, one workgroup per fold, forms the fold's counts by subtracting the
+ * sample's own bit, and selects kmax times.  No fold recounts all pairs.
+ * More than 2^26 candidates, or more than fit in free device memory: REO_ENOMEM, with the count and the cut in the message (small sides
+ * and many genes: one sample moves every score by a large step).  REO_TOP_PAIRS_LOO_CAP=n and REO_TOP_PAIRS_LOO_FIRST=n in the
+ * environment lower that cap and the first buffer, REO_TOP_PAIRS_LOO_ALL=1 sets T = 0 (all three: for the tests, read per call).
+ * Needs the matrix, the groups and the transform (run here if need be); no class table, no thresholds, no reference set.  Reads and writes
+ * none of the iteration's buffers.  Host arrays only, allocated by the caller.  reo_get_info 40 and 41 = the microseconds of k_loo_words
+ * and of k_loo_select of the last call (HIP events); no other info entry is touched.
+ * REO_EINVAL, each with its own message, checked on the host before anything is uploaded, and a refused call writes nothing: everything
+ * reo_top_pairs refuses of the context and of a, b (a reo_create_multi context; a sharded context; a validity mask set; G or S above
+ * 65535; a or b outside the groups; b == a); kmax outside [1, 64]; a NULL output; a gene_mask byte other than 0 or 1; a side of fewer
+ * than two samples (the message names the side and its size). */
+int32_t reo_top_pairs_loo(reo_ctx *ctx, int32_t a, int32_t b /* -1: every other sample */, const uint8_t *gene_mask /* G bytes 0/1, or NULL */,
+                          int32_t kmax, int32_t *gene_i, int32_t *gene_j /* [S][kmax] each */,
+                          int64_t *num /* [S][kmax]: N(s), signed */, int64_t *rank_num /* [S][kmax]: Gamma(s) */,
+                          int8_t *outcome /* [S][kmax]: -1 / 0 / +1 */, int8_t *side /* [S] */, int64_t *stats /* [4] */);
+
 /* Missing values: pair classes from the samples where BOTH genes were observed.  The reference drops every gene with a missing cell
  * (dropmissing!, src/RankCompV3.jl:601) and the library refuses a NaN; with a validity mask V beside the resident matrix a pair (i, j) is
  * compared in the samples where both values exist, and its stability is judged against the threshold of that many samples.
@@ -772,7 +810,8 @@ int32_t reo_get_timings(reo_ctx *ctx, double *ms, int32_t n);
  * makes them once: 0 or 1), 34 the tables per batch of the last reo_perm_null, 35 the microseconds that its launches of the permuted pair
  * kernel took in all (HIP events around each launch), 36 and 37 the microseconds of the histogram passes and of the emit pass of the
  * last reo_top_pairs, 38 the permutations per launch of the last reo_top_pairs_null, 39 the microseconds that its launches of the null
- * kernel took in all (HIP events around each launch). */
+ * kernel took in all (HIP events around each launch), 40 and 41 the microseconds of k_loo_words and of k_loo_select of the last
+ * reo_top_pairs_loo. */
 int32_t reo_get_info(reo_ctx *ctx, int64_t *info, int32_t n);
 
 #ifdef __cplusplus

@@ -35,7 +35,7 @@ SYMBOLS = [
     "reo_set_matrix_pseudobulk_dense_f64", "reo_set_matrix_pseudobulk_dense_i64", "reo_set_matrix_pseudobulk_csc_f64", "reo_set_matrix_pseudobulk_csc_i64",
     "reo_filter_matrix", "reo_get_matrix", "reo_get_ref_mask", "reo_pair_list", "reo_sample_counts", "reo_pair_support",
     "reo_sample_tests", "reo_sample_calls", "reo_set_valid_mask", "reo_build_pairs_masked", "reo_pair_counts_masked",
-    "reo_perm_null", "reo_perm_codes", "reo_rank_shift", "reo_top_pairs", "reo_top_pairs_null",
+    "reo_perm_null", "reo_perm_codes", "reo_rank_shift", "reo_top_pairs", "reo_top_pairs_null", "reo_top_pairs_loo",
 ] +[f"reo_set_matrix_{form}_{t}" for form in ("csc_dev", "pseudobulk_csc_dev", "pseudobulk_dense_dev") for t in ("f64", "i64", "f32", "i32")]
 
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p)
@@ -153,6 +153,7 @@ def lib() -> ctypes.CDLL:
         "reo_rank_shift": (i32, [vp, i32, i32, vp]),
         "reo_top_pairs": (i32, [vp, i32, i32, vp, i64, vp, vp, vp, vp, vp, vp]),
         "reo_top_pairs_null": (i32, [vp, i32, i32, vp, i64, vp, vp, i32, vp, vp, vp, vp]),
+        "reo_top_pairs_loo": (i32, [vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
     }
     for t in ("f64", "i64", "f32", "i32"):   # SPARSE ON THE DEVICE
         sig["reo_set_matrix_csc_dev_" + t] = (i32, [vp, i64, i64, i64, vp, vp, i32, vp])
@@ -542,6 +543,80 @@ class TopPairsNull(NamedTuple):
         """The mean of n_reach over the permutations, one value per cut: with cuts = |tp.num[n - 1]| the expected number of chance pairs at
         least as good as the n-th listed one."""
         return self.n_reach.astype(np.float64).mean(axis=0) if self.n_reach.shape[0] else np.zeros(self.cuts.size)
+
+
+class TopPairsLoo(NamedTuple):
+    """reo_top_pairs_loo: leave-one-out cross-validation of the k-TSP classifier for side A (group a) against side B (group b, or every
+    other sample for b None).  Row s = sample s (the caller's column): the kmax picks of the greedy disjoint selection on both sides
+    WITHOUT s, in the order of TopPairs with the fold's own counts, sizes and rank shifts; num = N of the fold (signed), rank_num = its
+    Gamma, outcome = what sample s itself shows on the pick (+1 gene_i above gene_j, 0 tied, -1 below).  The selection is nested: the
+    first k picks are the k-TSP of every k <= kmax.  gene_i = gene_j = -1 (num, rank_num, outcome 0) where a fold has fewer disjoint
+    pairs and in the rows of samples on neither side (side 2), which are no folds."""
+    gene_i: np.ndarray       # int32, S x kmax
+    gene_j: np.ndarray       # int32, S x kmax
+    num: np.ndarray          # int64, S x kmax
+    rank_num: np.ndarray     # int64, S x kmax
+    outcome: np.ndarray      # int8, S x kmax
+    side: np.ndarray         # int8, S: 1 = A, 0 = B, 2 = neither
+    side_sizes: np.ndarray   # int64, 2: S_A, S_B (of the full data)
+    a: int
+    b: int | None
+    cut: int                 # the cut T on the full-data |N| that defines the candidates
+    n_candidates: int
+
+    def votes(self) -> np.ndarray:
+        """S x kmax int32: the cumulative sum along k of sign(num) * outcome -- the k-TSP vote of the held-out sample with the first k
+        picks of its own fold; positive means A-like."""
+        return np.cumsum(np.sign(self.num).astype(np.int32) * self.outcome.astype(np.int32), axis=1, dtype=np.int64).astype(np.int32).reshape(self.num.shape)
+
+    def predictions(self, k: int) -> np.ndarray:
+        """int8 per sample with the first k picks: +1 A-like, -1 B-like, 0 undecided; 0 for the samples that are no folds."""
+        k = int(k)
+        if not 1 <= k <= self.num.shape[1]:
+            raise DimensionMismatch(REO_EINVAL, f"predictions: k = {k}, between 1 and kmax = {self.num.shape[1]}")
+        return np.where(self.side == 2, 0, np.sign(self.votes()[:, k - 1])).astype(np.int8)
+
+    def errors(self) -> dict:
+        """{"n_wrong", "n_undecided", "n_folds"}: per k = 1 .. kmax (int64 arrays of length kmax) the folds whose held-out sample is
+        predicted onto the other side, those left undecided (vote 0), and the number of folds."""
+        fold = self.side != 2
+        truth = np.where(self.side == 1, 1, -1)[fold]
+        pred = np.sign(self.votes()[fold, :])
+        kmax = self.num.shape[1]
+        return {"n_wrong": (pred == -truth[:, None]).sum(axis=0, dtype=np.int64).reshape(kmax),
+                "n_undecided": (pred == 0).sum(axis=0, dtype=np.int64).reshape(kmax),
+                "n_folds": np.full(kmax, int(fold.sum()), dtype=np.int64)}
+
+    def error_rate(self, k=None):
+        """(wrong + undecided) / folds with the first k picks, float64; k None: the array over k = 1 .. kmax."""
+        e = self.errors()
+        rate = (e["n_wrong"] + e["n_undecided"]).astype(np.float64) / np.maximum(e["n_folds"], 1)
+        if k is None:
+            return rate
+        k = int(k)
+        if not 1 <= k <= rate.size:
+            raise DimensionMismatch(REO_EINVAL, f"error_rate: k = {k}, between 1 and kmax = {rate.size}")
+        return float(rate[k - 1])
+
+    def best_k(self, odd: bool = True) -> int:
+        """The smallest k with the lowest error rate; odd=True (the k-TSP convention: no tied votes on tie-free data) looks at odd k only."""
+        rate = self.error_rate()
+        ks = [k for k in range(1, rate.size + 1) if not odd or k % 2 == 1]
+        return min(ks, key=lambda k: (rate[k - 1], k))
+
+    def pair_frequency(self, k: int):
+        """(gene_i, gene_j, count): the distinct pairs among the first k picks of all folds and the number of folds that chose each, in the
+        order count descending, then (i, j) ascending; int32, int32, int64."""
+        k = int(k)
+        if not 1 <= k <= self.num.shape[1]:
+            raise DimensionMismatch(REO_EINVAL, f"pair_frequency: k = {k}, between 1 and kmax = {self.num.shape[1]}")
+        gi, gj = self.gene_i[:, :k].reshape(-1), self.gene_j[:, :k].reshape(-1)
+        keep = gi >= 0
+        if not keep.any():
+            return np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.int64)
+        pairs, count = np.unique(np.stack([gi[keep], gj[keep]], axis=1), axis=0, return_counts=True)
+        order = np.lexsort((pairs[:, 1], pairs[:, 0], -count))
+        return pairs[order, 0].astype(np.int32), pairs[order, 1].astype(np.int32), count[order].astype(np.int64)
 
 
 def bh_columns(p: np.ndarray) -> np.ndarray:
@@ -1298,6 +1373,27 @@ class Context:
                                          _ptr(max_n), _ptr(gi), _ptr(gj), _ptr(reach) if reach.size else None))
         return TopPairsNull(max_n[:B], gi[:B], gj[:B], reach[:B], ct, sizes, a, None if b < 0 else b)
 
+    def top_pairs_loo(self, kmax: int, a: int = 0, b=None, gene_mask=None) -> TopPairsLoo:
+        """Leave-one-out cross-validation of k-TSP (reo_top_pairs_loo): for every sample of group a or of side B (group b; None: every
+        other sample) the kmax greedy disjoint picks of the search on both sides without that sample -- both genes inside gene_mask when
+        one is given -- and the sample's own outcome on every pick, as a TopPairsLoo.  Every fold is decided on the device from one set of
+        candidate pairs; exact.  Sides and refusals as in top_pairs; each side needs two samples; 1 <= kmax <= 64."""
+        kmax = int(kmax)
+        a, b, sizes = self._sides(a, b)
+        gm = None
+        if gene_mask is not None:
+            gm = np.asarray(gene_mask)
+            if gm.shape != (self.G,):
+                raise DimensionMismatch(REO_EINVAL, f"top_pairs_loo: gene_mask has shape {tuple(gm.shape)}, the matrix has {self.G} genes")
+            gm = np.ascontiguousarray(gm if gm.dtype == np.uint8 else gm != 0, dtype=np.uint8)
+        m, S = min(max(kmax, 1), 64), max(self.S, 1)   # (the library refuses kmax outside [1, 64] before it writes)
+        gi, gj = np.full((S, m), -1, dtype=np.int32), np.full((S, m), -1, dtype=np.int32)
+        num, gam = np.zeros((S, m), dtype=np.int64), np.zeros((S, m), dtype=np.int64)
+        out, side, stats = np.zeros((S, m), dtype=np.int8), np.full(S, 2, dtype=np.int8), np.zeros(4, dtype=np.int64)
+        check(self._L.reo_top_pairs_loo(self._h, a, b, _opt(gm), kmax, _ptr(gi), _ptr(gj), _ptr(num), _ptr(gam), _ptr(out), _ptr(side), _ptr(stats)))
+        n = self.S
+        return TopPairsLoo(gi[:n], gj[:n], num[:n], gam[:n], out[:n], side[:n], sizes, a, None if b < 0 else b, int(stats[0]), int(stats[1]))
+
     def mccullagh(self, cont) -> np.ndarray:
         cont = np.ascontiguousarray(cont, dtype=np.int32).reshape(-1, 9)
         out = np.zeros((cont.shape[0], 5), dtype=np.float64)
@@ -1400,8 +1496,8 @@ class Context:
                 "k2_full_launches": int(ms[9]), "k2_delta_ms": ms[10], "set_matrix_host_wall_ms": ms[11]}
 
     def info(self) -> dict:
-        w = np.zeros(40, dtype=np.int64)
-        check(self._L.reo_get_info(self._h, _ptr(w), 40))
+        w = np.zeros(42, dtype=np.int64)
+        check(self._L.reo_get_info(self._h, _ptr(w), 42))
         v = np.zeros(28, dtype=np.int64)   # fields 0-27 keep their places (tests/test_csc_device_cpu.py reads this line); 28 is appended
         v[:] = w[:28]
         return {"G": int(v[0]), "S": int(v[1]), "Gp": int(v[2]), "table_bytes": int(v[3]), "has_ties": int(v[4]),
@@ -1416,4 +1512,5 @@ class Context:
                 "masked_build": int(w[31]), "k1_slot_slice": int(w[32]), "planes_on_demand": int(w[33]),
                 "perm_batch": int(w[34]), "perm_kernel_us": int(w[35]),
                 "top_pairs_hist_us": int(w[36]), "top_pairs_emit_us": int(w[37]),
-                "top_pairs_null_batch": int(w[38]), "top_pairs_null_us": int(w[39])}
+                "top_pairs_null_batch": int(w[38]), "top_pairs_null_us": int(w[39]),
+                "top_pairs_loo_words_us": int(w[40]), "top_pairs_loo_select_us": int(w[41])}

@@ -1,6 +1,7 @@
 // The query entry points of the C ABI (include/reo_hip.h): reo_pair_list, reo_sample_counts, reo_sample_tests, reo_sample_calls,
-// reo_pair_support, reo_rank_shift, reo_top_pairs, reo_top_pairs_null.  Host code only; the kernels are in pairlist.hip, samplecounts.hip,
-// sampletests.hip, samplecalls.hip, pairsupport.hip, toppairs.hip and toppairsnull.hip.  What they share stands once, in front.
+// reo_pair_support, reo_rank_shift, reo_top_pairs, reo_top_pairs_null, reo_top_pairs_loo.  Host code only; the kernels are in pairlist.hip,
+// samplecounts.hip, sampletests.hip, samplecalls.hip, pairsupport.hip, toppairs.hip, toppairsnull.hip and toppairsloo.hip.  What they share
+// stands once, in front.
 #include <algorithm>
 #include <cstdlib>
 #include <utility>
@@ -13,6 +14,7 @@
 #include "pair_support.h"
 #include "top_pairs.h"
 #include "top_pairs_null.h"
+#include "top_pairs_loo.h"
 
 namespace reo {
 namespace {
@@ -126,7 +128,7 @@ struct TimedPair {
 struct TopSides {
     std::vector<int32_t> gside;   // per group: 0 side A, 1 side B, 2 neither
     int s_a = 0, s_b = 0;
-    int32_t make(reo_ctx *c, const char *what, int32_t a, int32_t b)
+    void count(reo_ctx *c, int32_t a, int32_t b)   // the sides and their sizes, unchecked
     {
         gside.assign(static_cast<size_t>(c->ngroups), 2);
         for (int g = 0; g < c->ngroups; ++g) gside[static_cast<size_t>(g)] = g == a ? 0 : ((b < 0 || g == b) ? 1 : 2);
@@ -136,6 +138,10 @@ struct TopSides {
             if (gside[static_cast<size_t>(g)] == 0) ++s_a;
             else if (gside[static_cast<size_t>(g)] == 1) ++s_b;
         }
+    }
+    int32_t make(reo_ctx *c, const char *what, int32_t a, int32_t b)
+    {
+        count(c, a, b);
         if (s_a > 0 && s_b > 0) return REO_OK;
         set_error("%s: side A has %d samples and side B %d, both sides need at least one", what, s_a, s_b);
         return REO_EINVAL;
@@ -623,6 +629,143 @@ int32_t reo_top_pairs_null(reo_ctx *c, int32_t a, int32_t b, const uint8_t *side
         tn_unpack(keys[static_cast<size_t>(p)], G, &max_n[p], &arg_i[p], &arg_j[p]);
         for (int t = 0; t < n_cuts; ++t) n_reach[p * n_cuts + t] = static_cast<int64_t>(reach[static_cast<size_t>(p) * kTnMaxCuts + static_cast<size_t>(t)]);
     }
+    return REO_OK;
+}
+
+// Leave-one-out cross-validation of the k-TSP selection (include/reo_hip.h): every check on the host first (top_pairs_loo.h).  Step 1: the
+// full-data list of reo_top_pairs itself, deepened until its greedy disjoint walk yields 2 kmax pairs, gives the cut T (loo_cut).  Step 2:
+// the emit pass of k_top_pairs with the cut on the |N| field of the key leaves every pair with |N| >= T on the device; a counter past the
+// buffer sizes a second emit.  Step 3: k_loo_words; step 4: k_loo_select, one workgroup per fold (toppairsloo.hip).  Reads the bit planes
+// of the transform and nothing of the class table or the iteration; writes none of them.  The caller's arrays are written at the end.
+int32_t reo_top_pairs_loo(reo_ctx *c, int32_t a, int32_t b, const uint8_t *gene_mask, int32_t kmax, int32_t *gene_i, int32_t *gene_j, int64_t *num,
+                          int64_t *rank_num, int8_t *outcome, int8_t *side, int64_t *stats)
+{
+    const char *what = "reo_top_pairs_loo";
+    int32_t rc = top_begin(c, what);
+    if (rc) return rc;
+    char msg[320];
+    if (loo_check_args(top_state(c), a, b, gene_mask, kmax, gene_i, gene_j, num, rank_num, outcome, side, stats, msg, sizeof msg)) { set_error("%s", msg); return REO_EINVAL; }
+    TopSides sides;
+    sides.count(c, a, b);
+    if (loo_check_sides(sides.s_a, sides.s_b, msg, sizeof msg)) { set_error("%s", msg); return REO_EINVAL; }
+    std::vector<int32_t> map;
+    if ((rc = ensure_transform(c)) || (rc = query_slot_map(c, what, map))) return rc;
+    const int G = static_cast<int>(c->G);
+    const size_t S = static_cast<size_t>(c->S), cells = S * static_cast<size_t>(kmax);
+    const int nblk = c->goff32.back() / 32;
+    const uint64_t n_max = 2 * static_cast<uint64_t>(sides.s_a) * static_cast<uint64_t>(sides.s_b);
+    if (n_max >> 31) { set_error("%s: 2 S_A S_B is %llu: more than the key's 31 bits hold", what, (unsigned long long)n_max); return REO_EHIP; }
+    // step 1: the cut
+    int64_t cut = 0, passes = 0;
+    const char *all = getenv("REO_TOP_PAIRS_LOO_ALL");
+    if (!(all && atoi(all) == 1)) {
+        const int64_t hist_us = c->top_hist_us, emit_us = c->top_emit_us;   // (reo_get_info 36 / 37 belong to the caller's last reo_top_pairs)
+        std::vector<int32_t> li, lj, lc;
+        std::vector<int64_t> lk;
+        for (int64_t n_want = kLooFirstWant; ; n_want *= 2) {
+            const size_t n = static_cast<size_t>(n_want);
+            li.resize(n); lj.resize(n); lc.resize(4 * n); lk.resize(2 * n);
+            int64_t found = 0, last = -1;
+            int32_t run = 0;
+            rc = reo_top_pairs(c, a, b, gene_mask, n_want, li.data(), lj.data(), lc.data(), lk.data(), &found, &run);
+            c->top_hist_us = hist_us; c->top_emit_us = emit_us;
+            if (rc) return rc;
+            passes += run;
+            if (loo_disjoint(li.data(), lj.data(), found, G, 2 * static_cast<int64_t>(kmax), &last) >= 2 * static_cast<int64_t>(kmax)) {
+                cut = loo_cut(static_cast<int64_t>(tp_abs(lk[2 * static_cast<size_t>(last)])), sides.s_a, sides.s_b);
+                break;
+            }
+            if (found < n_want || n_want >= kTpMaxWant) break;   // every eligible pair is listed, or the deepest list: T = 0
+        }
+    }
+    std::vector<uint32_t> bits;
+    if (gene_mask) {
+        bits.assign(static_cast<size_t>(c->Wp), 0u);
+        for (int g = 0; g < G; ++g)
+            if (gene_mask[g]) bits[static_cast<size_t>(g) >> 5] |= 1u << (g & 31);
+    }
+    const int64_t cap = loo_capacity(env_batch("REO_TOP_PAIRS_LOO_CAP"));
+    int64_t have = loo_first_records(cap, env_batch("REO_TOP_PAIRS_LOO_FIRST"));
+    DevBuf<int32_t> d_gside, d_oi, d_oj;
+    DevBuf<int64_t> d_D, d_sums, d_on, d_og;
+    DevBuf<int8_t> d_oo;
+    DevBuf<uint32_t> d_bits, d_cand_n;
+    DevBuf<TpRec> d_cand;
+    DevBuf<uint2> d_words;
+    if ((rc = d_gside.ensure(sides.gside.size())) || (rc = d_D.ensure(static_cast<size_t>(c->Gp))) || (rc = d_sums.ensure(2 * static_cast<size_t>(c->Gp))) ||
+        (gene_mask && (rc = d_bits.ensure(bits.size()))) || (rc = d_cand.ensure(static_cast<size_t>(have))) || (rc = d_cand_n.ensure(1)) ||
+        (rc = d_oi.ensure(cells)) || (rc = d_oj.ensure(cells)) || (rc = d_on.ensure(cells)) || (rc = d_og.ensure(cells)) || (rc = d_oo.ensure(cells)) ||
+        (rc = c->sc_slot2col.ensure(map.size())))
+        return rc;
+    TimedPair ev_words, ev_select;   // (reo_get_info 40, 41: what the two kernels cost on the device)
+    if ((rc = ev_words.make()) || (rc = ev_select.make())) return rc;
+    std::vector<int32_t> h_i(cells), h_j(cells);
+    std::vector<int64_t> h_n(cells), h_g(cells);
+    std::vector<int8_t> h_o(cells);
+    uint32_t n_cand = 0;
+    DrainOnExit drain(c);   // the sides and the mask in, the counter and the picks out (declared after the buffers: the wait comes before their release)
+    REO_HIP_CHECK(hipMemcpyAsync(d_gside.p, sides.gside.data(), sides.gside.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    if (gene_mask) REO_HIP_CHECK(hipMemcpyAsync(d_bits.p, bits.data(), bits.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    const uint32_t *maskbits = gene_mask ? d_bits.p : nullptr;
+    if ((rc = upload_slot2col(c, map)) || (rc = launch_rank_shift(c, d_gside.p, sides.s_a, sides.s_b, d_D.p, d_sums.p))) return rc;
+    // step 2: the candidates; the cut sits on the |N| field of the key
+    const TpKey ref{0, static_cast<uint64_t>(cut)};
+    const int shift = kTpGammaBits + 32;
+    REO_HIP_CHECK(hipMemsetAsync(d_cand_n.p, 0, sizeof(uint32_t), c->stream));
+    if ((rc = launch_top_emit(c, d_gside.p, sides.s_a, sides.s_b, d_D.p, maskbits, ref, shift, d_cand.p, have, d_cand_n.p)) ||
+        (rc = copy_back(c, &n_cand, 0, d_cand_n.p, 1)) || (rc = wait_or_drop_table(c)))
+        return rc;
+    size_t free_bytes = 0, total_bytes = 0;
+    REO_HIP_CHECK(hipMemGetInfo(&free_bytes, &total_bytes));
+    if (loo_check_count(n_cand, cut, cap, nblk, static_cast<uint64_t>(free_bytes) + static_cast<uint64_t>(have) * sizeof(TpRec), msg, sizeof msg)) {
+        set_error("%s", msg);
+        return REO_ENOMEM;
+    }
+    if (n_cand > have) {   // the counter ran past the buffer: size it from the counter and emit again
+        uint32_t again = 0;
+        have = n_cand;
+        if ((rc = d_cand.ensure(static_cast<size_t>(have)))) return rc;
+        REO_HIP_CHECK(hipMemsetAsync(d_cand_n.p, 0, sizeof(uint32_t), c->stream));
+        if ((rc = launch_top_emit(c, d_gside.p, sides.s_a, sides.s_b, d_D.p, maskbits, ref, shift, d_cand.p, have, d_cand_n.p)) ||
+            (rc = copy_back(c, &again, 0, d_cand_n.p, 1)) || (rc = wait_or_drop_table(c)))
+            return rc;
+        if (again != n_cand) { set_error("%s: the second emit pass found %u candidates, the first %u; nothing was written", what, again, n_cand); return REO_EHIP; }
+    }
+    // the rows of samples that are no folds, and the picks that a fold does not have
+    REO_HIP_CHECK(hipMemsetAsync(d_oi.p, 0xFF, cells * sizeof(int32_t), c->stream));
+    REO_HIP_CHECK(hipMemsetAsync(d_oj.p, 0xFF, cells * sizeof(int32_t), c->stream));
+    REO_HIP_CHECK(hipMemsetAsync(d_on.p, 0, cells * sizeof(int64_t), c->stream));
+    REO_HIP_CHECK(hipMemsetAsync(d_og.p, 0, cells * sizeof(int64_t), c->stream));
+    REO_HIP_CHECK(hipMemsetAsync(d_oo.p, 0, cells, c->stream));
+    c->top_loo_words_us = 0; c->top_loo_select_us = 0;
+    if (n_cand > 0) {
+        if ((rc = d_words.ensure(static_cast<size_t>(n_cand) * static_cast<size_t>(nblk)))) return rc;
+        if ((rc = ev_words.start(c)) || (rc = launch_loo_words(c, d_cand.p, n_cand, d_words.p)) || (rc = ev_words.stop(c)) ||   // step 3
+            (rc = ev_select.start(c)) ||
+            (rc = launch_loo_select(c, d_cand.p, n_cand, d_words.p, d_gside.p, c->sc_slot2col.p, d_sums.p, sides.s_a, sides.s_b, kmax, d_oi.p, d_oj.p,
+                                    d_on.p, d_og.p, d_oo.p)) ||                                                                   // step 4
+            (rc = ev_select.stop(c)))
+            return rc;
+    }
+    if ((rc = copy_back(c, h_i.data(), 0, d_oi.p, cells)) || (rc = copy_back(c, h_j.data(), 0, d_oj.p, cells)) ||
+        (rc = copy_back(c, h_n.data(), 0, d_on.p, cells)) || (rc = copy_back(c, h_g.data(), 0, d_og.p, cells)) ||
+        (rc = copy_back(c, h_o.data(), 0, d_oo.p, cells)) || (rc = wait_or_drop_table(c)))
+        return rc;
+    drain.dismiss();
+    if (n_cand > 0 && ((rc = ev_words.add_us(&c->top_loo_words_us)) || (rc = ev_select.add_us(&c->top_loo_select_us)))) return rc;
+    for (size_t e = 0; e < cells; ++e)
+        if (h_i[e] != -1 && !(h_i[e] >= 0 && h_i[e] < h_j[e] && h_j[e] < G && h_o[e] >= -1 && h_o[e] <= 1)) {
+            set_error("%s: fold %zu picked the pair (%d, %d) with %d genes; nothing was written", what, e / static_cast<size_t>(kmax), h_i[e], h_j[e], G);
+            return REO_EHIP;
+        }
+    std::copy(h_i.begin(), h_i.end(), gene_i); std::copy(h_j.begin(), h_j.end(), gene_j);
+    std::copy(h_n.begin(), h_n.end(), num); std::copy(h_g.begin(), h_g.end(), rank_num);
+    std::copy(h_o.begin(), h_o.end(), outcome);
+    for (size_t s = 0; s < S; ++s) {
+        const int32_t g = c->group_id[s];
+        side[s] = static_cast<int8_t>((g < 0 || g >= c->ngroups) ? 2 : (sides.gside[static_cast<size_t>(g)] == 0 ? 1 : (sides.gside[static_cast<size_t>(g)] == 1 ? 0 : 2)));
+    }
+    stats[0] = cut; stats[1] = n_cand; stats[2] = passes; stats[3] = static_cast<int64_t>(sides.s_a) + sides.s_b;
     return REO_OK;
 }
 

@@ -345,6 +345,8 @@ struct reo_ctx {
     int64_t top_emit_us = 0;            // reo_get_info 37: microseconds of its emit pass
     int64_t top_null_batch = 0;         // reo_get_info 38: permutations per launch of the last reo_top_pairs_null
     int64_t top_null_us = 0;            // reo_get_info 39: microseconds its launches of k_top_pairs_null took in all (HIP events)
+    int64_t top_loo_words_us = 0;       // reo_get_info 40: microseconds k_loo_words of the last reo_top_pairs_loo took (HIP events)
+    int64_t top_loo_select_us = 0;      // reo_get_info 41: microseconds of its k_loo_select
     reo::DevBuf<int32_t> raw;           // [G][8]
     reo::DevBuf<uint32_t> delta_list;   // [2][Gp] changed genes (gene << 1 | added) per pass parity
     reo::DevBuf<int32_t> cont;          // [G][9]
@@ -492,7 +494,7 @@ int32_t launch_pair_support(reo_ctx *c, const PsItem *d_items, int64_t n_items, 
 // ([capacity] records) and counts them all in d_cand_n ([1], cleared by the caller)
 struct TpKey;
 struct TpRec;
-int32_t launch_rank_shift(reo_ctx *c, const int32_t *d_gside, int s_a, int s_b, int64_t *d_D);
+int32_t launch_rank_shift(reo_ctx *c, const int32_t *d_gside, int s_a, int s_b, int64_t *d_D, int64_t *d_sums = nullptr);   // d_sums: [2][Gp] sum_A, sum_B of lo + hi, or null
 int32_t launch_top_hist(reo_ctx *c, const int32_t *d_gside, int s_a, int s_b, const int64_t *d_D, const uint32_t *d_maskbits, const TpKey &prefix,
                         int shift, unsigned long long *d_hist);
 int32_t launch_top_emit(reo_ctx *c, const int32_t *d_gside, int s_a, int s_b, const int64_t *d_D, const uint32_t *d_maskbits, const TpKey &cut,
@@ -506,6 +508,15 @@ int32_t launch_top_emit(reo_ctx *c, const int32_t *d_gside, int s_a, int s_b, co
 int32_t launch_top_null_words(reo_ctx *c, const uint8_t *d_side, int64_t n_perm, const int32_t *d_slot2col, uint32_t *d_aw, uint32_t *d_live);
 int32_t launch_top_pairs_null(reo_ctx *c, const uint32_t *d_aw, const uint32_t *d_live, int np, int s_a, int s_b, const uint32_t *d_maskbits,
                               const int64_t *cuts, int n_cuts, unsigned long long *d_keys, unsigned long long *d_reach);
+
+// toppairsloo.hip: the kernels of reo_top_pairs_loo (the fold arithmetic, the cut rule and the host checks: top_pairs_loo.h).
+// launch_loo_words: for the n_cand records of d_cand (the emit pass's, on the device) and every block of 32 sample slots the gt word and
+// the eq word of the pair into d_words ([blocks][n_cand]).  launch_loo_select: one workgroup per sample slot decides the fold of that slot
+// from d_cand, d_words and d_sums ([2][Gp] of launch_rank_shift) and stores its kmax picks into row slot2col[slot] of d_i, d_j, d_n, d_g,
+// d_o ([S][kmax], preset by the caller: rows of no fold and picks that do not exist keep what they hold)
+int32_t launch_loo_words(reo_ctx *c, const TpRec *d_cand, int64_t n_cand, uint2 *d_words);
+int32_t launch_loo_select(reo_ctx *c, const TpRec *d_cand, int64_t n_cand, const uint2 *d_words, const int32_t *d_gside, const int32_t *d_slot2col,
+                          const int64_t *d_sums, int s_a, int s_b, int kmax, int32_t *d_i, int32_t *d_j, int64_t *d_n, int64_t *d_g, int8_t *d_o);
 
 // maskedpairs.hip: the kernels of reo_set_valid_mask / reo_build_pairs_masked / reo_pair_counts_masked (shared arithmetic and host checks:
 // masked_pairs.h).  launch_valid_words: c->vmask and d_slot2col ([32 * sample blocks], -1 for padding) into c->vwords (sized by the

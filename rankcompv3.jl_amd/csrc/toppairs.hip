@@ -2,7 +2,8 @@
 // checks: top_pairs.h; entry points: queries.hip).
 //   k_rank_shift     one thread per gene.  It walks the blocks of 32 sample slots of side A and of side B and adds, per block,
 //     sum_k 2^k (popcount(lo plane k) + popcount(hi plane k)) -- the block's sum of lo + hi over its live slots; padding slots are rows of
-//     zeros in both edges (transform.hip) -- and stores D = sum_A S_B - sum_B S_A as int64.  128 bytes per gene and block.
+//     zeros in both edges (transform.hip) -- and stores D = sum_A S_B - sum_B S_A as int64.  128 bytes per gene and block.  With `sums`
+//     it also stores sum_A and sum_B themselves ([2][Gp]; reo_top_pairs_loo forms D of a fold from them); D is the same either way.
 //   k_top_pairs<MODE, NB>   (NB = plane_bits(G) planes: a constant trip count of the chain)  the hot path, in the geometry of k_pairs_masked: a wave owns 64 columns (lane = gene j) and kTpRows rows, four
 //     waves per workgroup take four neighbouring column tiles of the same rows.  Only tiles that touch i < j are walked (tp_tile_live), and
 //     inside a tile on the diagonal the lanes with j <= i are dead.  Side A's groups, then side B's; groups of neither side are skipped
@@ -40,7 +41,7 @@ struct TpArgs {
 
 __global__ __launch_bounds__(256) void k_rank_shift(const uint4 *__restrict__ AL, const uint4 *__restrict__ AH, const int32_t *__restrict__ goff,
                                                     const int32_t *__restrict__ gside, int G, int Gp, int ngroups, int s_a, int s_b,
-                                                    int64_t *__restrict__ D)
+                                                    int64_t *__restrict__ D, int64_t *__restrict__ sums)
 {
     const int gene = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
     if (gene >= Gp) return;
@@ -69,6 +70,7 @@ __global__ __launch_bounds__(256) void k_rank_shift(const uint4 *__restrict__ AL
         }
     }
     D[gene] = tp_shift(sum[0], sum[1], s_a, s_b);   // (genes >= G: 0)
+    if (sums) { sums[gene] = sum[0]; sums[Gp + gene] = sum[1]; }   // (reo_top_pairs_loo: D of a fold needs the two sums apart)
 }
 
 // The counts of one side: gt[r] += popcount(lt), le[r] += popcount(le) of rows i0 + r against column j over the blocks of the side's groups.
@@ -206,12 +208,12 @@ void tp_launch(reo_ctx *c, const int32_t *d_gside, const int64_t *d_D, const uin
 
 }  // namespace
 
-int32_t launch_rank_shift(reo_ctx *c, const int32_t *d_gside, int s_a, int s_b, int64_t *d_D)
+int32_t launch_rank_shift(reo_ctx *c, const int32_t *d_gside, int s_a, int s_b, int64_t *d_D, int64_t *d_sums)
 {
     int32_t rc = tp_need_planes(c, "reo_rank_shift");
     if (rc) return rc;
     k_rank_shift<<<static_cast<unsigned>(c->Gp / 256), 256, 0, c->stream>>>(c->lo.p, c->hi.p, c->goff_dev.p, d_gside, static_cast<int>(c->G), c->Gp,
-                                                                            c->ngroups, s_a, s_b, d_D);
+                                                                            c->ngroups, s_a, s_b, d_D, d_sums);
     REO_HIP_CHECK(hipGetLastError());
     return REO_OK;
 }

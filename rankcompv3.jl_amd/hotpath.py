@@ -15,7 +15,7 @@ from typing import NamedTuple
 import numpy as np
 
 from . import _ffi, synth
-from ._ffi import PairList, PairSupport, PermNull, SampleCalls, SampleCounts, SampleScores, SampleTests, TopPairs, TopPairsNull, class_mask, permuted_labels, permuted_sides  # noqa: F401
+from ._ffi import PairList, PairSupport, PermNull, SampleCalls, SampleCounts, SampleScores, SampleTests, TopPairs, TopPairsLoo, TopPairsNull, class_mask, permuted_labels, permuted_sides  # noqa: F401
 
 HEADER = ["pval", "padj", "n11", "n12", "n13", "n21", "n22", "n23", "n31", "n32", "n33",
           "Δ1", "Δ2", "se", "z1", "up_down"]  # src/RankCompV3.jl:665
@@ -291,6 +291,50 @@ def write_top_pairs_tsv(path, gene_names, top) -> None:
                                str(int(top.n_gt[e, 1])), str(int(top.n_eq[e, 1]))]) + "\n")
 
 
+def top_pairs_loo_plan(top_pairs_loo, *, masked=False, shard=(0, 1)) -> None:
+    """The refusals of `top_pairs_loo`, raised before any context is opened: a kmax outside [1, 64], and the routes that have no search --
+    a validity mask (missing="pairwise" / `valid`) and shard[1] > 1."""
+    if top_pairs_loo is None:
+        return
+
+    def bad(why):
+        return _ffi.DimensionMismatch(_ffi.REO_EINVAL, why)
+    if isinstance(top_pairs_loo, bool) or not isinstance(top_pairs_loo, (int, np.integer)) or not 1 <= int(top_pairs_loo) <= 64:
+        raise bad(f"top_pairs_loo = {top_pairs_loo!r}: None (no cross-validation) or kmax, a number of picks per fold between 1 and 64")
+    if masked:
+        raise bad("top_pairs_loo: the search compares on the whole matrix and would count the fillers under the validity mask; it is not "
+                  "available together with missing=\"pairwise\" or `valid`")
+    if shard[1] > 1:
+        raise bad(f"top_pairs_loo: the search has no sharded form (shard = {tuple(shard)!r})")
+
+
+def deg_top_pairs_loo(ctx, k, treat, top_pairs_loo) -> dict:
+    """{"top_pairs_loo"} of one comparison on `ctx`: the TopPairsLoo (kmax = top_pairs_loo) of group k against the contrast's treatment
+    group, or against every other sample for the reference's comparisons (treat None)."""
+    return {"top_pairs_loo": ctx.top_pairs_loo(int(top_pairs_loo), a=k, b=treat)}
+
+
+def write_top_pairs_cv_tsv(path, loo) -> None:
+    """k, n_folds, n_wrong, n_undecided, error: one line per k = 1 .. kmax of a TopPairsLoo, the error (wrong + undecided) / folds by repr."""
+    e, rate = loo.errors(), loo.error_rate()
+    with open(path, "w") as f:
+        f.write("k\tn_folds\tn_wrong\tn_undecided\terror\n")
+        for k in range(rate.size):
+            f.write(f"{k + 1}\t{int(e['n_folds'][k])}\t{int(e['n_wrong'][k])}\t{int(e['n_undecided'][k])}\t{float(rate[k])!r}\n")
+
+
+def write_top_pairs_loo_tsv(path, sample_names, loo) -> None:
+    """sample, side (A / B), votes_1 .. votes_kmax: one line per fold of a TopPairsLoo in the samples' own order; the samples of neither
+    side are no folds and have no line."""
+    votes = loo.votes()
+    with open(path, "w") as f:
+        f.write("\t".join(["sample", "side"] + [f"votes_{k + 1}" for k in range(votes.shape[1])]) + "\n")
+        for s in range(votes.shape[0]):
+            if int(loo.side[s]) == 2:
+                continue
+            f.write("\t".join([str(sample_names[s]), "A" if int(loo.side[s]) == 1 else "B"] + [str(int(v)) for v in votes[s]]) + "\n")
+
+
 def top_pairs_null_plan(top_pairs, top_pairs_permutations) -> None:
     """The refusals of `top_pairs_permutations`, raised before any context is opened (ValueError): given without `top_pairs`, or no number
     of permutations between 1 and 2^20."""
@@ -376,7 +420,8 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
                       seed: int = 0, device: int = -1, shard=(0, 1), allreduce=None, allgather=None, profile: bool = False,
                       pairs=None, sample_scores: bool = False, pair_support: bool = False, contrasts=None,
                       sample_tests: bool = False, sample_calls: bool = False, missing=None, valid=None, min_complete=None,
-                      permutations=None, perm_seed: int = 0, perm_strata=None, top_pairs=None, top_pairs_permutations=None) -> DegRun:
+                      permutations=None, perm_seed: int = 0, perm_strata=None, top_pairs=None, top_pairs_permutations=None,
+                      top_pairs_loo=None) -> DegRun:
     """identify_degs with the extras (trace, timings) kept.  `data` is a host matrix (numpy, anything np.asarray takes) or a torch
     tensor on a ROCm device, which is used in place (_ffi.device_matrix).  A column-major host matrix is read in place; a row-major one
     (numpy's default C order, column slices of a wider C-ordered array) is copied column-major on the host first, or, with REO_ROWMAJOR=1
@@ -434,13 +479,18 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
     the TopPairsNull of B label shuffles of the search's two sides (Context.top_pairs_null; rows from permuted_sides with seed
     perm_seed + k, shuffled within perm_strata when given; cuts: |N| of the list's entries 1, 10, 100 and K) -- .p_max(top_pairs) is the
     single-step maxT adjusted p-value of every listed pair.  Works for the reference's comparisons and for contrasts.  Without `top_pairs`:
-    ValueError.  None (the default): no further call, no new key."""
+    ValueError.  None (the default): no further call, no new key.
+    `top_pairs_loo` (not in the reference): an int kmax adds "top_pairs_loo" to every comparison dict, the TopPairsLoo of the
+    leave-one-out cross-validation of the k-TSP selection (Context.top_pairs_loo) with the sides of `top_pairs` -- the comparison's group
+    against the contrast's treatment group or every other sample; independent of `top_pairs`.  Refused with a mask and with shard[1] > 1
+    (top_pairs_loo_plan).  None (the default): no further call, no new key."""
     need_pairs_for_support(pairs, pair_support)
     data, mask = missing_plan(data, missing, valid, shard=shard, contrasts=contrasts, sample_scores=sample_scores, sample_tests=sample_tests,
                               sample_calls=sample_calls, pair_support=pair_support)
     perm_plan(permutations, contrasts=contrasts, masked=mask is not None, shard=shard)
     top_pairs_plan(top_pairs, masked=mask is not None, shard=shard)
     top_pairs_null_plan(top_pairs, top_pairs_permutations)
+    top_pairs_loo_plan(top_pairs_loo, masked=mask is not None, shard=shard)
     if mask is not None:
         _ffi.resolve_min_complete(min_complete, (1, 1), pval_reo)   # (its refusals, before a context is opened)
     # a torch tensor on a ROCm device: a strided one is used where it is, a sparse one is made dense there (its device is the context's)
@@ -503,6 +553,8 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
                 comps[-1].update(deg_top_pairs(ctx, k, treat, top_pairs))
                 if top_pairs_permutations is not None:
                     comps[-1].update(deg_top_pairs_null(ctx, gid, k, treat, comps[-1]["top_pairs"], top_pairs_permutations, perm_seed, perm_strata))
+            if top_pairs_loo is not None:
+                comps[-1].update(deg_top_pairs_loo(ctx, k, treat, top_pairs_loo))
             if permutations is not None:   # last: it uses the iteration's buffers (ref_mask is refused behind it)
                 comps[-1].update(deg_perm_null(ctx, gid, k, permutations, perm_seed, perm_strata, pval_deg, padj_deg))
         timings = ctx.timings() if profile else {}
@@ -546,7 +598,7 @@ def identify_degs_cells(cells, cell_group, gene_names, n_pseudo, pval_reo, pval_
                         profile: bool = False, pairs=None, sample_scores: bool = False, pair_support: bool = False,
                         contrasts=None, sample_tests: bool = False, sample_calls: bool = False,
                         permutations=None, perm_seed: int = 0, perm_strata=None, top_pairs=None,
-                        top_pairs_permutations=None) -> CellsDegRun:
+                        top_pairs_permutations=None, top_pairs_loo=None) -> CellsDegRun:
     """Cells to DEGs without a host trip for the profiles: `cells` is a genes x cells matrix (scipy.sparse, anything np.asarray takes, or
     a torch tensor on a ROCm device -- sparse or strided -- which is read where it is: reo_set_matrix_pseudobulk_*_dev_*),
     cell_group one label per cell.  cells_partition -> the pseudo-bulk sums written into the context's matrix (set_matrix_pseudobulk) ->
@@ -558,11 +610,12 @@ def identify_degs_cells(cells, cell_group, gene_names, n_pseudo, pval_reo, pval_
     the kept profiles.  `contrasts`: as in run_identify_degs, over the group levels of the cells (checked against the levels of cell_group
     before any context is opened, and again against those of the kept profiles).  `permutations`, `perm_seed`, `perm_strata`: as in
     run_identify_degs; perm_strata has one label per pseudo-bulk PROFILE of cells_partition (the kept ones are used).  `top_pairs`,
-    `top_pairs_permutations`: as in run_identify_degs."""
+    `top_pairs_permutations`, `top_pairs_loo`: as in run_identify_degs."""
     need_pairs_for_support(pairs, pair_support)
     perm_plan(permutations, contrasts=contrasts)
     top_pairs_plan(top_pairs)
     top_pairs_null_plan(top_pairs, top_pairs_permutations)
+    top_pairs_loo_plan(top_pairs_loo)
     on_device = _ffi.is_device_sparse(cells) or _ffi.is_device_tensor(cells)
     if on_device:   # a torch tensor on a ROCm device, sparse or strided: summed where it is, on its own device
         device = cells.device.index if cells.device.index is not None else -1
@@ -615,6 +668,8 @@ def identify_degs_cells(cells, cell_group, gene_names, n_pseudo, pval_reo, pval_
                 if top_pairs_permutations is not None:
                     strata = None if perm_strata is None else np.asarray(perm_strata)[np.asarray(profile_kept, dtype=bool)]
                     comps[-1].update(deg_top_pairs_null(ctx, gid, k, treat, comps[-1]["top_pairs"], top_pairs_permutations, perm_seed, strata))
+            if top_pairs_loo is not None:
+                comps[-1].update(deg_top_pairs_loo(ctx, k, treat, top_pairs_loo))
             if permutations is not None:   # last: it uses the iteration's buffers (ref_mask is refused behind it)
                 strata = None if perm_strata is None else np.asarray(perm_strata)[np.asarray(profile_kept, dtype=bool)]
                 comps[-1].update(deg_perm_null(ctx, gid, k, permutations, perm_seed, strata, pval_deg, padj_deg))
