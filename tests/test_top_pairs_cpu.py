@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import top_pairs_cases as tpc
+import wide_top_pairs_cases as wt
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -57,8 +58,9 @@ def test_key_tiles_digit_pick_pass_loop_and_argument_checks_under_sanitizers(dri
 
 
 def run_select(driver, name, n, cap, gene_mask=None):
-    X, gid, ng, a, b = tpc.case(name)
-    exp = tpc.expected(name) if gene_mask is None else tpc.oracle(X, gid, ng, a, b, gene_mask)
+    cases = wt if name in wt.DEEP else tpc                                       # (deep_gamma, limit: tests/wide_top_pairs_cases.py)
+    X, gid, ng, a, b = cases.case(name)
+    exp = cases.expected(name) if gene_mask is None else tpc.oracle(X, gid, ng, a, b, gene_mask)
     G = X.shape[0]
     n_max = 2 * exp.sizes[0] * exp.sizes[1]
     g_max = int(exp.D.max() - exp.D.min())
@@ -73,17 +75,26 @@ def run_select(driver, name, n, cap, gene_mask=None):
     return passes, cand
 
 
-@pytest.mark.parametrize("name", tpc.EQUALITY)
+@pytest.mark.parametrize("name", tpc.EQUALITY + list(wt.DEEP))
 def test_the_pass_loop_selects_the_oracles_order_at_any_capacity(driver, name):
     """the library's own pass loop, a host histogram in place of the kernel: the oracle's first 50 pairs, at the default capacity and at
-    capacity = n; the tight buffer needs more passes wherever more than 50 keys share the first digit's bin"""
-    exp = tpc.expected(name)
+    capacity = n; the tight buffer needs more passes wherever more than 50 keys share the first digit's bin.  deep_gamma and limit: Gamma
+    at and above 2^32, whose upper bits tp_pack puts into TpKey.hi, decides among hundreds of pairs at |N| = 2 S_A S_B, and at the
+    limit |N| has the top bit of its field set"""
+    exp = wt.expected(name) if name in wt.DEEP else tpc.expected(name)
     assert np.array_equal(exp.N, -exp.N.T)                                        # N is antisymmetric
     p_default, c_default = run_select(driver, name, 50, 0)
     p_tight, c_tight = run_select(driver, name, 50, 50)
     assert 1 <= p_default <= p_tight <= 10 and 50 <= c_tight <= c_default <= exp.gene_i.size
-    if name in ("separated", "level"):
+    G = (wt if name in wt.DEEP else tpc).case(name)[0].shape[0]                   # the numpy restatement of the loop counts the same
+    assert wt.select_passes(exp, G, 50, wt.default_capacity(50)) == (p_default, c_default) and wt.select_passes(exp, G, 50, 50) == (p_tight, c_tight)
+    if name in ("separated", "level") or name in wt.DEEP:
         assert p_tight > p_default
+    if name in wt.DEEP:                                                          # the tight run refines through digits of Gamma that lie in TpKey.hi
+        head = exp.rank_num[:50]
+        assert np.unique(head >> 32).size >= 2 and (np.abs(exp.num[:51]) == 2 * exp.sizes[0] * exp.sizes[1]).all() and p_tight >= 4
+        if name == "limit":
+            assert abs(int(exp.num[0])) >> 30 == 1 and int(head.max()) >> 37 == 1
     if name == "level":
         assert run_select(driver, name, 5000, 0)[1] == 4950                       # fewer pairs than wanted: all of them
 
