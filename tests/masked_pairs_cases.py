@@ -138,12 +138,20 @@ def count_case(G, sizes, frac, seed, dtype=np.int64):
     return X, random_mask(rng, G, S, frac), gid
 
 
-def rank_case(G, sizes, frac, seed):
-    """tie-free: every sample a permutation of 0, 10, 20, ... (Float64)"""
+def rank_case(G, sizes, frac, seed, level=0.0, shift=0.0, planted=0):
+    """tie-free: every sample a permutation of 0, 10, 20, ... (Float64).  level > 0: the permutations are the ranks of unit noise around
+    gene levels of that spread, with the planted effects of float_case, so that stable and reversed pairs occur (level = 0: pure noise)"""
     rng = np.random.default_rng(seed)
     gid = interleaved(*sizes)
     S = int(gid.size)
-    X = np.stack([rng.permutation(G) for _ in range(S)], axis=1).astype(np.float64) * 10.0
+    if level > 0.0:
+        v = rng.normal(0.0, 1.0, size=(G, S)) + level * rng.normal(0.0, 1.0, size=(G, 1))
+        v[4: 4 + planted, gid == 1] += shift
+        v[4 + planted: 4 + 2 * planted, gid == 1] -= shift
+        X = np.empty((G, S), dtype=np.float64)
+        np.put_along_axis(X, np.argsort(v, axis=0, kind="stable"), 10.0 * np.arange(G, dtype=np.float64)[:, None], axis=0)
+    else:
+        X = np.stack([rng.permutation(G) for _ in range(S)], axis=1).astype(np.float64) * 10.0
     return X, random_mask(rng, G, S, frac), gid
 
 

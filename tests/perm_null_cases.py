@@ -71,15 +71,15 @@ def pack_words(rows, gid, ngroups):
     return aw, live
 
 
-def case(G, sizes, kind, seed, dtype=np.float64):
+def case(G, sizes, kind, seed, dtype=np.float64, **kw):
     """X (Fortran order), gid: `ties` = Float64 rounded to two decimals (ties inside the 0.1 band on both sides), `ranks` = every sample a
-    permutation (tie-free), `counts` = small counts with equality ties in `dtype`"""
+    permutation (tie-free), `counts` = small counts with equality ties in `dtype`; further keywords go to the generator"""
     if kind == "ranks":
-        X, _, gid = mpc.rank_case(G, sizes, 0.0, seed)
+        X, _, gid = mpc.rank_case(G, sizes, 0.0, seed, **kw)
     elif kind == "counts":
         X, _, gid = mpc.count_case(G, sizes, 0.0, seed, dtype=dtype)
     else:
-        X, _, gid = mpc.float_case(G, sizes, 0.0, seed)
+        X, _, gid = mpc.float_case(G, sizes, 0.0, seed, **kw)
         X = X.astype(dtype)
     return np.asfortranarray(X), gid
 

@@ -74,3 +74,15 @@ def expected_counts(X: np.ndarray, codes_of_row, genes, class_mask: int, partner
     sel = np.stack([selection(codes_of_row(int(i)), class_mask, partner_mask) for i in genes])
     assert not sel[np.arange(genes.size), genes].any()
     return counts_of(gt, eq, sel)
+
+
+def plane_case_data(G, marks, seed, X=None, S=8):
+    """the matrix and partner mask of the plane-layout cases (tests/test_gpu_sample_counts.py, plane_case): Int64 below 30 000, Fortran
+    order, unless X is given; 1 000 random partners and `marks`"""
+    rng = np.random.default_rng(seed)
+    if X is None:
+        X = np.asfortranarray(rng.integers(0, 30000, size=(G, S)).astype(np.int64))
+    pm = np.zeros(G, dtype=bool)
+    pm[rng.choice(G, 1000, replace=False)] = True
+    pm[list(marks)] = True
+    return X, pm

@@ -35,17 +35,21 @@ class Relabelled:
     def __init__(self, pkg, seed):
         self.ctx = pkg.Context(device=0, seed=seed)
 
-    def codes(self, X, row):
+    def build(self, X, row, pval_reo=0.01):
         X2, gid2 = pnc.relabelled(X, row)
         self.ctx.set_groups(gid2, 2)
-        self.ctx.compute_thresholds(0.01)
+        self.ctx.compute_thresholds(pval_reo)
         self.ctx.set_matrix(X2)
         self.ctx.build_pairs(0)
+
+    def codes(self, X, row, rect=None):
+        """the whole table, or the rectangle (i0, i1, j0, j1) of it"""
+        self.build(X, row)
         G = X.shape[0]
-        return self.ctx.get_codes(0, G, 0, G)
+        return self.ctx.get_codes(*(rect if rect is not None else (0, G, 0, G)))
 
     def one_pass(self, X, row, ref, pval_deg=PVAL_DEG, padj_deg=PADJ_DEG):
-        self.codes(X, row)
+        self.build(X, row)
         return self.ctx.identify_degs(ref, pval_deg, padj_deg, 1, 0)[0]
 
     def close(self):
@@ -115,12 +119,16 @@ def planted(G, sizes, seed, kind="ties"):
     return X, gid
 
 
-def check_null_against_relabelled(pkg, rel, X, gid, seed, k, rows, ref):
+def check_null_against_relabelled(pkg, rel, X, gid, seed, k, rows, ref, keep=None):
+    """keep: a rectangle (i0, i1, j0, j1) of the resident table that is read before the call and must read the same after it"""
     G = X.shape[0]
     r = rel(seed)
     with open_ctx(pkg, X, gid, seed, build_k=k) as ctx:
+        before = ctx.get_codes(*keep) if keep is not None else None
         pn = ctx.permutation_null(rows, k=k, ref_mask=ref, pval_deg=PVAL_DEG, padj_deg=PADJ_DEG, keep_null=True)
         info = ctx.info()
+        if keep is not None:
+            assert np.array_equal(ctx.get_codes(*keep), before), "the resident table changed under reo_perm_null"
     assert pn.delta1_null.shape == (rows.shape[0], G)
     called = 0
     for p, row in enumerate(rows):

@@ -112,22 +112,27 @@ def test_batch_seam(pkg, monkeypatch):
         cc.bitwise(ctx.sample_calls(1.0, 0.2, q, pm), ref)
 
 
-def test_17_plane_layout(pkg):
-    """G = 66 000, S = 8, the six queries of the sample tests' case: the other plane layout behind the same calls"""
-    G, S, seed = 66000, 8, 61
+def plane_case(pkg, G, q, marks, seed, tag):
+    """the case of the sample tests' plane_case (tests/test_gpu_sample_tests.py): S = 8, the same matrix, queries and mask"""
+    S = 8
     rng = np.random.default_rng(seed)
     X = (rng.integers(0, 30000, size=(G, 1)) + rng.integers(0, 6000, size=(G, S))).astype(np.int64)
     X[:20000, 1::2] += 9000
     X = np.asfortranarray(X)
     labels = np.array(["a", "b"] * (S // 2), dtype=object)
-    q = np.array([65999, 0, 40000, 65535, 65536, 7], dtype=np.int32)
+    q = np.asarray(q, dtype=np.int32)
     pm = np.zeros(G, dtype=bool)
     pm[rng.choice(G, 194, replace=False)] = True
-    pm[[0, 4095, 4096, 65535, 65536, 65999]] = True
+    pm[list(marks)] = True
     with cc.open_ctx(pkg, X, labels, pval_reo=0.3) as ctx:
-        got, st, calls, cut = check(ctx, q, pm, 1.0, 0.2, "17 planes")
+        got, st, calls, cut = check(ctx, q, pm, 1.0, 0.2, tag)
         assert (calls != 0).any()
-        check(ctx, q, pm, 0.05, 1.0, "17 planes, pval_deg", st)
+        check(ctx, q, pm, 0.05, 1.0, tag + ", pval_deg", st)
+
+
+def test_17_plane_layout(pkg):
+    """G = 66 000, S = 8, the six queries of the sample tests' case: the other plane layout behind the same calls"""
+    plane_case(pkg, 66000, [65999, 0, 40000, 65535, 65536, 7], [0, 4095, 4096, 65535, 65536, 65999], 61, "17 planes")
 
 
 @pytest.mark.parametrize("k,treat", [(2, None), (1, 2)])

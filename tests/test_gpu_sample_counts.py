@@ -248,21 +248,24 @@ def test_after_a_slot_order_build_the_gene_order_planes_are_intact(pkg):
             assert (got.n_eq == 0).all()
 
 
-def test_17_plane_layout(pkg):
-    """G = 65 600: five pos quads, edge rows of eight uint4, plane k in word k; partners either side of 65 536"""
-    G, S, seed = 65600, 8, 61
-    rng = np.random.default_rng(seed)
-    X = np.asfortranarray(rng.integers(0, 30000, size=(G, S)).astype(np.int64))
+def plane_case(pkg, G, q, marks, seed, X=None):
+    """S = 8, labels a b a b ..., class 0x1FF under a mask of `marks` and 1 000 random partners; X: Int64 below 30 000 (ties by equality)
+    unless given, and a given matrix is tie-free"""
+    S = 8
+    tie_free = X is not None
+    X, pm = scc.plane_case_data(G, marks, seed, X, S)
     labels = np.array(["a", "b"] * (S // 2), dtype=object)
-    q = np.array([65599, 0, 40000], dtype=np.int32)
-    pm = np.zeros(G, dtype=bool)
-    pm[rng.choice(G, 1000, replace=False)] = True
-    pm[[0, 4095, 4096, 65535, 65536, 65599]] = True
+    q = np.asarray(q, dtype=np.int32)
     with open_ctx(pkg, X, labels, pval_reo=0.3) as ctx:
         got, exp = check(ctx, X, q, ALL, pm, pkg)
-        assert got.n_sel.tolist() == [int(pm.sum()) - 1, int(pm.sum()) - 1, int(pm.sum()) - int(pm[40000])]
-        assert exp[1].sum() > 0 and exp[2].sum() > 0
+        assert got.n_sel.tolist() == [int(pm.sum()) - int(pm[i]) for i in q]
+        assert exp[1].sum() > 0 and (exp[2].sum() == 0 if tie_free else exp[2].sum() > 0)
         check(ctx, X, q, ALL, pm, pkg, ties=False)
+
+
+def test_17_plane_layout(pkg):
+    """G = 65 600: five pos quads, edge rows of eight uint4, plane k in word k; partners either side of 65 536"""
+    plane_case(pkg, 65600, [65599, 0, 40000], [0, 4095, 4096, 65535, 65536, 65599], 61)
 
 
 def test_after_a_real_identify_degs(pkg):

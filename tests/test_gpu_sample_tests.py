@@ -155,22 +155,28 @@ def test_tile_seam_and_batch_seam(pkg, monkeypatch):
         bitwise(ctx.sample_tests(q16, np.ones(G, dtype=bool)), dense)
 
 
-def test_17_plane_layout(pkg):
-    """G = 66 000: five pos quads, edge rows of eight uint4; partners either side of 65 536; the log-factorial table has 131 999 entries.
-    A mask of about 200 partners keeps the exact tails cheap."""
-    G, S, seed = 66000, 8, 61
+def plane_case(pkg, G, q, marks, seed, tag):
+    """S = 8, labels a b a b ..., Int64 gene levels with the first 20 000 genes up in b; a mask of `marks` and 194 random partners keeps
+    the exact tails cheap"""
+    S = 8
     rng = np.random.default_rng(seed)
     X = (rng.integers(0, 30000, size=(G, 1)) + rng.integers(0, 6000, size=(G, S))).astype(np.int64)
     X[:20000, 1::2] += 9000
     X = np.asfortranarray(X)
     labels = np.array(["a", "b"] * (S // 2), dtype=object)
-    q = np.array([65999, 0, 40000, 65535, 65536, 7], dtype=np.int32)
+    q = np.asarray(q, dtype=np.int32)
     pm = np.zeros(G, dtype=bool)
     pm[rng.choice(G, 194, replace=False)] = True
-    pm[[0, 4095, 4096, 65535, 65536, 65999]] = True
+    pm[list(marks)] = True
     with open_ctx(pkg, X, labels, pval_reo=0.3) as ctx:
-        got, exp = check(ctx, X, q, pm, pkg, tag="17 planes")
+        got, exp = check(ctx, X, q, pm, pkg, tag=tag)
         assert int((got.n_above_ctrl + got.n_below_ctrl).max()) > 100 and exp["u"].max() > 50 and exp["d"].max() > 50
+
+
+def test_17_plane_layout(pkg):
+    """G = 66 000: five pos quads, edge rows of eight uint4; partners either side of 65 536; the log-factorial table has 131 999 entries.
+    A mask of about 200 partners keeps the exact tails cheap."""
+    plane_case(pkg, 66000, [65999, 0, 40000, 65535, 65536, 7], [0, 4095, 4096, 65535, 65536, 65999], 61, "17 planes")
 
 
 @pytest.mark.parametrize("k,treat", [(0, None), (2, None), (1, 2)])
