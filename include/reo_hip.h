@@ -499,6 +499,39 @@ int32_t reo_top_pairs_loo(reo_ctx *ctx, int32_t a, int32_t b /* -1: every other 
                           int64_t *num /* [S][kmax]: N(s), signed */, int64_t *rank_num /* [S][kmax]: Gamma(s) */,
                           int8_t *outcome /* [S][kmax]: -1 / 0 / +1 */, int8_t *side /* [S] */, int64_t *stats /* [4] */);
 
+/* Top partners: the best partner genes of given genes.  reo_top_pairs answers "which pairs, out of all"; a user who holds a gene -- a DEG of
+ * reo_identify_degs, the genes of a marker panel, or every gene for a gene-level ranking that needs no normalisation -- asks "which single
+ * partner makes the best two-gene rule with THIS gene, and how good is that rule".  The reference has no such output.
+ * Sides A and B, the four counts per side, N, D and Gamma are exactly those of reo_top_pairs(a, b).  For a query gene q = genes[r] and a
+ * partner p != q with partner_mask[p] != 0 (NULL: every gene; q itself need not be inside the mask): the counts are those of "q above p",
+ * N_qp is signed (N_pq = -N_qp), Gamma_qp = |D_q - D_p| with D over all genes, independent of the mask (reo_rank_shift).  Row r lists the
+ * partners in the order |N| descending, Gamma descending, p ascending -- a total order; it is the subsequence of reo_top_pairs' total order
+ * over all pairs that contain q (csrc/top_partners.h has the argument).  The call returns the first m_want partners of every row:
+ * partner[r m_want + e] (-1 beyond n_found[r]), counts[4 (r m_want + e) ..] = gt_A, eq_A, gt_B, eq_B of "q above p", key[2 (r m_want + e)]
+ * = N (signed), key[.. + 1] = Gamma (counts and key 0 beyond n_found[r]), n_found[r] = min(m_want, eligible partners).  Query genes may
+ * repeat and come in any order: every row is decided on its own.  The result is exact and does not depend on the launch geometry, on the
+ * batch size or on the arrival order of anything.  (partner, n_found) is the row-shaped input (genes, rowptr, partner) of reo_pair_support.
+ * Needs the matrix, the groups and the transform (run here if need be); no class table, no thresholds, no reference set.  Reads and writes
+ * none of the iteration's buffers: the resident table, reo_get_ref_mask and a following reo_identify_degs behave as if the call had not
+ * happened.  Host arrays only, allocated by the caller; no stage timer of its own.
+ * The route (csrc/toppartners.hip, csrc/top_partners.h): k_top_partners_count walks the bit planes as the search's kernel does, with the
+ * query genes as its rows and every column as a partner, and stores one 8-byte cell of four unsigned 16-bit counts per (row, column);
+ * k_top_partners_select, one workgroup per row, runs m_want rounds over the row's cells, each taking the best key strictly behind the
+ * previous round's.  The rows go in batches whose cells and outputs stay within 256 MiB of device memory and within what is free
+ * (REO_TOP_PARTNERS_BATCH=n in the environment, read per call, lowers the rows per batch: tests of the seam).  reo_get_info 42 and 43 =
+ * the microseconds of the count launches and of the select launches of the last call (HIP events); no other info entry is touched.
+ * REO_EINVAL, each with its own message, checked on the host before anything is uploaded, and a refused call writes nothing: everything
+ * reo_top_pairs refuses of the context and of a, b (a reo_create_multi context; a sharded context; a validity mask set; G or S above
+ * 65535; a or b outside the groups; b == a); n_genes outside [1, 2^20]; m_want outside [1, 1024]; n_genes * m_want above 2^26; a NULL
+ * genes or output; a query gene outside [0, G) (the message names the row); a partner_mask byte other than 0 or 1. */
+int32_t reo_top_partners(reo_ctx *ctx, int32_t a, int32_t b /* -1: every other sample */,
+                         const int32_t *genes, int64_t n_genes /* query genes, any order, repeats allowed */,
+                         const uint8_t *partner_mask /* G bytes 0/1, or NULL */, int32_t m_want,
+                         int32_t *partner /* [n_genes][m_want], -1 beyond n_found */,
+                         int32_t *counts /* [n_genes][m_want][4]: gt_A, eq_A, gt_B, eq_B of (query above partner), 0 beyond */,
+                         int64_t *key /* [n_genes][m_want][2]: N (signed, query against partner), Gamma, 0 beyond */,
+                         int32_t *n_found /* [n_genes]: min(m_want, eligible partners) */);
+
 /* Missing values: pair classes from the samples where BOTH genes were observed.  The reference drops every gene with a missing cell
  * (dropmissing!, src/RankCompV3.jl:601) and the library refuses a NaN; with a validity mask V beside the resident matrix a pair (i, j) is
  * compared in the samples where both values exist, and its stability is judged against the threshold of that many samples.
@@ -811,7 +844,8 @@ int32_t reo_get_timings(reo_ctx *ctx, double *ms, int32_t n);
  * kernel took in all (HIP events around each launch), 36 and 37 the microseconds of the histogram passes and of the emit pass of the
  * last reo_top_pairs, 38 the permutations per launch of the last reo_top_pairs_null, 39 the microseconds that its launches of the null
  * kernel took in all (HIP events around each launch), 40 and 41 the microseconds of k_loo_words and of k_loo_select of the last
- * reo_top_pairs_loo. */
+ * reo_top_pairs_loo, 42 and 43 the microseconds of the launches of k_top_partners_count and of k_top_partners_select of the last
+ * reo_top_partners. */
 int32_t reo_get_info(reo_ctx *ctx, int64_t *info, int32_t n);
 
 #ifdef __cplusplus

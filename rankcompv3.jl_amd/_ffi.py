@@ -36,6 +36,7 @@ SYMBOLS = [
     "reo_filter_matrix", "reo_get_matrix", "reo_get_ref_mask", "reo_pair_list", "reo_sample_counts", "reo_pair_support",
     "reo_sample_tests", "reo_sample_calls", "reo_set_valid_mask", "reo_build_pairs_masked", "reo_pair_counts_masked",
     "reo_perm_null", "reo_perm_codes", "reo_rank_shift", "reo_top_pairs", "reo_top_pairs_null", "reo_top_pairs_loo",
+    "reo_top_partners",
 ] +[f"reo_set_matrix_{form}_{t}" for form in ("csc_dev", "pseudobulk_csc_dev", "pseudobulk_dense_dev") for t in ("f64", "i64", "f32", "i32")]
 
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p)
@@ -154,6 +155,7 @@ def lib() -> ctypes.CDLL:
         "reo_top_pairs": (i32, [vp, i32, i32, vp, i64, vp, vp, vp, vp, vp, vp]),
         "reo_top_pairs_null": (i32, [vp, i32, i32, vp, i64, vp, vp, i32, vp, vp, vp, vp]),
         "reo_top_pairs_loo": (i32, [vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+        "reo_top_partners": (i32, [vp, i32, i32, vp, i64, vp, i32, vp, vp, vp, vp]),
     }
     for t in ("f64", "i64", "f32", "i32"):   # SPARSE ON THE DEVICE
         sig["reo_set_matrix_csc_dev_" + t] = (i32, [vp, i64, i64, i64, vp, vp, i32, vp])
@@ -511,6 +513,76 @@ class TopPairs(NamedTuple):
         if out.shape[0] != self.gene_i.size:
             raise DimensionMismatch(REO_EINVAL, f"votes: the support lists {out.shape[0]} pairs, this object {self.gene_i.size}")
         return (self.direction.astype(np.int32)[:, None] * (out.astype(np.int32) - 1)).sum(axis=0, dtype=np.int64).astype(np.int32)
+
+
+class TopPartners(NamedTuple):
+    """reo_top_partners: per query gene (row) its best m partner genes for side A (group a) against side B (group b, or every other sample
+    for b None), in the order |num| descending, rank_num descending, partner ascending -- the subsequence of TopPairs' order over the pairs
+    that contain the gene.  Per cell and side, n_gt = samples with the QUERY gene above the partner and not tied, n_eq = tied samples; num
+    = N of (query, partner), signed: positive where the query lies above the partner more often in A than in B.  Cells beyond n_found of a
+    row are padding: partner -1, everything else 0."""
+    genes: np.ndarray        # int32, Q: the query genes
+    partner: np.ndarray      # int32, Q x m
+    n_gt: np.ndarray         # int32, Q x m x 2: side A, side B
+    n_eq: np.ndarray         # int32, Q x m x 2
+    num: np.ndarray          # int64, Q x m, N (signed)
+    rank_num: np.ndarray     # int64, Q x m, Gamma
+    n_found: np.ndarray      # int32, Q
+    side_sizes: np.ndarray   # int64, 2: S_A, S_B
+    a: int
+    b: int | None
+
+    @property
+    def score(self) -> np.ndarray:
+        """|num| / (2 S_A S_B), float64 in [0, 1], Q x m; 0 in padded cells."""
+        return np.abs(self.num).astype(np.float64) / (2.0 * float(self.side_sizes[0]) * float(self.side_sizes[1]))
+
+    @property
+    def rank_score(self) -> np.ndarray:
+        """rank_num / (2 S_A S_B), float64, Q x m; 0 in padded cells."""
+        return self.rank_num.astype(np.float64) / (2.0 * float(self.side_sizes[0]) * float(self.side_sizes[1]))
+
+    @property
+    def direction(self) -> np.ndarray:
+        """int8, Q x m: +1 where the query gene lies above the partner more often in A than in B, -1 the other way, 0 at num = 0 and in
+        padded cells."""
+        return np.sign(self.num).astype(np.int8)
+
+    def best(self):
+        """(partner, score) per row: the first partner (int32) and its score (float64); -1 / 0.0 where a row found none.  With all genes as
+        queries: the best pair score every gene can reach."""
+        if self.partner.shape[1] == 0:
+            return np.full(self.genes.size, -1, dtype=np.int32), np.zeros(self.genes.size, dtype=np.float64)
+        none = self.n_found == 0
+        return np.where(none, -1, self.partner[:, 0]).astype(np.int32), np.where(none, 0.0, self.score[:, 0])
+
+    def csr(self):
+        """The (genes, rowptr, partner) triple that Context.pair_support takes: one row per query gene with its found partners in order,
+        the padding dropped."""
+        rowptr = np.zeros(self.genes.size + 1, dtype=np.int64)
+        np.cumsum(self.n_found, out=rowptr[1:])
+        keep = np.arange(self.partner.shape[1])[None, :] < self.n_found[:, None]
+        return self.genes.astype(np.int32), rowptr, self.partner[keep].astype(np.int32)
+
+    def pairs(self) -> TopPairs:
+        """The distinct unordered pairs of the table as a TopPairs (passes = 0): re-oriented to gene_i < gene_j -- where the query is the
+        larger gene, n_gt becomes S_side - n_gt - n_eq and num changes its sign -- and sorted in TopPairs' order, so that disjoint, csr
+        and votes work on it unchanged."""
+        keep = np.arange(self.partner.shape[1])[None, :] < self.n_found[:, None]
+        q = np.broadcast_to(self.genes[:, None], self.partner.shape)[keep].astype(np.int64)
+        p = self.partner[keep].astype(np.int64)
+        gt, eq = self.n_gt[keep].astype(np.int64), self.n_eq[keep].astype(np.int64)
+        num, gam = self.num[keep].astype(np.int64), self.rank_num[keep].astype(np.int64)
+        flip = q > p
+        gt = np.where(flip[:, None], self.side_sizes[None, :] - gt - eq, gt)
+        num = np.where(flip, -num, num)
+        gi, gj = np.minimum(q, p), np.maximum(q, p)
+        order = np.lexsort((gj, gi, -gam, -np.abs(num)))                         # (the last key is the primary one)
+        first = np.ones(order.size, dtype=bool)
+        first[1:] = (gi[order][1:] != gi[order][:-1]) | (gj[order][1:] != gj[order][:-1])   # (the two listings of a pair share every key)
+        order = order[first]
+        return TopPairs(gi[order].astype(np.int32), gj[order].astype(np.int32), gt[order].astype(np.int32).reshape(-1, 2),
+                        eq[order].astype(np.int32).reshape(-1, 2), num[order], gam[order], self.side_sizes, self.a, self.b, 0)
 
 
 class TopPairsNull(NamedTuple):
@@ -1083,8 +1155,8 @@ class Context:
     def set_valid_mask(self, valid) -> None:
         """reo_set_valid_mask: a G x S validity mask (nonzero / True = observed) beside the resident matrix, in the caller's column
         order; None clears it.  The cell under an invalid entry is ignored by build_pairs_masked but must still be a number (NaN stays
-        refused).  While a mask is set, sample_counts, sample_tests, sample_calls, pair_support, rank_shift, top_pairs and build_contrast are
-        refused."""
+        refused).  While a mask is set, sample_counts, sample_tests, sample_calls, pair_support, rank_shift, top_pairs, top_partners and
+        build_contrast are refused."""
         if valid is None:
             check(self._L.reo_set_valid_mask(self._h, None, 0, 0, 0))
             return
@@ -1343,6 +1415,30 @@ class Context:
         return TopPairs(gi[:k].copy(), gj[:k].copy(), counts[:k, 0::2].copy(), counts[:k, 1::2].copy(), key[:k, 0].copy(), key[:k, 1].copy(),
                         sizes, a, None if b < 0 else b, int(passes.value))
 
+    def top_partners(self, genes=None, m: int = 1, a: int = 0, b=None, partner_mask=None) -> TopPartners:
+        """Which partners (reo_top_partners): for every gene of `genes` (None: all genes in order; any order, repeats allowed) its m best
+        partner genes -- inside partner_mask (bool over the genes) when one is given; the query itself need not be -- for group a against
+        group b (None: against every other sample), as a TopPartners.  A row with fewer than m eligible partners is padded.  Exact; sides
+        and refusals as in top_pairs; 1 <= m <= 1024, at most 2^20 queries and 2^26 listed partners per call."""
+        m = int(m)
+        a, b, sizes = self._sides(a, b)
+        g = np.arange(self.G, dtype=np.int32) if genes is None else np.ascontiguousarray(np.asarray(genes).reshape(-1), dtype=np.int32)
+        pm = None
+        if partner_mask is not None:
+            pm = np.asarray(partner_mask)
+            if pm.shape != (self.G,):
+                raise DimensionMismatch(REO_EINVAL, f"top_partners: partner_mask has shape {tuple(pm.shape)}, the matrix has {self.G} genes")
+            pm = np.ascontiguousarray(pm if pm.dtype == np.uint8 else pm != 0, dtype=np.uint8)
+        Q = int(g.size)
+        w = min(max(m, 1), 1024)   # (the library refuses m outside [1, 1024] before it writes)
+        rows = Q if 1 <= Q <= 1 << 20 and Q * w <= 1 << 26 else 1   # (and a number of rows it does not take)
+        partner = np.full((rows, w), -1, dtype=np.int32)
+        counts, key = np.zeros((rows, w, 4), dtype=np.int32), np.zeros((rows, w, 2), dtype=np.int64)
+        found = np.zeros(rows, dtype=np.int32)
+        check(self._L.reo_top_partners(self._h, a, b, _ptr(g) if Q else None, Q, _opt(pm), m, _ptr(partner), _ptr(counts), _ptr(key), _ptr(found)))
+        return TopPartners(g, partner, counts[:, :, 0::2].copy(), counts[:, :, 1::2].copy(), key[:, :, 0].copy(), key[:, :, 1].copy(), found,
+                           sizes, a, None if b < 0 else b)
+
     def top_pairs_null(self, sides, a: int = 0, b=None, gene_mask=None, cuts=None) -> TopPairsNull:
         """The null of the best score (reo_top_pairs_null): for every label row of `sides` (B x S, 1 = side A, 0 = side B, 2 = the samples of
         groups on neither side; permuted_sides makes them) the largest |N| over all gene pairs i < j -- both genes inside gene_mask when
@@ -1496,8 +1592,8 @@ class Context:
                 "k2_full_launches": int(ms[9]), "k2_delta_ms": ms[10], "set_matrix_host_wall_ms": ms[11]}
 
     def info(self) -> dict:
-        w = np.zeros(42, dtype=np.int64)
-        check(self._L.reo_get_info(self._h, _ptr(w), 42))
+        w = np.zeros(44, dtype=np.int64)
+        check(self._L.reo_get_info(self._h, _ptr(w), 44))
         v = np.zeros(28, dtype=np.int64)   # fields 0-27 keep their places (tests/test_csc_device_cpu.py reads this line); 28 is appended
         v[:] = w[:28]
         return {"G": int(v[0]), "S": int(v[1]), "Gp": int(v[2]), "table_bytes": int(v[3]), "has_ties": int(v[4]),
@@ -1513,4 +1609,5 @@ class Context:
                 "perm_batch": int(w[34]), "perm_kernel_us": int(w[35]),
                 "top_pairs_hist_us": int(w[36]), "top_pairs_emit_us": int(w[37]),
                 "top_pairs_null_batch": int(w[38]), "top_pairs_null_us": int(w[39]),
-                "top_pairs_loo_words_us": int(w[40]), "top_pairs_loo_select_us": int(w[41])}
+                "top_pairs_loo_words_us": int(w[40]), "top_pairs_loo_select_us": int(w[41]),
+                "top_partners_count_us": int(w[42]), "top_partners_select_us": int(w[43])}

@@ -1,7 +1,7 @@
 // The query entry points of the C ABI (include/reo_hip.h): reo_pair_list, reo_sample_counts, reo_sample_tests, reo_sample_calls,
-// reo_pair_support, reo_rank_shift, reo_top_pairs, reo_top_pairs_null, reo_top_pairs_loo.  Host code only; the kernels are in pairlist.hip,
-// samplecounts.hip, sampletests.hip, samplecalls.hip, pairsupport.hip, toppairs.hip, toppairsnull.hip and toppairsloo.hip.  What they share
-// stands once, in front.
+// reo_pair_support, reo_rank_shift, reo_top_pairs, reo_top_pairs_null, reo_top_pairs_loo, reo_top_partners.  Host code only; the kernels are
+// in pairlist.hip, samplecounts.hip, sampletests.hip, samplecalls.hip, pairsupport.hip, toppairs.hip, toppairsnull.hip, toppairsloo.hip and
+// toppartners.hip.  What they share stands once, in front.
 #include <algorithm>
 #include <cstdlib>
 #include <utility>
@@ -15,6 +15,7 @@
 #include "top_pairs.h"
 #include "top_pairs_null.h"
 #include "top_pairs_loo.h"
+#include "top_partners.h"
 
 namespace reo {
 namespace {
@@ -766,6 +767,70 @@ int32_t reo_top_pairs_loo(reo_ctx *c, int32_t a, int32_t b, const uint8_t *gene_
         side[s] = static_cast<int8_t>((g < 0 || g >= c->ngroups) ? 2 : (sides.gside[static_cast<size_t>(g)] == 0 ? 1 : (sides.gside[static_cast<size_t>(g)] == 1 ? 0 : 2)));
     }
     stats[0] = cut; stats[1] = n_cand; stats[2] = passes; stats[3] = static_cast<int64_t>(sides.s_a) + sides.s_b;
+    return REO_OK;
+}
+
+// The best partners of given genes (include/reo_hip.h): every check on the host first (top_partners.h), then D, and per batch of query rows
+// one launch of k_top_partners_count into the batch's cells, one of k_top_partners_select over them, and the batch's rows back into the
+// caller's arrays.  Reads the bit planes of the transform and nothing of the class table or the iteration; writes none of them.
+int32_t reo_top_partners(reo_ctx *c, int32_t a, int32_t b, const int32_t *genes, int64_t n_genes, const uint8_t *partner_mask, int32_t m_want,
+                         int32_t *partner, int32_t *counts, int64_t *key, int32_t *n_found)
+{
+    const char *what = "reo_top_partners";
+    int32_t rc = top_begin(c, what);
+    if (rc) return rc;
+    char msg[320];
+    if (tpr_check_args(top_state(c), a, b, genes, n_genes, partner_mask, m_want, partner, counts, key, n_found, msg, sizeof msg)) { set_error("%s", msg); return REO_EINVAL; }
+    TopSides sides;
+    if ((rc = sides.make(c, what, a, b)) || (rc = ensure_transform(c))) return rc;
+    const int G = static_cast<int>(c->G);
+    const size_t m = static_cast<size_t>(m_want), padded = static_cast<size_t>(tpr_padded_rows(n_genes));
+    std::vector<uint32_t> bits;
+    if (partner_mask) {
+        bits.assign(static_cast<size_t>(c->Wp), 0u);
+        for (int g = 0; g < G; ++g)
+            if (partner_mask[g]) bits[static_cast<size_t>(g) >> 5] |= 1u << (g & 31);
+    }
+    std::vector<int32_t> rows(padded, 0);   // (the rows that fill the last tile walk gene 0; nothing of them is selected)
+    std::copy(genes, genes + n_genes, rows.begin());
+    DevBuf<int32_t> d_gside, d_genes, d_partner, d_counts, d_found;
+    DevBuf<int64_t> d_D, d_key;
+    DevBuf<uint32_t> d_bits;
+    DevBuf<unsigned long long> d_cells;
+    if ((rc = d_gside.ensure(sides.gside.size())) || (rc = d_D.ensure(static_cast<size_t>(c->Gp))) || (rc = d_genes.ensure(padded)) ||
+        (partner_mask && (rc = d_bits.ensure(bits.size()))))
+        return rc;
+    size_t free_bytes = 0, total_bytes = 0;
+    REO_HIP_CHECK(hipMemGetInfo(&free_bytes, &total_bytes));
+    const int64_t batch = tpr_batch_rows(n_genes, c->Gp, m_want, static_cast<uint64_t>(free_bytes), env_batch("REO_TOP_PARTNERS_BATCH"));
+    const size_t nb = static_cast<size_t>(batch);
+    if ((rc = d_cells.ensure(nb * static_cast<size_t>(c->Gp))) || (rc = d_partner.ensure(nb * m)) || (rc = d_counts.ensure(4 * nb * m)) ||
+        (rc = d_key.ensure(2 * nb * m)) || (rc = d_found.ensure(nb)))
+        return rc;
+    TimedPair ev_count, ev_select;   // (reo_get_info 42, 43: what the two kernels cost on the device)
+    if ((rc = ev_count.make()) || (rc = ev_select.make())) return rc;
+    DrainOnExit drain(c);   // the sides, the genes and the mask in, the rows out (declared after the buffers: the wait comes before their release)
+    REO_HIP_CHECK(hipMemcpyAsync(d_gside.p, sides.gside.data(), sides.gside.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    REO_HIP_CHECK(hipMemcpyAsync(d_genes.p, rows.data(), padded * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    if (partner_mask) REO_HIP_CHECK(hipMemcpyAsync(d_bits.p, bits.data(), bits.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    const uint32_t *maskbits = partner_mask ? d_bits.p : nullptr;
+    if ((rc = launch_rank_shift(c, d_gside.p, sides.s_a, sides.s_b, d_D.p))) return rc;
+    c->top_partners_count_us = 0; c->top_partners_select_us = 0;
+    for (int64_t q0 = 0; q0 < n_genes; q0 += batch) {
+        const int64_t nq = std::min(batch, n_genes - q0);
+        const size_t at = static_cast<size_t>(q0), nrow = static_cast<size_t>(nq);
+        const int32_t *g = d_genes.p + q0;   // (q0 is a multiple of kTpRows: the padded rows of this batch follow its own)
+        if ((rc = ev_count.start(c)) || (rc = launch_top_partners_count(c, d_gside.p, sides.s_a, sides.s_b, g, tpr_padded_rows(nq), d_cells.p)) ||
+            (rc = ev_count.stop(c)) || (rc = ev_select.start(c)) ||
+            (rc = launch_top_partners_select(c, d_cells.p, g, nq, d_D.p, maskbits, sides.s_a, sides.s_b, m_want, d_partner.p, d_counts.p, d_key.p,
+                                             d_found.p)) ||
+            (rc = ev_select.stop(c)) || (rc = copy_back(c, partner, at * m, d_partner.p, nrow * m)) ||
+            (rc = copy_back(c, counts, 4 * at * m, d_counts.p, 4 * nrow * m)) || (rc = copy_back(c, key, 2 * at * m, d_key.p, 2 * nrow * m)) ||
+            (rc = copy_back(c, n_found, at, d_found.p, nrow)) || (rc = wait_or_drop_table(c)) ||   // (the next batch reuses the buffers)
+            (rc = ev_count.add_us(&c->top_partners_count_us)) || (rc = ev_select.add_us(&c->top_partners_select_us)))
+            return rc;
+    }
+    drain.dismiss();
     return REO_OK;
 }
 

@@ -347,6 +347,8 @@ struct reo_ctx {
     int64_t top_null_us = 0;            // reo_get_info 39: microseconds its launches of k_top_pairs_null took in all (HIP events)
     int64_t top_loo_words_us = 0;       // reo_get_info 40: microseconds k_loo_words of the last reo_top_pairs_loo took (HIP events)
     int64_t top_loo_select_us = 0;      // reo_get_info 41: microseconds of its k_loo_select
+    int64_t top_partners_count_us = 0;  // reo_get_info 42: microseconds the launches of k_top_partners_count of the last reo_top_partners took in all (HIP events)
+    int64_t top_partners_select_us = 0; // reo_get_info 43: microseconds of its launches of k_top_partners_select
     reo::DevBuf<int32_t> raw;           // [G][8]
     reo::DevBuf<uint32_t> delta_list;   // [2][Gp] changed genes (gene << 1 | added) per pass parity
     reo::DevBuf<int32_t> cont;          // [G][9]
@@ -517,6 +519,17 @@ int32_t launch_top_pairs_null(reo_ctx *c, const uint32_t *d_aw, const uint32_t *
 int32_t launch_loo_words(reo_ctx *c, const TpRec *d_cand, int64_t n_cand, uint2 *d_words);
 int32_t launch_loo_select(reo_ctx *c, const TpRec *d_cand, int64_t n_cand, const uint2 *d_words, const int32_t *d_gside, const int32_t *d_slot2col,
                           const int64_t *d_sums, int s_a, int s_b, int kmax, int32_t *d_i, int32_t *d_j, int64_t *d_n, int64_t *d_g, int8_t *d_o);
+
+// toppartners.hip: the kernels of reo_top_partners (the cell, the row key, the batch rule and the host checks: top_partners.h).
+// launch_top_partners_count: for the n_rows query genes d_genes[0 .. n_rows - 1] (n_rows a multiple of kTpRows, every entry a gene) and
+// every column the cell of "query above column" into d_cells ([n_rows][Gp] 64-bit words).  launch_top_partners_select: one workgroup per
+// row decides the first m_want partners of rows 0 .. n_rows - 1 from the cells and d_D and stores them into d_partner ([n_rows][m_want]),
+// d_counts ([..][4]), d_key ([..][2]) and d_found ([n_rows]); entries beyond a row's n_found are -1 / 0
+int32_t launch_top_partners_count(reo_ctx *c, const int32_t *d_gside, int s_a, int s_b, const int32_t *d_genes, int64_t n_rows,
+                                  unsigned long long *d_cells);
+int32_t launch_top_partners_select(reo_ctx *c, const unsigned long long *d_cells, const int32_t *d_genes, int64_t n_rows, const int64_t *d_D,
+                                   const uint32_t *d_maskbits, int s_a, int s_b, int m_want, int32_t *d_partner, int32_t *d_counts, int64_t *d_key,
+                                   int32_t *d_found);
 
 // maskedpairs.hip: the kernels of reo_set_valid_mask / reo_build_pairs_masked / reo_pair_counts_masked (shared arithmetic and host checks:
 // masked_pairs.h).  launch_valid_words: c->vmask and d_slot2col ([32 * sample blocks], -1 for padding) into c->vwords (sized by the

@@ -335,6 +335,50 @@ def write_top_pairs_loo_tsv(path, sample_names, loo) -> None:
             f.write("\t".join([str(sample_names[s]), "A" if int(loo.side[s]) == 1 else "B"] + [str(int(v)) for v in votes[s]]) + "\n")
 
 
+def top_partners_plan(top_partners, *, masked=False, shard=(0, 1)) -> None:
+    """The refusals of `top_partners`, raised before any context is opened: a number of partners outside [1, 1024], and the routes that have
+    no search -- a validity mask (missing="pairwise" / `valid`) and shard[1] > 1."""
+    if top_partners is None:
+        return
+
+    def bad(why):
+        return _ffi.DimensionMismatch(_ffi.REO_EINVAL, why)
+    if isinstance(top_partners, bool) or not isinstance(top_partners, (int, np.integer)) or not 1 <= int(top_partners) <= 1024:
+        raise bad(f"top_partners = {top_partners!r}: None (no partner lists) or m, a number of partners per DEG between 1 and 1024")
+    if masked:
+        raise bad("top_partners: the search compares on the whole matrix and would count the fillers under the validity mask; it is not "
+                  "available together with missing=\"pairwise\" or `valid`")
+    if shard[1] > 1:
+        raise bad(f"top_partners: the search has no sharded form (shard = {tuple(shard)!r})")
+
+
+def deg_top_partners(ctx, labels, k, treat, top_partners) -> dict:
+    """{"top_partners"} of one comparison on `ctx`: the TopPartners (m = top_partners) of its DEGs against all genes, for group k against the
+    contrast's treatment group, or against every other sample for the reference's comparisons (treat None).  No DEGs: an empty object, no
+    library call for it."""
+    degs = np.flatnonzero(np.asarray(labels) != "no change").astype(np.int32)
+    m = int(top_partners)
+    if degs.size == 0:
+        a, b, sizes = ctx._sides(k, treat)
+        return {"top_partners": _ffi.TopPartners(degs, np.zeros((0, m), np.int32), np.zeros((0, m, 2), np.int32), np.zeros((0, m, 2), np.int32),
+                                                 np.zeros((0, m), np.int64), np.zeros((0, m), np.int64), np.zeros(0, np.int32), sizes, a,
+                                                 None if b < 0 else b)}
+    return {"top_partners": ctx.top_partners(degs, m, a=k, b=treat)}
+
+
+def write_top_partners_tsv(path, gene_names, tp) -> None:
+    """gene, rank, partner, num, score, rank_num, gt_A, eq_A, gt_B, eq_B: one line per found partner of a TopPartners, row by row in the
+    rows' own order, rank counted from 1; names from gene_names, the score by repr; a header line, "\n" line ends."""
+    score = tp.score
+    with open(path, "w") as f:
+        f.write("gene\trank\tpartner\tnum\tscore\trank_num\tgt_A\teq_A\tgt_B\teq_B\n")
+        for r in range(tp.genes.size):
+            for e in range(int(tp.n_found[r])):
+                f.write("\t".join([str(gene_names[int(tp.genes[r])]), str(e + 1), str(gene_names[int(tp.partner[r, e])]), str(int(tp.num[r, e])),
+                                   repr(float(score[r, e])), str(int(tp.rank_num[r, e])), str(int(tp.n_gt[r, e, 0])), str(int(tp.n_eq[r, e, 0])),
+                                   str(int(tp.n_gt[r, e, 1])), str(int(tp.n_eq[r, e, 1]))]) + "\n")
+
+
 def top_pairs_null_plan(top_pairs, top_pairs_permutations) -> None:
     """The refusals of `top_pairs_permutations`, raised before any context is opened (ValueError): given without `top_pairs`, or no number
     of permutations between 1 and 2^20."""
@@ -421,7 +465,7 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
                       pairs=None, sample_scores: bool = False, pair_support: bool = False, contrasts=None,
                       sample_tests: bool = False, sample_calls: bool = False, missing=None, valid=None, min_complete=None,
                       permutations=None, perm_seed: int = 0, perm_strata=None, top_pairs=None, top_pairs_permutations=None,
-                      top_pairs_loo=None) -> DegRun:
+                      top_pairs_loo=None, top_partners=None) -> DegRun:
     """identify_degs with the extras (trace, timings) kept.  `data` is a host matrix (numpy, anything np.asarray takes) or a torch
     tensor on a ROCm device, which is used in place (_ffi.device_matrix).  A column-major host matrix is read in place; a row-major one
     (numpy's default C order, column slices of a wider C-ordered array) is copied column-major on the host first, or, with REO_ROWMAJOR=1
@@ -483,7 +527,11 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
     `top_pairs_loo` (not in the reference): an int kmax adds "top_pairs_loo" to every comparison dict, the TopPairsLoo of the
     leave-one-out cross-validation of the k-TSP selection (Context.top_pairs_loo) with the sides of `top_pairs` -- the comparison's group
     against the contrast's treatment group or every other sample; independent of `top_pairs`.  Refused with a mask and with shard[1] > 1
-    (top_pairs_loo_plan).  None (the default): no further call, no new key."""
+    (top_pairs_loo_plan).  None (the default): no further call, no new key.
+    `top_partners` (not in the reference): an int m adds "top_partners" to every comparison dict, the TopPartners of the comparison's DEGs
+    against all genes (Context.top_partners: per DEG its m best partner genes, with the counts and the score of the two-gene rule), with the
+    sides of `top_pairs`.  A comparison without DEGs gets an empty TopPartners.  Refused with a mask and with shard[1] > 1
+    (top_partners_plan).  None (the default): no further call, no new key."""
     need_pairs_for_support(pairs, pair_support)
     data, mask = missing_plan(data, missing, valid, shard=shard, contrasts=contrasts, sample_scores=sample_scores, sample_tests=sample_tests,
                               sample_calls=sample_calls, pair_support=pair_support)
@@ -491,6 +539,7 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
     top_pairs_plan(top_pairs, masked=mask is not None, shard=shard)
     top_pairs_null_plan(top_pairs, top_pairs_permutations)
     top_pairs_loo_plan(top_pairs_loo, masked=mask is not None, shard=shard)
+    top_partners_plan(top_partners, masked=mask is not None, shard=shard)
     if mask is not None:
         _ffi.resolve_min_complete(min_complete, (1, 1), pval_reo)   # (its refusals, before a context is opened)
     # a torch tensor on a ROCm device: a strided one is used where it is, a sparse one is made dense there (its device is the context's)
@@ -555,6 +604,8 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
                     comps[-1].update(deg_top_pairs_null(ctx, gid, k, treat, comps[-1]["top_pairs"], top_pairs_permutations, perm_seed, perm_strata))
             if top_pairs_loo is not None:
                 comps[-1].update(deg_top_pairs_loo(ctx, k, treat, top_pairs_loo))
+            if top_partners is not None:
+                comps[-1].update(deg_top_partners(ctx, comps[-1]["labels"], k, treat, top_partners))
             if permutations is not None:   # last: it uses the iteration's buffers (ref_mask is refused behind it)
                 comps[-1].update(deg_perm_null(ctx, gid, k, permutations, perm_seed, perm_strata, pval_deg, padj_deg))
         timings = ctx.timings() if profile else {}
@@ -598,7 +649,7 @@ def identify_degs_cells(cells, cell_group, gene_names, n_pseudo, pval_reo, pval_
                         profile: bool = False, pairs=None, sample_scores: bool = False, pair_support: bool = False,
                         contrasts=None, sample_tests: bool = False, sample_calls: bool = False,
                         permutations=None, perm_seed: int = 0, perm_strata=None, top_pairs=None,
-                        top_pairs_permutations=None, top_pairs_loo=None) -> CellsDegRun:
+                        top_pairs_permutations=None, top_pairs_loo=None, top_partners=None) -> CellsDegRun:
     """Cells to DEGs without a host trip for the profiles: `cells` is a genes x cells matrix (scipy.sparse, anything np.asarray takes, or
     a torch tensor on a ROCm device -- sparse or strided -- which is read where it is: reo_set_matrix_pseudobulk_*_dev_*),
     cell_group one label per cell.  cells_partition -> the pseudo-bulk sums written into the context's matrix (set_matrix_pseudobulk) ->
@@ -610,12 +661,13 @@ def identify_degs_cells(cells, cell_group, gene_names, n_pseudo, pval_reo, pval_
     the kept profiles.  `contrasts`: as in run_identify_degs, over the group levels of the cells (checked against the levels of cell_group
     before any context is opened, and again against those of the kept profiles).  `permutations`, `perm_seed`, `perm_strata`: as in
     run_identify_degs; perm_strata has one label per pseudo-bulk PROFILE of cells_partition (the kept ones are used).  `top_pairs`,
-    `top_pairs_permutations`, `top_pairs_loo`: as in run_identify_degs."""
+    `top_pairs_permutations`, `top_pairs_loo`, `top_partners`: as in run_identify_degs."""
     need_pairs_for_support(pairs, pair_support)
     perm_plan(permutations, contrasts=contrasts)
     top_pairs_plan(top_pairs)
     top_pairs_null_plan(top_pairs, top_pairs_permutations)
     top_pairs_loo_plan(top_pairs_loo)
+    top_partners_plan(top_partners)
     on_device = _ffi.is_device_sparse(cells) or _ffi.is_device_tensor(cells)
     if on_device:   # a torch tensor on a ROCm device, sparse or strided: summed where it is, on its own device
         device = cells.device.index if cells.device.index is not None else -1
@@ -670,6 +722,8 @@ def identify_degs_cells(cells, cell_group, gene_names, n_pseudo, pval_reo, pval_
                     comps[-1].update(deg_top_pairs_null(ctx, gid, k, treat, comps[-1]["top_pairs"], top_pairs_permutations, perm_seed, strata))
             if top_pairs_loo is not None:
                 comps[-1].update(deg_top_pairs_loo(ctx, k, treat, top_pairs_loo))
+            if top_partners is not None:
+                comps[-1].update(deg_top_partners(ctx, comps[-1]["labels"], k, treat, top_partners))
             if permutations is not None:   # last: it uses the iteration's buffers (ref_mask is refused behind it)
                 strata = None if perm_strata is None else np.asarray(perm_strata)[np.asarray(profile_kept, dtype=bool)]
                 comps[-1].update(deg_perm_null(ctx, gid, k, permutations, perm_seed, strata, pval_deg, padj_deg))
