@@ -39,26 +39,6 @@ __global__ __launch_bounds__(256) void k_valid_words(const uint8_t *__restrict__
     words[static_cast<size_t>(b) * Gp + gene] = mp_valid_word(valid, G, S, gene, slot2col + static_cast<size_t>(b) * 32);
 }
 
-// lt / le of one pair and block: row i's band edges against column j's pos planes (16-plane layout).
-__device__ __forceinline__ void mp_chain(const uint32_t (&p)[16], const uint4 *__restrict__ al, const uint4 *__restrict__ ah, int nbits,
-                                         uint32_t &lt, uint32_t &le)
-{
-    uint32_t lo[16], hi[16];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        band_unpack(al[q], lo, q);
-        band_unpack(ah[q], hi, q);
-    }
-    lt = 0; le = 0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        if (k >= nbits) continue;   // (a guard per plane, not a break: the trip count stays constant and every p[k] a fixed register)
-        const int ew = BandLayout<false>::edge_word(k);
-        lt = __builtin_amdgcn_bitop3_b32(p[k], lo[ew], lt, 0x8e);
-        le = __builtin_amdgcn_bitop3_b32(p[k], hi[ew], le, 0x8e);
-    }
-}
-
 struct MpArgs {
     int G, Gp, Wp, nbits, ngroups, k;
     int n1, n2;        // the sides' sizes: the last index of their threshold tables
@@ -86,16 +66,14 @@ __global__ __launch_bounds__(kMpThreads) void k_pairs_masked(const uint4 *__rest
         const int b1 = goff[g + 1];
         for (int b = goff[g]; b < b1; ++b) {
             uint32_t p[16];
-            const uint4 *pb = P + static_cast<size_t>(b) * 4 * a.Gp + j;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) band_unpack(pb[static_cast<size_t>(q) * a.Gp], p, q);
+            band_load_pos<false>(P, a.Gp, b, j, p);
             const uint32_t *vb = VW + static_cast<size_t>(b) * a.Gp;
             const uint32_t vj = vb[j];
 #pragma unroll
             for (int r = 0; r < kMpRows; ++r) {
-                const size_t row = static_cast<size_t>(b) * a.Gp + (i0 + r);   // (i0 + r < Gp)
+                const size_t row = band_edge_row<false>(a.Gp, b, i0 + r);   // (i0 + r < Gp)
                 uint32_t lt, le;
-                mp_chain(p, AL + row * 4, AH + row * 4, a.nbits, lt, le);
+                band_compare<false, true, kBandGuard>(p, AL + row, AH + row, lt, le, a.nbits);
                 mp_count_block(lt, le, vb[i0 + r] & vj, gt[r], eq[r], nv[r]);
             }
         }
@@ -140,13 +118,13 @@ __global__ __launch_bounds__(256) void k_counts_masked(const uint4 *__restrict__
     for (int g = 0; g < ngroups; ++g) {
         uint32_t n_gt = 0, n_eq = 0, n_av = 0;
         for (int b = goff[g]; b < goff[g + 1]; ++b) {
-            uint32_t p[16];
+            uint32_t p[16], lt, le;
             const uint4 *pb = P + static_cast<size_t>(b) * 4 * Gp + j;
 #pragma unroll
             for (int q = 0; q < 4; ++q) band_unpack(pb[static_cast<size_t>(q) * Gp], p, q);
             const size_t row = static_cast<size_t>(b) * Gp + i;
-            uint32_t lt, le;
-            mp_chain(p, AL + row * 4, AH + row * 4, nbits, lt, le);
+            // (row * EQ and not band_edge_row: the row is the index of the validity words too, and the other spelling reorders this kernel)
+            band_compare<false, true, kBandGuard>(p, AL + row * BandLayout<false>::EQ, AH + row * BandLayout<false>::EQ, lt, le, nbits);
             mp_count_block(lt, le, VW[row] & VW[static_cast<size_t>(b) * Gp + j], n_gt, n_eq, n_av);
         }
         const size_t o = (static_cast<size_t>(i - ci0) * nj + (j - cj0)) * ngroups + g;
@@ -156,11 +134,12 @@ __global__ __launch_bounds__(256) void k_counts_masked(const uint4 *__restrict__
     }
 }
 
-int32_t need_planes(reo_ctx *c, const char *what)
+// the guard of the plane readers and the validity words on top; one text for either miss (ensure_planes never gives REO_EINVAL)
+int32_t mp_need_planes(reo_ctx *c, const char *what)
 {
-    if (c->pos.p && c->lo.p && c->hi.p && c->goff_dev.p && !c->goff32.empty() && c->ngroups >= 1 && c->G <= kMpMaxGenes && c->vwords.p) return ensure_planes(c);
-    set_error("%s: no bit planes or no validity words", what);
-    return REO_EINVAL;
+    const int32_t rc = c->vwords.p ? need_planes(c, what, kMpMaxGenes) : REO_EINVAL;
+    if (rc == REO_EINVAL) set_error("%s: no bit planes or no validity words", what);
+    return rc;
 }
 
 }  // namespace
@@ -178,22 +157,21 @@ int32_t launch_valid_words(reo_ctx *c, const int32_t *d_slot2col)
 
 int32_t launch_pairs_masked(reo_ctx *c, int k, const int32_t *d_m1, int n1, const int32_t *d_m2, int n2, int min_complete1, int min_complete2)
 {
-    int32_t rc = need_planes(c, "reo_build_pairs_masked");
+    int32_t rc = mp_need_planes(c, "reo_build_pairs_masked");
     if (rc) return rc;
     if (!d_m1 || !d_m2 || n1 < 0 || n2 < 0 || k < 0 || k >= c->ngroups) { set_error("reo_build_pairs_masked: no threshold tables"); return REO_EINVAL; }
     MpArgs a;
     a.G = static_cast<int>(c->G); a.Gp = c->Gp; a.Wp = c->Wp; a.nbits = plane_bits(c->G); a.ngroups = c->ngroups; a.k = k;
     a.n1 = n1; a.n2 = n2; a.mc1 = min_complete1; a.mc2 = min_complete2; a.seed = c->seed;
-    const unsigned ctiles = static_cast<unsigned>((c->G + 63) / 64), rtiles = static_cast<unsigned>((c->G + kMpRows - 1) / kMpRows);
-    k_pairs_masked<<<dim3((ctiles + kMpWaves - 1) / kMpWaves, rtiles), kMpThreads, 0, c->stream>>>(c->pos.p, c->lo.p, c->hi.p, c->vwords.p, c->goff_dev.p,
-                                                                                                   d_m1, d_m2, c->table.p, a);
+    k_pairs_masked<<<tile_grid(c->G, c->G, kMpRows, kMpWaves), kMpThreads, 0, c->stream>>>(c->pos.p, c->lo.p, c->hi.p, c->vwords.p, c->goff_dev.p, d_m1, d_m2,
+                                                                                           c->table.p, a);
     REO_HIP_CHECK(hipGetLastError());
     return REO_OK;
 }
 
 int32_t launch_counts_masked(reo_ctx *c, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int32_t *d_gt, int32_t *d_eq, int32_t *d_avail)
 {
-    int32_t rc = need_planes(c, "reo_pair_counts_masked");
+    int32_t rc = mp_need_planes(c, "reo_pair_counts_masked");
     if (rc) return rc;
     if (i0 < 0 || j0 < 0 || i1 > c->G || j1 > c->G || i0 >= i1 || j0 >= j1 || i1 - i0 > 65535) { set_error("reo_pair_counts_masked: bad pair block"); return REO_EINVAL; }
     const dim3 grid(static_cast<unsigned>((j1 - j0 + 255) / 256), static_cast<unsigned>(i1 - i0));

@@ -38,7 +38,7 @@ __global__ __launch_bounds__(kPsThreads) void k_pair_support(const PsItem *__res
                                                              const uint4 *__restrict__ AH, int32_t *__restrict__ out_gt,
                                                              int32_t *__restrict__ out_eq, uint8_t *__restrict__ outcome, PsArgs a)
 {
-    constexpr int NQ = BandLayout<BIG>::NQ, EQ = BandLayout<BIG>::EQ;   // uint4 per gene and block: pos planes, edge row
+    constexpr int NW = BandLayout<BIG>::NW;   // plane words per gene and block
     constexpr bool LE = WITH_EQ || WITH_OUTCOME;
     const int lane = threadIdx.x & (kPsLanes - 1);
     const int item = static_cast<int>(blockIdx.x) * kPsWaves + __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);
@@ -53,22 +53,23 @@ __global__ __launch_bounds__(kPsThreads) void k_pair_support(const PsItem *__res
         uint32_t n_lt = 0, n_le = 0;
         const int b1 = goff[g + 1];
         for (int b = goff[g]; b < b1; ++b) {
-            uint32_t lo[4 * NQ], hi[4 * NQ], p[4 * NQ];   // (hi: unused and gone without the le chain)
-            const uint4 *al = AL + (static_cast<size_t>(b) * a.Gp + gene) * EQ, *ah = AH + (static_cast<size_t>(b) * a.Gp + gene) * EQ;
-            const uint4 *pb = P + static_cast<size_t>(b) * NQ * a.Gp + j;
+            uint32_t lo[NW], hi[NW], p[NW];   // (hi: unused and gone without the le chain)
+            const size_t row = band_edge_row<BIG>(a.Gp, b, gene);
+            const uint4 *al = AL + row, *ah = AH + row;
+            const uint4 *pb = P + static_cast<size_t>(b) * BandLayout<BIG>::NQ * a.Gp + j;
 #pragma unroll
-            for (int q = 0; q < NQ; ++q) {
+            for (int q = 0; q < BandLayout<BIG>::NQ; ++q) {   // (one loop for the three: the loads of a quarter are issued together)
                 band_unpack(al[q], lo, q);
                 if constexpr (LE) band_unpack(ah[q], hi, q);
                 band_unpack(pb[static_cast<size_t>(q) * a.Gp], p, q);
             }
             uint32_t lt = 0, le = 0;
 #pragma unroll
-            for (int k = 0; k < 4 * NQ; ++k) {
+            for (int k = 0; k < NW; ++k) {
                 if (k >= a.nbits) continue;   // (a guard per plane, not a break: the trip count stays constant and every p[k] a fixed register)
                 const int ew = BandLayout<BIG>::edge_word(k);
-                lt = __builtin_amdgcn_bitop3_b32(p[k], lo[ew], lt, 0x8e);
-                if constexpr (LE) le = __builtin_amdgcn_bitop3_b32(p[k], hi[ew], le, 0x8e);
+                lt = band_borrow(p[k], lo[ew], lt);
+                if constexpr (LE) le = band_borrow(p[k], hi[ew], le);
             }
             n_lt += static_cast<uint32_t>(__builtin_popcount(lt));
             if constexpr (WITH_EQ) n_le += static_cast<uint32_t>(__builtin_popcount(le));

@@ -7,7 +7,8 @@
 //     four waves per workgroup take four neighbouring column tiles of the same rows; blockIdx.z is the launch group of kPermQ permutations.
 //     The wave walks ALL sample blocks of all groups: a lane loads the 16 pos planes of its column once per block and keeps them for all
 //     rows of the tile; the band edges of a row, the live word and the kPermQ A-words of the block are wave-uniform (__restrict__
-//     arguments, wave-uniform addresses: scalar loads).  Per (row, block) there is one borrow chain (mp_chain), then
+//     arguments, wave-uniform addresses: scalar loads).  Per (row, block) there is one borrow chain (band_chain.h; the tie-free form reads no
+//     upper edges and runs the lt chain alone), then
 //     gt_all += popc(lt & live), eq_all += popc(le & ~lt & live), and per permutation q  gtA[q] += popc(lt & A[q]), eqA[q] likewise: two
 //     VALU instructions per counter instead of the whole chain per permutation.  Side B is all - A.  The tie-free form (the transform
 //     reported no ties) carries no eq counters.  At the end every permutation is classified as k_pairs_masked classifies: EVERY ordered
@@ -46,28 +47,6 @@ __global__ __launch_bounds__(256) void k_perm_words(const uint8_t *__restrict__ 
     const int32_t *map = slot2col + static_cast<size_t>(b) * 32;
     aw[pn_word_index(p, b, nblk)] = pn_side_word(side + p * S, S, map);
     if (p == 0) live[b] = pn_live_word(S, map);
-}
-
-// lt / le of one pair and block: row i's band edges against column j's pos planes (16-plane layout; the chain of maskedpairs.hip).  The
-// tie-free form (TIES = false) reads no upper edges and runs the lt chain alone.
-template <bool TIES>
-__device__ __forceinline__ void pn_chain(const uint32_t (&p)[16], const uint4 *__restrict__ al, const uint4 *__restrict__ ah, int nbits,
-                                         uint32_t &lt, uint32_t &le)
-{
-    uint32_t lo[16], hi[16];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        band_unpack(al[q], lo, q);
-        if (TIES) band_unpack(ah[q], hi, q);
-    }
-    lt = 0; le = 0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        if (k >= nbits) continue;   // (a guard per plane, not a break: the trip count stays constant and every p[k] a fixed register)
-        const int ew = BandLayout<false>::edge_word(k);
-        lt = __builtin_amdgcn_bitop3_b32(p[k], lo[ew], lt, 0x8e);
-        if (TIES) le = __builtin_amdgcn_bitop3_b32(p[k], hi[ew], le, 0x8e);
-    }
 }
 
 struct PnArgs {
@@ -111,9 +90,10 @@ __global__ __launch_bounds__(kPnThreads) void k_pairs_permuted(const uint4 *__re
         for (int q = 0; q < kPermQ; ++q) A[q] = aw[static_cast<size_t>(b) * kPermQ + q];
 #pragma unroll
         for (int r = 0; r < kPermRows; ++r) {
-            const size_t row = static_cast<size_t>(b) * a.Gp + (i0 + r);   // (i0 + r < Gp)
+            // (i0 + r < Gp; row * EQ and not band_edge_row, which multiplies before it adds the pointer and reorders this kernel)
+            const size_t row = static_cast<size_t>(b) * a.Gp + (i0 + r);
             uint32_t lt, le;
-            pn_chain<TIES>(p, AL + row * 4, AH + row * 4, a.nbits, lt, le);
+            band_compare<false, TIES, kBandGuard>(p, AL + row * BandLayout<false>::EQ, AH + row * BandLayout<false>::EQ, lt, le, a.nbits);
             lt &= live;
             gtAll[r] += static_cast<uint32_t>(__builtin_popcount(lt));
 #pragma unroll
@@ -196,16 +176,14 @@ int32_t launch_perm_words(reo_ctx *c, const uint8_t *d_side, int64_t n_perm, con
 int32_t launch_pairs_permuted(reo_ctx *c, const uint32_t *d_aw, const uint32_t *d_live, int np, int n1, int n2, int m1, int m2,
                               uint32_t *d_tables)
 {
-    if (!(c->pos.p && c->lo.p && c->hi.p && !c->goff32.empty() && c->G <= kMpMaxGenes)) { set_error("reo_perm_null: no bit planes"); return REO_EINVAL; }
-    int32_t rc = ensure_planes(c);
+    int32_t rc = need_planes(c, "reo_perm_null", kMpMaxGenes);
     if (rc) return rc;
     if (!d_aw || !d_live || !d_tables || np < 1) { set_error("reo_perm_null: bad batch"); return REO_EINVAL; }
     PnArgs a;
     a.G = static_cast<int>(c->G); a.Gp = c->Gp; a.Wp = c->Wp; a.nbits = plane_bits(c->G); a.nblk = c->goff32.back() / 32;
     a.n1 = n1; a.n2 = n2; a.m1 = m1; a.m2 = m2; a.np = np; a.seed = c->seed;
     a.table_words = static_cast<size_t>(c->G) * kPlanes * c->Wp;
-    const unsigned ctiles = static_cast<unsigned>((c->G + 63) / 64), rtiles = static_cast<unsigned>((c->G + kPermRows - 1) / kPermRows);
-    const dim3 grid((ctiles + kPnWaves - 1) / kPnWaves, rtiles, static_cast<unsigned>((np + kPermQ - 1) / kPermQ));
+    const dim3 grid = tile_grid(c->G, c->G, kPermRows, kPnWaves, (np + kPermQ - 1) / kPermQ);
     if (c->has_ties)
         k_pairs_permuted<true><<<grid, kPnThreads, 0, c->stream>>>(c->pos.p, c->lo.p, c->hi.p, d_aw, d_live, d_tables, a);
     else

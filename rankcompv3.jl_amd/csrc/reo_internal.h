@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <functional>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "reo_hip.h"
@@ -452,6 +453,33 @@ int32_t light_min_genes();
 int32_t light_window();
 int32_t launch_mccullagh(reo_ctx *c, const int32_t *d_cont, int64_t n, double *d_out);
 
+// What the launchers of the plane-reading kernels share (band_chain.h).
+int plane_bits(int64_t G);   // kernels.hip: position planes that the count loops read
+// The guard in front of a kernel that reads the planes of the 16-plane layout: they exist, for at most max_genes genes, and are sliced.
+inline int32_t need_planes(reo_ctx *c, const char *what, int64_t max_genes)
+{
+    if (c->pos.p && c->lo.p && c->hi.p && c->goff_dev.p && !c->goff32.empty() && c->ngroups >= 1 && c->G <= max_genes) return ensure_planes(c);
+    set_error("%s: no bit planes", what);
+    return REO_EINVAL;
+}
+// f(std::integral_constant<int, NB>) with NB = plane_bits(G) of the 16-plane layout, 12, 15 or 16: one kernel instantiation per number of
+// planes that the chain reads, so that its trip count is a constant without a guard per plane.
+template <typename F>
+void with_plane_bits(int64_t G, F &&f)
+{
+    switch (plane_bits(G)) {
+    case 12: f(std::integral_constant<int, 12>{}); break;
+    case 15: f(std::integral_constant<int, 15>{}); break;
+    default: f(std::integral_constant<int, 16>{}); break;
+    }
+}
+// The grid of the tiled kernels: a wave owns 64 of `cols` columns and `tile_rows` of `rows` rows, `waves` waves a workgroup.
+inline dim3 tile_grid(int64_t cols, int64_t rows, int tile_rows, int waves, int z = 1)
+{
+    const unsigned ctiles = static_cast<unsigned>((cols + 63) / 64);
+    return dim3((ctiles + waves - 1) / waves, static_cast<unsigned>((rows + tile_rows - 1) / tile_rows), static_cast<unsigned>(z));
+}
+
 // pairlist.hip: the kernels of reo_pair_list (shared arithmetic and host checks: pair_list.h).  d_maskbits: [Wp] the partner mask as bits
 // (k_pack_ref's layout, a refbits slot); d_genes: [n_genes] query rows, checked by the caller to lie in [0, G)
 int32_t launch_pair_count(reo_ctx *c, const int32_t *d_genes, int64_t n_genes, const uint32_t *d_maskbits, uint32_t class_mask, int32_t *d_count);
@@ -461,7 +489,6 @@ int32_t launch_pair_fill(reo_ctx *c, const int32_t *d_genes, int64_t n_genes, co
 // samplecounts.hip: the kernel of reo_sample_counts (shared arithmetic and host checks: sample_counts.h).  d_genes: [n_queries] query rows,
 // checked by the caller to lie in [0, G); d_maskbits as above; d_slot2col: [32 * sample blocks] the caller's column of every sample slot, -1
 // for padding; d_gt / d_eq: [n_queries][S] (d_eq null: the tied counts are not computed); d_sel: [n_queries]
-int plane_bits(int64_t G);   // kernels.hip: position planes that the count loops read
 int32_t launch_sample_counts(reo_ctx *c, const int32_t *d_genes, int64_t n_queries, const uint32_t *d_maskbits, uint32_t class_mask,
                              const int32_t *d_slot2col, int32_t *d_sel, int32_t *d_gt, int32_t *d_eq);
 

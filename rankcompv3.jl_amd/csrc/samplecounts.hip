@@ -58,7 +58,7 @@ __device__ __forceinline__ uint32_t wave_counts(const uint32_t (&c)[kScMaxPlanes
 template <bool BIG, bool WITH_EQ>
 __global__ __launch_bounds__(kScThreads) void k_sample_counts(ScArgs a)
 {
-    constexpr int NQ = BandLayout<BIG>::NQ, EQ = BandLayout<BIG>::EQ;   // uint4 per gene and block: pos planes, edge row
+    constexpr int NW = BandLayout<BIG>::NW;   // plane words per gene and block
     __shared__ uint16_t list[kScTileCols];
     __shared__ int32_t acc_lt[kScThreads], acc_le[WITH_EQ ? kScThreads : 1];
     __shared__ int32_t wave_tot[2];
@@ -103,27 +103,22 @@ __global__ __launch_bounds__(kScThreads) void k_sample_counts(ScArgs a)
         for (int rb = wave; rb < kScChunkBlocks; rb += kScWaves) {
             const int b = b0 + rb;
             if (b >= a.nblk) break;
-            uint32_t lo[4 * NQ], hi[4 * NQ];   // (hi, cle: unused and gone without WITH_EQ)
-            const uint4 *al = a.AL + (static_cast<size_t>(b) * a.Gp + row) * EQ, *ah = a.AH + (static_cast<size_t>(b) * a.Gp + row) * EQ;
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) {
-                band_unpack(al[q], lo, q);
-                if constexpr (WITH_EQ) band_unpack(ah[q], hi, q);
-            }
+            uint32_t lo[NW], hi[NW];   // (hi, cle: unused and gone without WITH_EQ)
+            band_load_edges<BIG, WITH_EQ>(a.AL, a.AH, band_edge_row<BIG>(a.Gp, b, row), lo, hi);
             uint32_t clt[kScMaxPlanes] = {0, 0, 0, 0, 0, 0, 0}, cle[kScMaxPlanes] = {0, 0, 0, 0, 0, 0, 0};
-            const uint4 *pb = a.P + static_cast<size_t>(b) * NQ * a.Gp;
+            const uint4 *pb = a.P + static_cast<size_t>(b) * BandLayout<BIG>::NQ * a.Gp;
             for (int e = lane; e < n_tile; e += kScLanes) {
                 const int j = t0 + list[e];
-                uint32_t p[4 * NQ];
+                uint32_t p[NW];
 #pragma unroll
-                for (int q = 0; q < NQ; ++q) band_unpack(pb[static_cast<size_t>(q) * a.Gp + j], p, q);
+                for (int q = 0; q < BandLayout<BIG>::NQ; ++q) band_unpack(pb[static_cast<size_t>(q) * a.Gp + j], p, q);
                 uint32_t lt = 0, le = 0;
 #pragma unroll
-                for (int k = 0; k < 4 * NQ; ++k) {
+                for (int k = 0; k < NW; ++k) {
                     if (k >= a.nbits) break;
                     const int ew = BandLayout<BIG>::edge_word(k);
-                    lt = __builtin_amdgcn_bitop3_b32(p[k], lo[ew], lt, 0x8e);
-                    if constexpr (WITH_EQ) le = __builtin_amdgcn_bitop3_b32(p[k], hi[ew], le, 0x8e);
+                    lt = band_borrow(p[k], lo[ew], lt);
+                    if constexpr (WITH_EQ) le = band_borrow(p[k], hi[ew], le);
                 }
 #pragma unroll
                 for (int k = 0; k < kScMaxPlanes; ++k) {   // sc_counter_add, unrolled over registers

@@ -20,7 +20,7 @@
 // Gp genes; blocks are bounded by the group offsets of the transform; bins by the 12 bits of a digit.
 #include "top_pairs.h"
 #include "reo_internal.h"
-#include "band_chain.h"
+#include "top_count.h"
 
 namespace reo {
 
@@ -54,60 +54,15 @@ __global__ __launch_bounds__(256) void k_rank_shift(const uint4 *__restrict__ AL
             const int b1 = goff[g + 1];
             for (int b = goff[g]; b < b1; ++b) {
                 uint32_t lo[16], hi[16];
-                const size_t row = (static_cast<size_t>(b) * Gp + gene) * 4;
+                band_load_edges<false, true>(AL, AH, band_edge_row<false>(Gp, b, gene), lo, hi);
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    band_unpack(AL[row + q], lo, q);
-                    band_unpack(AH[row + q], hi, q);
-                }
-#pragma unroll
-                for (int k = 0; k < 16; ++k) {   // (the planes above plane_bits(G) are zero: lo and hi are at most G)
-                    const int ew = BandLayout<false>::edge_word(k);
-                    acc += static_cast<int64_t>(__builtin_popcount(lo[ew]) + __builtin_popcount(hi[ew])) << k;
-                }
+                for (int k = 0; k < 16; ++k) acc += band_edge_term<int64_t>(lo, hi, k, BandPopcount{});
             }
             if (side == 0) sum[0] += acc; else sum[1] += acc;
         }
     }
     D[gene] = tp_shift(sum[0], sum[1], s_a, s_b);   // (genes >= G: 0)
     if (sums) { sums[gene] = sum[0]; sums[Gp + gene] = sum[1]; }   // (reo_top_pairs_loo: D of a fold needs the two sums apart)
-}
-
-// The counts of one side: gt[r] += popcount(lt), le[r] += popcount(le) of rows i0 + r against column j over the blocks of the side's groups.
-template <int NB>
-__device__ __forceinline__ void tp_count_side(const uint4 *__restrict__ P, const uint4 *__restrict__ AL, const uint4 *__restrict__ AH,
-                                              const int32_t *__restrict__ goff, const int32_t *__restrict__ gside, int side, int j, int i0,
-                                              const TpArgs &a, uint32_t (&gt)[kTpRows], uint32_t (&le)[kTpRows])
-{
-    for (int g = 0; g < a.ngroups; ++g) {
-        if (gside[g] != side) continue;   // (wave-uniform)
-        const int b1 = goff[g + 1];
-        for (int b = goff[g]; b < b1; ++b) {
-            uint32_t p[16];
-            const uint4 *pb = P + static_cast<size_t>(b) * 4 * a.Gp + j;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) band_unpack(pb[static_cast<size_t>(q) * a.Gp], p, q);
-#pragma unroll
-            for (int r = 0; r < kTpRows; ++r) {
-                const size_t row = (static_cast<size_t>(b) * a.Gp + (i0 + r)) * 4;   // (i0 + r < Gp)
-                uint32_t lo[16], hi[16];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    band_unpack(AL[row + q], lo, q);
-                    band_unpack(AH[row + q], hi, q);
-                }
-                uint32_t lt = 0, lq = 0;
-#pragma unroll
-                for (int k = 0; k < NB; ++k) {
-                    const int ew = BandLayout<false>::edge_word(k);
-                    lt = __builtin_amdgcn_bitop3_b32(p[k], lo[ew], lt, 0x8e);
-                    lq = __builtin_amdgcn_bitop3_b32(p[k], hi[ew], lq, 0x8e);
-                }
-                gt[r] += static_cast<uint32_t>(__builtin_popcount(lt));
-                le[r] += static_cast<uint32_t>(__builtin_popcount(lq));
-            }
-        }
-    }
 }
 
 template <int MODE, int NB>   // NB = plane_bits(G): 12, 15 or 16 planes
@@ -132,8 +87,9 @@ __global__ __launch_bounds__(kTpThreads) void k_top_pairs(const uint4 *__restric
         uint32_t gt_a[kTpRows], le_a[kTpRows], gt_b[kTpRows], le_b[kTpRows];
 #pragma unroll
         for (int r = 0; r < kTpRows; ++r) { gt_a[r] = 0; le_a[r] = 0; gt_b[r] = 0; le_b[r] = 0; }
-        tp_count_side<NB>(P, AL, AH, goff, gside, 0, j, i0, a, gt_a, le_a);
-        tp_count_side<NB>(P, AL, AH, goff, gside, 1, j, i0, a, gt_b, le_b);
+        const TpRowsFrom row_of{i0};   // (i0 + r < Gp)
+        tp_count_side<NB>(P, AL, AH, goff, gside, 0, j, row_of, a, gt_a, le_a);
+        tp_count_side<NB>(P, AL, AH, goff, gside, 1, j, row_of, a, gt_b, le_b);
         const int64_t dj = D[j];
         const bool col_ok = tp_mask_bit(maskbits, j);
 #pragma unroll
@@ -172,13 +128,6 @@ __global__ __launch_bounds__(kTpThreads) void k_top_pairs(const uint4 *__restric
     }
 }
 
-int32_t tp_need_planes(reo_ctx *c, const char *what)
-{
-    if (c->pos.p && c->lo.p && c->hi.p && c->goff_dev.p && !c->goff32.empty() && c->ngroups >= 1 && c->G <= kTpMaxGenes) return ensure_planes(c);
-    set_error("%s: no bit planes", what);
-    return REO_EINVAL;
-}
-
 TpArgs tp_args(reo_ctx *c, int s_a, int s_b)
 {
     TpArgs a;
@@ -187,30 +136,21 @@ TpArgs tp_args(reo_ctx *c, int s_a, int s_b)
     return a;
 }
 
-dim3 tp_grid(reo_ctx *c)
-{
-    const unsigned ctiles = static_cast<unsigned>((c->G + 63) / 64), rtiles = static_cast<unsigned>((c->G + kTpRows - 1) / kTpRows);
-    return dim3((ctiles + kTpWaves - 1) / kTpWaves, rtiles);
-}
-
-// One instantiation per number of planes that the chain reads (plane_bits), so that its trip count is a constant without a guard per plane.
 template <int MODE>
 void tp_launch(reo_ctx *c, const int32_t *d_gside, const int64_t *d_D, const uint32_t *d_maskbits, unsigned long long *d_hist, TpRec *d_cand,
                uint32_t *d_cand_n, const TpArgs &a)
 {
-    const dim3 g = tp_grid(c);
-    switch (plane_bits(c->G)) {
-    case 12: k_top_pairs<MODE, 12><<<g, kTpThreads, 0, c->stream>>>(c->pos.p, c->lo.p, c->hi.p, c->goff_dev.p, d_gside, d_D, d_maskbits, d_hist, d_cand, d_cand_n, a); break;
-    case 15: k_top_pairs<MODE, 15><<<g, kTpThreads, 0, c->stream>>>(c->pos.p, c->lo.p, c->hi.p, c->goff_dev.p, d_gside, d_D, d_maskbits, d_hist, d_cand, d_cand_n, a); break;
-    default: k_top_pairs<MODE, 16><<<g, kTpThreads, 0, c->stream>>>(c->pos.p, c->lo.p, c->hi.p, c->goff_dev.p, d_gside, d_D, d_maskbits, d_hist, d_cand, d_cand_n, a); break;
-    }
+    with_plane_bits(c->G, [&](auto nb) {
+        k_top_pairs<MODE, decltype(nb)::value><<<tile_grid(c->G, c->G, kTpRows, kTpWaves), kTpThreads, 0, c->stream>>>(
+            c->pos.p, c->lo.p, c->hi.p, c->goff_dev.p, d_gside, d_D, d_maskbits, d_hist, d_cand, d_cand_n, a);
+    });
 }
 
 }  // namespace
 
 int32_t launch_rank_shift(reo_ctx *c, const int32_t *d_gside, int s_a, int s_b, int64_t *d_D, int64_t *d_sums)
 {
-    int32_t rc = tp_need_planes(c, "reo_rank_shift");
+    int32_t rc = need_planes(c, "reo_rank_shift", kTpMaxGenes);
     if (rc) return rc;
     k_rank_shift<<<static_cast<unsigned>(c->Gp / 256), 256, 0, c->stream>>>(c->lo.p, c->hi.p, c->goff_dev.p, d_gside, static_cast<int>(c->G), c->Gp,
                                                                             c->ngroups, s_a, s_b, d_D, d_sums);
@@ -221,7 +161,7 @@ int32_t launch_rank_shift(reo_ctx *c, const int32_t *d_gside, int s_a, int s_b, 
 int32_t launch_top_hist(reo_ctx *c, const int32_t *d_gside, int s_a, int s_b, const int64_t *d_D, const uint32_t *d_maskbits, const TpKey &prefix,
                         int shift, unsigned long long *d_hist)
 {
-    int32_t rc = tp_need_planes(c, "reo_top_pairs");
+    int32_t rc = need_planes(c, "reo_top_pairs", kTpMaxGenes);
     if (rc) return rc;
     if (shift < 0 || shift > kTpKeyBits - kTpDigitBits || shift % kTpDigitBits) { set_error("reo_top_pairs: no digit at bit %d", shift); return REO_EINVAL; }
     TpArgs a = tp_args(c, s_a, s_b);
@@ -234,7 +174,7 @@ int32_t launch_top_hist(reo_ctx *c, const int32_t *d_gside, int s_a, int s_b, co
 int32_t launch_top_emit(reo_ctx *c, const int32_t *d_gside, int s_a, int s_b, const int64_t *d_D, const uint32_t *d_maskbits, const TpKey &cut,
                         int shift, TpRec *d_cand, int64_t capacity, uint32_t *d_cand_n)
 {
-    int32_t rc = tp_need_planes(c, "reo_top_pairs");
+    int32_t rc = need_planes(c, "reo_top_pairs", kTpMaxGenes);
     if (rc) return rc;
     if (shift < 0 || shift > kTpKeyBits - kTpDigitBits || capacity < 1 || capacity > (int64_t(1) << 30) || !d_cand || !d_cand_n) {
         set_error("reo_top_pairs: a candidate buffer of %lld records at bit %d cannot be filled", (long long)capacity, shift);

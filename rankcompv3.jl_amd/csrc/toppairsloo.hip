@@ -39,41 +39,20 @@ __global__ __launch_bounds__(kLooThreads) void k_loo_words(const TpRec *__restri
     if (cnd >= n_cand) return;
     const int b = static_cast<int>(blockIdx.y);
     const TpRec r = cand[cnd];
-    uint32_t p[16], lo[16], hi[16];
-    const uint4 *pb = P + static_cast<size_t>(b) * 4 * Gp + r.j;
-    const size_t row = (static_cast<size_t>(b) * Gp + r.i) * 4;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        band_unpack(pb[static_cast<size_t>(q) * Gp], p, q);
-        band_unpack(AL[row + q], lo, q);
-        band_unpack(AH[row + q], hi, q);
-    }
-    uint32_t lt = 0, le = 0;
-#pragma unroll
-    for (int k = 0; k < NB; ++k) {
-        const int ew = BandLayout<false>::edge_word(k);
-        lt = __builtin_amdgcn_bitop3_b32(p[k], lo[ew], lt, 0x8e);
-        le = __builtin_amdgcn_bitop3_b32(p[k], hi[ew], le, 0x8e);
-    }
+    uint32_t p[16], lo[16], hi[16], lt, le;
+    band_load_pos<false>(P, Gp, b, r.j, p);
+    band_load_edges<false, true>(AL, AH, band_edge_row<false>(Gp, b, r.i), lo, hi);
+    band_chain<false, true, NB>(p, lo, hi, lt, le);
     words[loo_word_index(b, cnd, n_cand)] = make_uint2(lt, le & ~lt);
 }
 
 // lo + hi of gene g in bit t of block b, from the edge planes.
 __device__ __forceinline__ int64_t loo_edge_sum(const uint4 *__restrict__ AL, const uint4 *__restrict__ AH, int Gp, int b, int g, int t)
 {
-    uint32_t lo[16], hi[16];
-    const size_t row = (static_cast<size_t>(b) * Gp + g) * 4;
+    uint32_t lo[16], hi[16], v = 0;
+    band_load_edges<false, true>(AL, AH, band_edge_row<false>(Gp, b, g), lo, hi);
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        band_unpack(AL[row + q], lo, q);
-        band_unpack(AH[row + q], hi, q);
-    }
-    uint32_t v = 0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const int ew = BandLayout<false>::edge_word(k);
-        v += (((lo[ew] >> t) & 1u) + ((hi[ew] >> t) & 1u)) << k;
-    }
+    for (int k = 0; k < 16; ++k) v += band_edge_term<uint32_t>(lo, hi, k, BandBit{t});
     return static_cast<int64_t>(v);
 }
 
@@ -170,18 +149,11 @@ __global__ __launch_bounds__(kLooThreads) void k_loo_select(const TpRec *__restr
     }
 }
 
-int32_t loo_need(reo_ctx *c)
-{
-    if (c->pos.p && c->lo.p && c->hi.p && c->goff_dev.p && !c->goff32.empty() && c->ngroups >= 1 && c->G <= kTpMaxGenes) return ensure_planes(c);
-    set_error("reo_top_pairs_loo: no bit planes");
-    return REO_EINVAL;
-}
-
 }  // namespace
 
 int32_t launch_loo_words(reo_ctx *c, const TpRec *d_cand, int64_t n_cand, uint2 *d_words)
 {
-    int32_t rc = loo_need(c);
+    int32_t rc = need_planes(c, "reo_top_pairs_loo", kTpMaxGenes);
     if (rc) return rc;
     const int nblk = c->goff32.back() / 32;
     if (n_cand < 1 || n_cand > kLooMaxRecords || nblk < 1 || nblk > 65535 || !d_cand || !d_words) {
@@ -190,11 +162,9 @@ int32_t launch_loo_words(reo_ctx *c, const TpRec *d_cand, int64_t n_cand, uint2 
     }
     const dim3 g(static_cast<unsigned>((n_cand + kLooThreads - 1) / kLooThreads), static_cast<unsigned>(nblk));
     const uint32_t n = static_cast<uint32_t>(n_cand);
-    switch (plane_bits(c->G)) {
-    case 12: k_loo_words<12><<<g, kLooThreads, 0, c->stream>>>(d_cand, c->pos.p, c->lo.p, c->hi.p, d_words, c->Gp, n); break;
-    case 15: k_loo_words<15><<<g, kLooThreads, 0, c->stream>>>(d_cand, c->pos.p, c->lo.p, c->hi.p, d_words, c->Gp, n); break;
-    default: k_loo_words<16><<<g, kLooThreads, 0, c->stream>>>(d_cand, c->pos.p, c->lo.p, c->hi.p, d_words, c->Gp, n); break;
-    }
+    with_plane_bits(c->G, [&](auto nb) {
+        k_loo_words<decltype(nb)::value><<<g, kLooThreads, 0, c->stream>>>(d_cand, c->pos.p, c->lo.p, c->hi.p, d_words, c->Gp, n);
+    });
     REO_HIP_CHECK(hipGetLastError());
     return REO_OK;
 }
@@ -202,7 +172,7 @@ int32_t launch_loo_words(reo_ctx *c, const TpRec *d_cand, int64_t n_cand, uint2 
 int32_t launch_loo_select(reo_ctx *c, const TpRec *d_cand, int64_t n_cand, const uint2 *d_words, const int32_t *d_gside, const int32_t *d_slot2col,
                           const int64_t *d_sums, int s_a, int s_b, int kmax, int32_t *d_i, int32_t *d_j, int64_t *d_n, int64_t *d_g, int8_t *d_o)
 {
-    int32_t rc = loo_need(c);
+    int32_t rc = need_planes(c, "reo_top_pairs_loo", kTpMaxGenes);
     if (rc) return rc;
     const int slots = c->goff32.back();
     if (n_cand < 1 || n_cand > kLooMaxRecords || slots < 32 || kmax < 1 || kmax > kLooMaxK || !d_cand || !d_words || !d_gside || !d_slot2col || !d_sums) {

@@ -107,8 +107,8 @@ __global__ __launch_bounds__(kTnThreads) void k_top_pairs_null(const uint4 *__re
 #pragma unroll
                 for (int k = 0; k < NB; ++k) {
                     const int ew = BandLayout<false>::edge_word(k);
-                    lt = __builtin_amdgcn_bitop3_b32(p[k], lo[ew], lt, 0x8e);
-                    if (TIES) le = __builtin_amdgcn_bitop3_b32(p[k], hi[ew], le, 0x8e);
+                    lt = band_borrow(p[k], lo[ew], lt);
+                    if (TIES) le = band_borrow(p[k], hi[ew], le);
                 }
                 lt &= live;
                 gtAll[r] += static_cast<uint32_t>(__builtin_popcount(lt));
@@ -178,11 +178,9 @@ template <bool TIES>
 void tn_launch(reo_ctx *c, const dim3 &g, const uint32_t *d_aw, const uint32_t *d_live, const uint32_t *d_maskbits, unsigned long long *d_keys,
                unsigned long long *d_reach, const TnArgs &a)
 {
-    switch (plane_bits(c->G)) {
-    case 12: k_top_pairs_null<TIES, 12><<<g, kTnThreads, 0, c->stream>>>(c->pos.p, c->lo.p, c->hi.p, d_aw, d_live, d_maskbits, d_keys, d_reach, a); break;
-    case 15: k_top_pairs_null<TIES, 15><<<g, kTnThreads, 0, c->stream>>>(c->pos.p, c->lo.p, c->hi.p, d_aw, d_live, d_maskbits, d_keys, d_reach, a); break;
-    default: k_top_pairs_null<TIES, 16><<<g, kTnThreads, 0, c->stream>>>(c->pos.p, c->lo.p, c->hi.p, d_aw, d_live, d_maskbits, d_keys, d_reach, a); break;
-    }
+    with_plane_bits(c->G, [&](auto nb) {
+        k_top_pairs_null<TIES, decltype(nb)::value><<<g, kTnThreads, 0, c->stream>>>(c->pos.p, c->lo.p, c->hi.p, d_aw, d_live, d_maskbits, d_keys, d_reach, a);
+    });
 }
 
 }  // namespace
@@ -205,8 +203,7 @@ int32_t launch_top_null_words(reo_ctx *c, const uint8_t *d_side, int64_t n_perm,
 int32_t launch_top_pairs_null(reo_ctx *c, const uint32_t *d_aw, const uint32_t *d_live, int np, int s_a, int s_b, const uint32_t *d_maskbits,
                               const int64_t *cuts, int n_cuts, unsigned long long *d_keys, unsigned long long *d_reach)
 {
-    if (!(c->pos.p && c->lo.p && c->hi.p && !c->goff32.empty() && c->G <= kTpMaxGenes)) { set_error("reo_top_pairs_null: no bit planes"); return REO_EINVAL; }
-    int32_t rc = ensure_planes(c);
+    int32_t rc = need_planes(c, "reo_top_pairs_null", kTpMaxGenes);
     if (rc) return rc;
     if (!d_aw || !d_live || !d_keys || !d_reach || np < 1 || np > kTnBatchCap || n_cuts < 0 || n_cuts > kTnMaxCuts || (n_cuts > 0 && !cuts)) {
         set_error("reo_top_pairs_null: bad batch");
@@ -216,8 +213,7 @@ int32_t launch_top_pairs_null(reo_ctx *c, const uint32_t *d_aw, const uint32_t *
     a.G = static_cast<int>(c->G); a.Gp = c->Gp; a.nblk = c->goff32.back() / 32;
     a.s_a = s_a; a.s_b = s_b; a.np = np; a.n_cuts = n_cuts;
     for (int t = 0; t < kTnMaxCuts; ++t) a.cuts[t] = (t < n_cuts && cuts[t] < (int64_t(1) << 31)) ? static_cast<uint32_t>(cuts[t]) : 0xFFFFFFFFu;
-    const unsigned ctiles = static_cast<unsigned>((c->G + 63) / 64), rtiles = static_cast<unsigned>((c->G + kTnRows - 1) / kTnRows);
-    const dim3 grid((ctiles + kTpWaves - 1) / kTpWaves, rtiles, static_cast<unsigned>((np + kPermQ - 1) / kPermQ));
+    const dim3 grid = tile_grid(c->G, c->G, kTnRows, kTpWaves, (np + kPermQ - 1) / kPermQ);
     if (c->has_ties) tn_launch<true>(c, grid, d_aw, d_live, d_maskbits, d_keys, d_reach, a);
     else tn_launch<false>(c, grid, d_aw, d_live, d_maskbits, d_keys, d_reach, a);
     REO_HIP_CHECK(hipGetLastError());

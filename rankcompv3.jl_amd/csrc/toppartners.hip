@@ -3,7 +3,7 @@
 //   k_top_partners_count<NB>   (NB = plane_bits(G) planes)  the walk of k_top_pairs (toppairs.hip) with the query genes as its rows: a wave owns
 //     64 columns (lane = partner p) and kTpRows query rows, four waves per workgroup take four neighbouring column tiles of the same rows.
 //     The rows are the genes genes[row0 + r], read through the row index instead of blockIdx.y * kTpRows -- wave-uniform, so the band edges
-//     of a row are still scalar loads; the count loop is tp_count_side's, restated here because its rows are not consecutive.  No i < j
+//     of a row are still scalar loads; the count loop is tp_count_side (top_count.h) with that row index.  No i < j
 //     restriction and no tile skip: a query row meets every column.  Side A's groups, then side B's; per (row, column) the lane packs
 //     gt_A, eq_A, gt_B, eq_B of "query above column" into one TprCell and stores it at cells[row of the batch][Gp]: one coalesced 64-bit
 //     store per lane.
@@ -18,7 +18,7 @@
 // offsets of the transform; the outputs have m_want entries per row of the batch.
 #include "top_partners.h"
 #include "reo_internal.h"
-#include "band_chain.h"
+#include "top_count.h"
 
 namespace reo {
 
@@ -33,44 +33,6 @@ struct TprArgs {
     int s_a, s_b;
     int m_want;
 };
-
-// The counts of one side: gt[r] += popcount(lt), le[r] += popcount(le) of the rows rows[r] against column j over the blocks of the side's
-// groups (tp_count_side of toppairs.hip with a row index).
-template <int NB>
-__device__ __forceinline__ void tpr_count_side(const uint4 *__restrict__ P, const uint4 *__restrict__ AL, const uint4 *__restrict__ AH,
-                                               const int32_t *__restrict__ goff, const int32_t *__restrict__ gside, int side, int j,
-                                               const int (&rows)[kTpRows], const TprArgs &a, uint32_t (&gt)[kTpRows], uint32_t (&le)[kTpRows])
-{
-    for (int g = 0; g < a.ngroups; ++g) {
-        if (gside[g] != side) continue;   // (wave-uniform)
-        const int b1 = goff[g + 1];
-        for (int b = goff[g]; b < b1; ++b) {
-            uint32_t p[16];
-            const uint4 *pb = P + static_cast<size_t>(b) * 4 * a.Gp + j;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) band_unpack(pb[static_cast<size_t>(q) * a.Gp], p, q);
-#pragma unroll
-            for (int r = 0; r < kTpRows; ++r) {
-                const size_t row = (static_cast<size_t>(b) * a.Gp + rows[r]) * 4;   // (rows[r] < G)
-                uint32_t lo[16], hi[16];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    band_unpack(AL[row + q], lo, q);
-                    band_unpack(AH[row + q], hi, q);
-                }
-                uint32_t lt = 0, lq = 0;
-#pragma unroll
-                for (int k = 0; k < NB; ++k) {
-                    const int ew = BandLayout<false>::edge_word(k);
-                    lt = __builtin_amdgcn_bitop3_b32(p[k], lo[ew], lt, 0x8e);
-                    lq = __builtin_amdgcn_bitop3_b32(p[k], hi[ew], lq, 0x8e);
-                }
-                gt[r] += static_cast<uint32_t>(__builtin_popcount(lt));
-                le[r] += static_cast<uint32_t>(__builtin_popcount(lq));
-            }
-        }
-    }
-}
 
 template <int NB>   // NB = plane_bits(G): 12, 15 or 16 planes
 __global__ __launch_bounds__(kTprCountThreads) void k_top_partners_count(const uint4 *__restrict__ P, const uint4 *__restrict__ AL,
@@ -90,8 +52,9 @@ __global__ __launch_bounds__(kTprCountThreads) void k_top_partners_count(const u
     uint32_t gt_a[kTpRows], le_a[kTpRows], gt_b[kTpRows], le_b[kTpRows];
 #pragma unroll
     for (int r = 0; r < kTpRows; ++r) { gt_a[r] = 0; le_a[r] = 0; gt_b[r] = 0; le_b[r] = 0; }
-    tpr_count_side<NB>(P, AL, AH, goff, gside, 0, j, rows, a, gt_a, le_a);
-    tpr_count_side<NB>(P, AL, AH, goff, gside, 1, j, rows, a, gt_b, le_b);
+    const auto row_of = [&rows](int r) { return rows[r]; };   // (rows[r] < G)
+    tp_count_side<NB>(P, AL, AH, goff, gside, 0, j, row_of, a, gt_a, le_a);
+    tp_count_side<NB>(P, AL, AH, goff, gside, 1, j, row_of, a, gt_b, le_b);
 #pragma unroll
     for (int r = 0; r < kTpRows; ++r)
         cells[static_cast<size_t>(row0 + r) * a.Gp + j] = tpr_pack(gt_a[r], le_a[r] - gt_a[r], gt_b[r], le_b[r] - gt_b[r]);
@@ -150,13 +113,6 @@ __global__ __launch_bounds__(kTprThreads) void k_top_partners_select(const unsig
     }
 }
 
-int32_t tpr_need_planes(reo_ctx *c)
-{
-    if (c->pos.p && c->lo.p && c->hi.p && c->goff_dev.p && !c->goff32.empty() && c->ngroups >= 1 && c->G <= kTpMaxGenes) return ensure_planes(c);
-    set_error("reo_top_partners: no bit planes");
-    return REO_EINVAL;
-}
-
 TprArgs tpr_args(reo_ctx *c, int s_a, int s_b, int m_want)
 {
     TprArgs a;
@@ -170,20 +126,17 @@ TprArgs tpr_args(reo_ctx *c, int s_a, int s_b, int m_want)
 int32_t launch_top_partners_count(reo_ctx *c, const int32_t *d_gside, int s_a, int s_b, const int32_t *d_genes, int64_t n_rows,
                                   unsigned long long *d_cells)
 {
-    int32_t rc = tpr_need_planes(c);
+    int32_t rc = need_planes(c, "reo_top_partners", kTpMaxGenes);
     if (rc) return rc;
     if (n_rows < kTpRows || n_rows % kTpRows || n_rows / kTpRows > 65535 || !d_genes || !d_cells) {   // (grid y; the budget allows 32 768 rows)
         set_error("reo_top_partners: a batch of %lld rows is no multiple of %d or more than one launch takes", (long long)n_rows, kTpRows);
         return REO_EINVAL;
     }
     const TprArgs a = tpr_args(c, s_a, s_b, 0);
-    const unsigned ctiles = static_cast<unsigned>((c->G + 63) / 64);
-    const dim3 g((ctiles + kTpWaves - 1) / kTpWaves, static_cast<unsigned>(n_rows / kTpRows));
-    switch (plane_bits(c->G)) {
-    case 12: k_top_partners_count<12><<<g, kTprCountThreads, 0, c->stream>>>(c->pos.p, c->lo.p, c->hi.p, c->goff_dev.p, d_gside, d_genes, d_cells, a); break;
-    case 15: k_top_partners_count<15><<<g, kTprCountThreads, 0, c->stream>>>(c->pos.p, c->lo.p, c->hi.p, c->goff_dev.p, d_gside, d_genes, d_cells, a); break;
-    default: k_top_partners_count<16><<<g, kTprCountThreads, 0, c->stream>>>(c->pos.p, c->lo.p, c->hi.p, c->goff_dev.p, d_gside, d_genes, d_cells, a); break;
-    }
+    with_plane_bits(c->G, [&](auto nb) {
+        k_top_partners_count<decltype(nb)::value><<<tile_grid(c->G, n_rows, kTpRows, kTpWaves), kTprCountThreads, 0, c->stream>>>(
+            c->pos.p, c->lo.p, c->hi.p, c->goff_dev.p, d_gside, d_genes, d_cells, a);
+    });
     REO_HIP_CHECK(hipGetLastError());
     return REO_OK;
 }
