@@ -532,6 +532,44 @@ int32_t reo_top_partners(reo_ctx *ctx, int32_t a, int32_t b /* -1: every other s
                          int64_t *key /* [n_genes][m_want][2]: N (signed, query against partner), Gamma, 0 beyond */,
                          int32_t *n_found /* [n_genes]: min(m_want, eligible partners) */);
 
+/* Label-permutation null of a gene's best partner score: reo_top_partners always lists a winner, and with thousands of candidate partners
+ * per gene a large best score is what chance alone produces.  Is the best partner of THIS gene better than the best partner that
+ * meaningless labels find for it?  The reference has no such output.
+ * Sides A and B are those of reo_top_partners(a, b); the label rows are those of reo_top_pairs_null: S bytes in the caller's column order,
+ * 1 = side A, 0 = side B, 2 = takes no part, exactly S_A ones and S_B zeros, a 2 exactly on the samples of the groups on neither side.  So
+ * the sizes, and with them 2 S_A S_B, hold under every row.  Query genes are those of reo_top_partners: any order, repeats allowed, q
+ * itself need not be inside partner_mask.
+ * Per label row b and query row r with gene q = genes[r], over the eligible partners p (p != q, p < G, partner_mask[p] != 0 or the mask
+ * NULL): N_b(q, p) from the four counts of "q above p" under the relabelling, ties counted as ties, no coin.  Then
+ *     max_n[b n_genes + r] = max |N_b(q, p)|,   arg_p[b n_genes + r] = the smallest p that attains it,
+ *     n_reach[b n_genes + r] = the number of eligible p with |N_b(q, p)| >= cuts[r]   (cuts: one per query row; NULL: not counted);
+ * a row with no eligible partner gives max_n = -1, arg_p = -1 and n_reach = 0.  The rank shift Gamma is NOT a tie-break here: it depends on
+ * the labels.  On a row that repeats the observed labels max_n equals |key[0]| of reo_top_partners(m_want = 1) -- the partner may differ
+ * among equal |N|, where Gamma decides there.  With every gene as a query the maximum over the rows is max_n of reo_top_pairs_null, and
+ * the smallest (min(q, p), max(q, p)) over the rows that attain it is its (arg_i, arg_j): two independent kernels, one answer.  The null
+ * is single-step (maxT over a gene's partners), not step-down.  All results are exact integers, independent of the launch geometry, of the
+ * batch size, of the arrival order of atomics and of a row's position in the call.
+ * Needs the matrix, the groups and the transform (run here if need be); no class table, no thresholds, no reference set.  Reads the bit
+ * planes only; the class table, the reference set and the iteration's buffers are untouched.  Host arrays only, allocated by the caller.
+ * The route (csrc/toppartnersnull.hip, csrc/top_partners_null.h): the A-words and the live word of reo_top_pairs_null, and
+ * k_top_partners_null, which walks the query rows against every column with one borrow chain for 16 permutations and reduces one 63-bit
+ * key (|N|, 2^32 - 1 - p) and one counter per (permutation, query row).  One launch handles at most 64 permutations, fewer when the keys and
+ * counters of a batch (12 bytes per permutation and query row) would not fit 256 MiB or the free memory (REO_TOP_PARTNERS_NULL_BATCH=n in
+ * the environment, read per call, asks for at most n).  reo_get_info 44 = the permutations per launch of the last call, 45 = the
+ * microseconds of its launches of the null kernel in all (HIP events).  No other info entry is touched.
+ * REO_EINVAL, each with its own message, all checked on the host before anything is uploaded, and a refused or failed call writes
+ * nothing: everything reo_top_pairs refuses of the context and of a, b (a reo_create_multi context; a sharded context; a validity mask set;
+ * G or S above 65535; a or b outside the groups; b == a); n_perm outside [1, 2^20]; n_genes outside [1, 2^20]; n_perm * n_genes above
+ * 2^26; a NULL sides, genes, max_n or arg_p; cuts without n_reach or n_reach without cuts; a query gene outside [0, G); a negative cut;
+ * the three kinds of bad label row of reo_top_pairs_null; a partner_mask byte other than 0 or 1. */
+int32_t reo_top_partners_null(reo_ctx *ctx, int32_t a, int32_t b /* -1: every other sample */,
+                              const uint8_t *sides /* [n_perm][S], caller's column order */, int64_t n_perm,
+                              const int32_t *genes, int64_t n_genes /* query genes, any order, repeats allowed */,
+                              const uint8_t *partner_mask /* G bytes 0/1, or NULL */,
+                              const int64_t *cuts /* [n_genes] or NULL */,
+                              int64_t *max_n /* [n_perm][n_genes] */, int32_t *arg_p /* [n_perm][n_genes] */,
+                              int32_t *n_reach /* [n_perm][n_genes]; NULL exactly when cuts is NULL */);
+
 /* Missing values: pair classes from the samples where BOTH genes were observed.  The reference drops every gene with a missing cell
  * (dropmissing!, src/RankCompV3.jl:601) and the library refuses a NaN; with a validity mask V beside the resident matrix a pair (i, j) is
  * compared in the samples where both values exist, and its stability is judged against the threshold of that many samples.
@@ -845,7 +883,8 @@ int32_t reo_get_timings(reo_ctx *ctx, double *ms, int32_t n);
  * last reo_top_pairs, 38 the permutations per launch of the last reo_top_pairs_null, 39 the microseconds that its launches of the null
  * kernel took in all (HIP events around each launch), 40 and 41 the microseconds of k_loo_words and of k_loo_select of the last
  * reo_top_pairs_loo, 42 and 43 the microseconds of the launches of k_top_partners_count and of k_top_partners_select of the last
- * reo_top_partners. */
+ * reo_top_partners, 44 the permutations per launch of the last reo_top_partners_null, 45 the microseconds that its launches of
+ * k_top_partners_null took in all (HIP events around each launch). */
 int32_t reo_get_info(reo_ctx *ctx, int64_t *info, int32_t n);
 
 #ifdef __cplusplus

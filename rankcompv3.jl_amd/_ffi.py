@@ -36,7 +36,7 @@ SYMBOLS = [
     "reo_filter_matrix", "reo_get_matrix", "reo_get_ref_mask", "reo_pair_list", "reo_sample_counts", "reo_pair_support",
     "reo_sample_tests", "reo_sample_calls", "reo_set_valid_mask", "reo_build_pairs_masked", "reo_pair_counts_masked",
     "reo_perm_null", "reo_perm_codes", "reo_rank_shift", "reo_top_pairs", "reo_top_pairs_null", "reo_top_pairs_loo",
-    "reo_top_partners",
+    "reo_top_partners", "reo_top_partners_null",
 ] +[f"reo_set_matrix_{form}_{t}" for form in ("csc_dev", "pseudobulk_csc_dev", "pseudobulk_dense_dev") for t in ("f64", "i64", "f32", "i32")]
 
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p)
@@ -156,6 +156,7 @@ def lib() -> ctypes.CDLL:
         "reo_top_pairs_null": (i32, [vp, i32, i32, vp, i64, vp, vp, i32, vp, vp, vp, vp]),
         "reo_top_pairs_loo": (i32, [vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
         "reo_top_partners": (i32, [vp, i32, i32, vp, i64, vp, i32, vp, vp, vp, vp]),
+        "reo_top_partners_null": (i32, [vp, i32, i32, vp, i64, vp, i64, vp, vp, vp, vp, vp]),
     }
     for t in ("f64", "i64", "f32", "i32"):   # SPARSE ON THE DEVICE
         sig["reo_set_matrix_csc_dev_" + t] = (i32, [vp, i64, i64, i64, vp, vp, i32, vp])
@@ -615,6 +616,72 @@ class TopPairsNull(NamedTuple):
         """The mean of n_reach over the permutations, one value per cut: with cuts = |tp.num[n - 1]| the expected number of chance pairs at
         least as good as the n-th listed one."""
         return self.n_reach.astype(np.float64).mean(axis=0) if self.n_reach.shape[0] else np.zeros(self.cuts.size)
+
+
+class TopPartnersNull(NamedTuple):
+    """reo_top_partners_null: per label permutation (row of `sides`) and query gene (column) the best score that the labelling reaches over
+    the gene's partners -- the null of the first column of Context.top_partners for side A (group a) against side B (group b, or every
+    other sample for b None).  max_num[b, r] = max |N_b| over the eligible partners of genes[r], arg_partner[b, r] the smallest partner
+    that attains it (the rank shift is no tie-break here), n_reach[b, r] = the partners with |N_b| >= cuts[r]; -1, -1 and 0 where a gene
+    has no eligible partner.  The null is single-step (maxT over a gene's partners), not step-down.  A query gene that was selected with
+    the same labels (a DEG) gets a permutation p-value of the partner search, not of its selection."""
+    genes: np.ndarray        # int32, Q: the query genes
+    max_num: np.ndarray      # int64, B x Q
+    arg_partner: np.ndarray  # int32, B x Q
+    n_reach: np.ndarray      # int32, B x Q, or B x 0 without cuts
+    cuts: np.ndarray         # int64, Q, or 0 without cuts
+    side_sizes: np.ndarray   # int64, 2: S_A, S_B
+    a: int
+    b: int | None
+
+    @property
+    def max_score(self) -> np.ndarray:
+        """max_num / (2 S_A S_B), float64, B x Q: the best partner score of every gene under every permutation."""
+        return self.max_num.astype(np.float64) / (2.0 * float(self.side_sizes[0]) * float(self.side_sizes[1]))
+
+    def _same_genes(self, tp, what):
+        if not np.array_equal(np.asarray(tp.genes), self.genes):
+            raise ValueError(f"{what}: the TopPartners lists other query genes than the null (the rows must be the same genes in the same order)")
+        keep = np.arange(tp.partner.shape[1])[None, :] < np.asarray(tp.n_found)[:, None]
+        return np.abs(np.asarray(tp.num, dtype=np.int64)), keep
+
+    def p_row(self, tp) -> np.ndarray:
+        """(1 + #{b : max_num[b, r] >= |tp.num[r, e]|}) / (1 + B) per cell of a TopPartners of the same genes (ValueError otherwise): the
+        single-step maxT adjusted p-value over the partners of the row's gene, the observed labelling counted among the permutations.
+        Non-decreasing along a row, because |num| is non-increasing; 1.0 in padded cells."""
+        obs, keep = self._same_genes(tp, "p_row")
+        ge = (self.max_num.T[:, None, :] >= obs[:, :, None]).sum(axis=2)
+        return np.where(keep, (1.0 + ge) / (1.0 + self.max_num.shape[0]), 1.0)
+
+    def p_max(self, tp) -> np.ndarray:
+        """As p_row with the maximum over ALL rows in place of the row's own: adjusted for the search over genes and partners.  With all
+        genes as queries it equals TopPairsNull.p_max.  1.0 in padded cells."""
+        obs, keep = self._same_genes(tp, "p_max")
+        top = self.max_num.max(axis=1) if self.max_num.shape[1] else np.full(self.max_num.shape[0], -1, dtype=np.int64)
+        ge = (top[None, None, :] >= obs[:, :, None]).sum(axis=2)
+        return np.where(keep, (1.0 + ge) / (1.0 + self.max_num.shape[0]), 1.0)
+
+    def expected_reach(self) -> np.ndarray:
+        """The mean of n_reach over the permutations, one value per query gene with a cut: with cuts[r] = |tp.num[r, m - 1]| the expected
+        number of chance partners at least as good as the row's m-th listed one."""
+        return self.n_reach.astype(np.float64).mean(axis=0) if self.n_reach.shape[0] else np.zeros(self.n_reach.shape[1])
+
+    def overall(self):
+        """(max_num, gene_i, gene_j) per permutation: the largest max_num over the rows and the smallest (min(q, p), max(q, p)) among the
+        rows that attain it; -1, -1, -1 where no row has a partner.  With all genes as queries (and the mask, if any, over queries and
+        partners alike) these are max_num, arg_i, arg_j of TopPairsNull."""
+        B, Q = self.max_num.shape
+        top = self.max_num.max(axis=1) if Q else np.full(B, -1, dtype=np.int64)
+        gi, gj = np.full(B, -1, dtype=np.int32), np.full(B, -1, dtype=np.int32)
+        for p in range(B):
+            if top[p] < 0:
+                continue
+            at = np.flatnonzero(self.max_num[p] == top[p])
+            q, w = self.genes[at].astype(np.int64), self.arg_partner[p, at].astype(np.int64)
+            lo, hi = np.minimum(q, w), np.maximum(q, w)
+            e = np.lexsort((hi, lo))[0]
+            gi[p], gj[p] = lo[e], hi[e]
+        return top.astype(np.int64), gi, gj
 
 
 class TopPairsLoo(NamedTuple):
@@ -1439,6 +1506,44 @@ class Context:
         return TopPartners(g, partner, counts[:, :, 0::2].copy(), counts[:, :, 1::2].copy(), key[:, :, 0].copy(), key[:, :, 1].copy(), found,
                            sizes, a, None if b < 0 else b)
 
+    def top_partners_null(self, sides, genes=None, a: int = 0, b=None, partner_mask=None, cuts=None) -> TopPartnersNull:
+        """The null of a gene's best partner (reo_top_partners_null): for every label row of `sides` (B x S, as in top_pairs_null;
+        permuted_sides makes them) and every gene of `genes` (None: all genes in order; any order, repeats allowed) the largest |N| over
+        the gene's partners -- inside partner_mask when one is given --, the smallest partner that attains it, and with `cuts` (one value
+        of |N| per query gene) how many partners reach the gene's cut, as a TopPartnersNull.  Sides and refusals as in top_partners; one
+        walk over the bit planes serves 16 rows; at most 2^20 rows, 2^20 queries and 2^26 cells per call."""
+        a, b, sizes = self._sides(a, b)
+        rows = np.asarray(sides)
+        if rows.ndim == 1:
+            rows = rows.reshape(1, -1)
+        if rows.ndim != 2 or rows.shape[1] != self.S:
+            raise DimensionMismatch(REO_EINVAL, f"top_partners_null: sides has shape {tuple(np.shape(sides))}, label rows are B x S = B x {self.S}")
+        if rows.size and (rows.min() < 0 or rows.max() > 255):
+            raise DimensionMismatch(REO_EINVAL, "top_partners_null: label rows hold 0 (side B), 1 (side A) and 2 (takes no part)")
+        rows = np.ascontiguousarray(rows, dtype=np.uint8)
+        g = np.arange(self.G, dtype=np.int32) if genes is None else np.ascontiguousarray(np.asarray(genes).reshape(-1), dtype=np.int32)
+        pm = None
+        if partner_mask is not None:
+            pm = np.asarray(partner_mask)
+            if pm.shape != (self.G,):
+                raise DimensionMismatch(REO_EINVAL, f"top_partners_null: partner_mask has shape {tuple(pm.shape)}, the matrix has {self.G} genes")
+            pm = np.ascontiguousarray(pm if pm.dtype == np.uint8 else pm != 0, dtype=np.uint8)
+        B, Q = rows.shape[0], int(g.size)
+        ct = None
+        if cuts is not None:
+            ct = np.ascontiguousarray(np.asarray(cuts, dtype=np.int64).reshape(-1))
+            if ct.size != Q:
+                raise DimensionMismatch(REO_EINVAL, f"top_partners_null: cuts has {ct.size} values, one per query gene is {Q}")
+        ok = 1 <= B <= 1 << 20 and 1 <= Q <= 1 << 20 and B * Q <= 1 << 26   # (the library refuses anything else before it writes)
+        shape = (B, Q) if ok else (1, 1)
+        max_n, arg = np.zeros(shape, dtype=np.int64), np.zeros(shape, dtype=np.int32)
+        reach = np.zeros(shape, dtype=np.int32) if ct is not None else None
+        check(self._L.reo_top_partners_null(self._h, a, b, _ptr(rows) if rows.size else None, B, _ptr(g) if Q else None, Q, _opt(pm),
+                                            _ptr(ct) if ct is not None and ct.size else None, _ptr(max_n), _ptr(arg),
+                                            _ptr(reach) if reach is not None else None))
+        return TopPartnersNull(g, max_n, arg, reach if reach is not None else np.zeros((B, 0), dtype=np.int32),
+                               ct if ct is not None else np.zeros(0, dtype=np.int64), sizes, a, None if b < 0 else b)
+
     def top_pairs_null(self, sides, a: int = 0, b=None, gene_mask=None, cuts=None) -> TopPairsNull:
         """The null of the best score (reo_top_pairs_null): for every label row of `sides` (B x S, 1 = side A, 0 = side B, 2 = the samples of
         groups on neither side; permuted_sides makes them) the largest |N| over all gene pairs i < j -- both genes inside gene_mask when
@@ -1592,8 +1697,8 @@ class Context:
                 "k2_full_launches": int(ms[9]), "k2_delta_ms": ms[10], "set_matrix_host_wall_ms": ms[11]}
 
     def info(self) -> dict:
-        w = np.zeros(44, dtype=np.int64)
-        check(self._L.reo_get_info(self._h, _ptr(w), 44))
+        w = np.zeros(46, dtype=np.int64)
+        check(self._L.reo_get_info(self._h, _ptr(w), 46))
         v = np.zeros(28, dtype=np.int64)   # fields 0-27 keep their places (tests/test_csc_device_cpu.py reads this line); 28 is appended
         v[:] = w[:28]
         return {"G": int(v[0]), "S": int(v[1]), "Gp": int(v[2]), "table_bytes": int(v[3]), "has_ties": int(v[4]),
@@ -1610,4 +1715,5 @@ class Context:
                 "top_pairs_hist_us": int(w[36]), "top_pairs_emit_us": int(w[37]),
                 "top_pairs_null_batch": int(w[38]), "top_pairs_null_us": int(w[39]),
                 "top_pairs_loo_words_us": int(w[40]), "top_pairs_loo_select_us": int(w[41]),
-                "top_partners_count_us": int(w[42]), "top_partners_select_us": int(w[43])}
+                "top_partners_count_us": int(w[42]), "top_partners_select_us": int(w[43]),
+                "top_partners_null_batch": int(w[44]), "top_partners_null_us": int(w[45])}

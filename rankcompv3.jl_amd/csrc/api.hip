@@ -600,7 +600,7 @@ using namespace reo;
 
 extern "C" {
 
-int32_t reo_version(void) { return 1600; }
+int32_t reo_version(void) { return 1700; }
 
 int32_t reo_trim_memory(void)
 {
@@ -1803,7 +1803,7 @@ int32_t reo_get_info(reo_ctx *c, int64_t *info, int32_t n)
         int32_t rc = use(c);
         if (rc || (rc = launch_slot_separated(c, &separated))) return rc;
     }
-    const int64_t v[44] = {c->G, c->S, c->Gp, static_cast<int64_t>(c->table.n * sizeof(uint32_t)), c->has_ties,
+    const int64_t v[46] = {c->G, c->S, c->Gp, static_cast<int64_t>(c->table.n * sizeof(uint32_t)), c->has_ties,
                            c->tiles_owned, c->tiles_total, kTileI, c->k1_cj, c->k1_q, kUnitH,
                            c->goff32.empty() ? 0 : c->goff32.back(), c->last_k1_shared,
                            static_cast<int64_t>(c->gcounts.n * sizeof(uint16_t)), c->transform_in_lds, c->xcc_local,
@@ -1813,8 +1813,8 @@ int32_t reo_get_info(reo_ctx *c, int64_t *info, int32_t n)
                            c->last_k1_slots ? c->last_k1_slot_sides : 0, (c->built_k >= 0 && c->built_masked) ? 1 : 0,
                            c->last_k1_slots ? c->last_k1_slot_slice : 0, c->transformed ? c->planes_on_demand : 0, c->perm_batch, c->perm_kernel_us,
                            c->top_hist_us, c->top_emit_us, c->top_null_batch, c->top_null_us, c->top_loo_words_us, c->top_loo_select_us,
-                           c->top_partners_count_us, c->top_partners_select_us};
-    for (int i = 0; i < n && i < 44; ++i) info[i] = v[i];
+                           c->top_partners_count_us, c->top_partners_select_us, c->top_partners_null_batch, c->top_partners_null_us};
+    for (int i = 0; i < n && i < 46; ++i) info[i] = v[i];
     return REO_OK;
 }
 

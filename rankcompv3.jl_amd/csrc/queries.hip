@@ -1,7 +1,7 @@
 // The query entry points of the C ABI (include/reo_hip.h): reo_pair_list, reo_sample_counts, reo_sample_tests, reo_sample_calls,
-// reo_pair_support, reo_rank_shift, reo_top_pairs, reo_top_pairs_null, reo_top_pairs_loo, reo_top_partners.  Host code only; the kernels are
-// in pairlist.hip, samplecounts.hip, sampletests.hip, samplecalls.hip, pairsupport.hip, toppairs.hip, toppairsnull.hip, toppairsloo.hip and
-// toppartners.hip.  What they share stands once, in front.
+// reo_pair_support, reo_rank_shift, reo_top_pairs, reo_top_pairs_null, reo_top_pairs_loo, reo_top_partners, reo_top_partners_null.  Host code
+// only; the kernels are in pairlist.hip, samplecounts.hip, sampletests.hip, samplecalls.hip, pairsupport.hip, toppairs.hip, toppairsnull.hip,
+// toppairsloo.hip, toppartners.hip and toppartnersnull.hip.  What they share stands once, in front.
 #include <algorithm>
 #include <cstdlib>
 #include <utility>
@@ -16,6 +16,7 @@
 #include "top_pairs_null.h"
 #include "top_pairs_loo.h"
 #include "top_partners.h"
+#include "top_partners_null.h"
 
 namespace reo {
 namespace {
@@ -831,6 +832,97 @@ int32_t reo_top_partners(reo_ctx *c, int32_t a, int32_t b, const int32_t *genes,
             return rc;
     }
     drain.dismiss();
+    return REO_OK;
+}
+
+// The null of a gene's best partner (include/reo_hip.h): every check on the host first (top_partners_null.h), then per batch of at most 64
+// label rows the A-words of reo_top_pairs_null, one launch of k_top_partners_null over all query rows and the batch's keys and counters
+// back.  Reads the bit planes of the transform and nothing of the class table or the iteration; writes none of them.  The caller's arrays
+// are written once every batch has run and every key has been found plausible.
+int32_t reo_top_partners_null(reo_ctx *c, int32_t a, int32_t b, const uint8_t *sides, int64_t n_perm, const int32_t *genes, int64_t n_genes,
+                              const uint8_t *partner_mask, const int64_t *cuts, int64_t *max_n, int32_t *arg_p, int32_t *n_reach)
+{
+    const char *what = "reo_top_partners_null";
+    int32_t rc = top_begin(c, what);
+    if (rc) return rc;
+    char msg[320];
+    int64_t s_a = 0, s_b = 0;
+    if (tprn_check_args(top_state(c), c->group_id.data(), a, b, sides, n_perm, genes, n_genes, partner_mask, cuts, max_n, arg_p, n_reach, &s_a, &s_b, msg,
+                        sizeof msg)) {
+        set_error("%s", msg);
+        return REO_EINVAL;
+    }
+    std::vector<int32_t> map;
+    if ((rc = ensure_transform(c)) || (rc = query_slot_map(c, what, map))) return rc;
+    const int G = static_cast<int>(c->G);
+    const size_t S = static_cast<size_t>(c->S), nq = static_cast<size_t>(n_genes), padded = static_cast<size_t>(tprn_padded_rows(n_genes));
+    const int nblk = c->goff32.back() / 32;
+    std::vector<uint32_t> bits;
+    if (partner_mask) {
+        bits.assign(static_cast<size_t>(c->Wp), 0u);
+        for (int g = 0; g < G; ++g)
+            if (partner_mask[g]) bits[static_cast<size_t>(g) >> 5] |= 1u << (g & 31);
+    }
+    std::vector<int32_t> rows(padded, 0);   // (the rows that fill the last tile walk gene 0; nothing of them is stored)
+    std::copy(genes, genes + n_genes, rows.begin());
+    std::vector<uint32_t> cutw(cuts ? padded : 0, 0xFFFFFFFFu);
+    for (size_t r = 0; cuts && r < nq; ++r) cutw[r] = tprn_cut_word(cuts[r]);
+    DevBuf<uint8_t> d_side;
+    DevBuf<int32_t> d_genes;
+    DevBuf<uint32_t> d_aw, d_live, d_bits, d_cuts, d_reach;
+    DevBuf<unsigned long long> d_keys;
+    if ((rc = d_genes.ensure(padded)) || (rc = d_live.ensure(static_cast<size_t>(nblk))) || (partner_mask && (rc = d_bits.ensure(bits.size()))) ||
+        (cuts && (rc = d_cuts.ensure(padded))) || (rc = c->sc_slot2col.ensure(map.size())))
+        return rc;
+    size_t free_bytes = 0, total_bytes = 0;
+    REO_HIP_CHECK(hipMemGetInfo(&free_bytes, &total_bytes));
+    const int64_t P = tprn_batch(n_perm, n_genes, static_cast<uint64_t>(free_bytes), env_batch("REO_TOP_PARTNERS_NULL_BATCH"));
+    const size_t cells = static_cast<size_t>(P) * padded;
+    if ((rc = d_side.ensure(static_cast<size_t>(P) * S)) || (rc = d_aw.ensure(pn_word_count(P, nblk))) || (rc = d_keys.ensure(cells)) ||
+        (rc = d_reach.ensure(cells)))
+        return rc;
+    TimedPair ev;   // (reo_get_info 45: what the launches cost on the device)
+    if ((rc = ev.make())) return rc;
+    std::vector<unsigned long long> keys(static_cast<size_t>(n_perm) * padded);   // (rows of `padded` cells, as they lie on the device)
+    std::vector<uint32_t> reach(cuts ? keys.size() : 0);
+    DrainOnExit drain(c);   // the rows, the genes, the cuts and the mask in, keys and counters out (declared after the buffers: the wait comes before their release)
+    if ((rc = upload_slot2col(c, map))) return rc;
+    REO_HIP_CHECK(hipMemcpyAsync(d_genes.p, rows.data(), padded * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    if (partner_mask) REO_HIP_CHECK(hipMemcpyAsync(d_bits.p, bits.data(), bits.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    if (cuts) REO_HIP_CHECK(hipMemcpyAsync(d_cuts.p, cutw.data(), padded * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    c->top_partners_null_batch = P; c->top_partners_null_us = 0;
+    for (int64_t p0 = 0; p0 < n_perm; p0 += P) {
+        const int np = static_cast<int>(std::min<int64_t>(P, n_perm - p0));
+        const size_t at = static_cast<size_t>(p0) * padded, n = static_cast<size_t>(np) * padded;
+        REO_HIP_CHECK(hipMemcpyAsync(d_side.p, sides + static_cast<size_t>(p0) * S, static_cast<size_t>(np) * S, hipMemcpyHostToDevice, c->stream));
+        REO_HIP_CHECK(hipMemsetAsync(d_keys.p, 0, n * sizeof(unsigned long long), c->stream));
+        REO_HIP_CHECK(hipMemsetAsync(d_reach.p, 0, n * sizeof(uint32_t), c->stream));
+        if ((rc = launch_top_null_words(c, d_side.p, np, c->sc_slot2col.p, d_aw.p, d_live.p)) || (rc = ev.start(c)) ||
+            (rc = launch_top_partners_null(c, d_aw.p, d_live.p, np, static_cast<int>(s_a), static_cast<int>(s_b), d_genes.p, n_genes,
+                                           partner_mask ? d_bits.p : nullptr, cuts ? d_cuts.p : nullptr, d_keys.p, d_reach.p)) ||
+            (rc = ev.stop(c)) || (rc = copy_back(c, keys.data(), at, d_keys.p, n)) ||
+            (cuts && (rc = copy_back(c, reach.data(), at, d_reach.p, n))) || (rc = wait_or_drop_table(c)) ||
+            (rc = ev.add_us(&c->top_partners_null_us)))   // (the next batch reuses the buffers)
+            return rc;
+    }
+    drain.dismiss();
+    for (int64_t p = 0; p < n_perm; ++p)
+        for (size_t r = 0; r < nq; ++r) {
+            int64_t m = -1;
+            int32_t gp = -1;
+            tprn_unpack(keys[static_cast<size_t>(p) * padded + r], &m, &gp);
+            if (m >= 0 && !(gp >= 0 && gp < G && gp != genes[r] && m <= 2 * s_a * s_b)) {
+                set_error("%s: permutation %lld, row %lld (gene %d) reduced to the partner %d with |N| = %lld of %d genes; nothing was written", what,
+                          (long long)p, (long long)r, genes[r], gp, (long long)m, G);
+                return REO_EHIP;
+            }
+        }
+    for (int64_t p = 0; p < n_perm; ++p)
+        for (size_t r = 0; r < nq; ++r) {
+            const size_t from = static_cast<size_t>(p) * padded + r, to = static_cast<size_t>(p) * nq + r;
+            tprn_unpack(keys[from], &max_n[to], &arg_p[to]);
+            if (cuts) n_reach[to] = static_cast<int32_t>(reach[from]);
+        }
     return REO_OK;
 }
 

@@ -350,6 +350,8 @@ struct reo_ctx {
     int64_t top_loo_select_us = 0;      // reo_get_info 41: microseconds of its k_loo_select
     int64_t top_partners_count_us = 0;  // reo_get_info 42: microseconds the launches of k_top_partners_count of the last reo_top_partners took in all (HIP events)
     int64_t top_partners_select_us = 0; // reo_get_info 43: microseconds of its launches of k_top_partners_select
+    int64_t top_partners_null_batch = 0; // reo_get_info 44: permutations per launch of the last reo_top_partners_null
+    int64_t top_partners_null_us = 0;    // reo_get_info 45: microseconds its launches of k_top_partners_null took in all (HIP events)
     reo::DevBuf<int32_t> raw;           // [G][8]
     reo::DevBuf<uint32_t> delta_list;   // [2][Gp] changed genes (gene << 1 | added) per pass parity
     reo::DevBuf<int32_t> cont;          // [G][9]
@@ -557,6 +559,14 @@ int32_t launch_top_partners_count(reo_ctx *c, const int32_t *d_gside, int s_a, i
 int32_t launch_top_partners_select(reo_ctx *c, const unsigned long long *d_cells, const int32_t *d_genes, int64_t n_rows, const int64_t *d_D,
                                    const uint32_t *d_maskbits, int s_a, int s_b, int m_want, int32_t *d_partner, int32_t *d_counts, int64_t *d_key,
                                    int32_t *d_found);
+
+// toppartnersnull.hip: the kernel of reo_top_partners_null (the key, the batch rule and the host checks: top_partners_null.h).  For
+// permutations 0 .. np - 1 of the words of launch_top_null_words and the n_genes query genes d_genes (padded with gene 0 up to a multiple
+// of kTnRows, every entry a gene) the largest key of every (permutation, row) into d_keys (atomicMax) and the partners with |N| >=
+// d_cuts[row] into d_reach (atomicAdd; d_cuts null: nothing is counted); both are [np][padded rows] and cleared by the caller; d_cuts:
+// [padded rows] words of tprn_cut_word; d_maskbits: [Wp] the partner mask as bits, or null for every gene
+int32_t launch_top_partners_null(reo_ctx *c, const uint32_t *d_aw, const uint32_t *d_live, int np, int s_a, int s_b, const int32_t *d_genes,
+                                 int64_t n_genes, const uint32_t *d_maskbits, const uint32_t *d_cuts, unsigned long long *d_keys, uint32_t *d_reach);
 
 // maskedpairs.hip: the kernels of reo_set_valid_mask / reo_build_pairs_masked / reo_pair_counts_masked (shared arithmetic and host checks:
 // masked_pairs.h).  launch_valid_words: c->vmask and d_slot2col ([32 * sample blocks], -1 for padding) into c->vwords (sized by the

@@ -15,7 +15,7 @@ from typing import NamedTuple
 import numpy as np
 
 from . import _ffi, synth
-from ._ffi import PairList, PairSupport, PermNull, SampleCalls, SampleCounts, SampleScores, SampleTests, TopPairs, TopPairsLoo, TopPairsNull, class_mask, permuted_labels, permuted_sides  # noqa: F401
+from ._ffi import PairList, PairSupport, PermNull, SampleCalls, SampleCounts, SampleScores, SampleTests, TopPairs, TopPairsLoo, TopPairsNull, TopPartners, TopPartnersNull, class_mask, permuted_labels, permuted_sides  # noqa: F401
 
 HEADER = ["pval", "padj", "n11", "n12", "n13", "n21", "n22", "n23", "n31", "n32", "n33",
           "Δ1", "Δ2", "se", "z1", "up_down"]  # src/RankCompV3.jl:665
@@ -379,6 +379,50 @@ def write_top_partners_tsv(path, gene_names, tp) -> None:
                                    str(int(tp.n_gt[r, e, 1])), str(int(tp.n_eq[r, e, 1]))]) + "\n")
 
 
+def top_partners_null_plan(top_partners, top_partners_permutations) -> None:
+    """The refusals of `top_partners_permutations`, raised before any context is opened (ValueError): given without `top_partners`, or no
+    number of permutations between 1 and 2^20."""
+    B = top_partners_permutations
+    if B is None:
+        return
+    if top_partners is None:
+        raise ValueError("top_partners_permutations needs top_partners: the null is that of the best partner score of the listed genes")
+    if isinstance(B, bool) or not isinstance(B, (int, np.integer)) or not 1 <= int(B) <= 1 << 20:
+        raise ValueError(f"top_partners_permutations = {B!r}: None (no null) or a number of permutations between 1 and 2^20")
+
+
+def top_partners_null_cuts(tp) -> np.ndarray:
+    """The cuts of a comparison's partner null: per row |N| of its last found partner (int64; 0 for a row that found none)."""
+    last = np.maximum(np.asarray(tp.n_found, dtype=np.int64) - 1, 0)
+    if tp.num.shape[1] == 0:
+        return np.zeros(tp.genes.size, dtype=np.int64)
+    return np.where(tp.n_found > 0, np.abs(tp.num[np.arange(tp.genes.size), last]), 0).astype(np.int64)
+
+
+def deg_top_partners_null(ctx, gid, k, treat, tp, permutations, perm_seed, perm_strata) -> dict:
+    """{"top_partners_null"} of one comparison on `ctx`: the TopPartnersNull of `permutations` label shuffles of the two sides for the genes
+    of its "top_partners" (the DEGs) against all genes (permuted_sides: seed perm_seed + k, within perm_strata if given -- the rows that
+    top_pairs_permutations uses), with the cuts of top_partners_null_cuts.  No DEGs: an empty object, no library call for it."""
+    B = int(permutations)
+    if tp.genes.size == 0:
+        return {"top_partners_null": TopPartnersNull(tp.genes, np.zeros((B, 0), np.int64), np.zeros((B, 0), np.int32), np.zeros((B, 0), np.int32),
+                                                     np.zeros(0, np.int64), tp.side_sizes, tp.a, tp.b)}
+    rows = permuted_sides(gid, k, treat, B, seed=int(perm_seed) + int(k), strata=perm_strata)
+    return {"top_partners_null": ctx.top_partners_null(rows, tp.genes, a=k, b=treat, cuts=top_partners_null_cuts(tp))}
+
+
+def write_top_partners_null_tsv(path, gene_names, tp, null) -> None:
+    """The columns of write_top_partners_tsv plus p_row (TopPartnersNull.p_row, by repr): one line per found partner, row by row."""
+    score, p_row = tp.score, null.p_row(tp)
+    with open(path, "w") as f:
+        f.write("gene\trank\tpartner\tnum\tscore\trank_num\tgt_A\teq_A\tgt_B\teq_B\tp_row\n")
+        for r in range(tp.genes.size):
+            for e in range(int(tp.n_found[r])):
+                f.write("\t".join([str(gene_names[int(tp.genes[r])]), str(e + 1), str(gene_names[int(tp.partner[r, e])]), str(int(tp.num[r, e])),
+                                   repr(float(score[r, e])), str(int(tp.rank_num[r, e])), str(int(tp.n_gt[r, e, 0])), str(int(tp.n_eq[r, e, 0])),
+                                   str(int(tp.n_gt[r, e, 1])), str(int(tp.n_eq[r, e, 1])), repr(float(p_row[r, e]))]) + "\n")
+
+
 def top_pairs_null_plan(top_pairs, top_pairs_permutations) -> None:
     """The refusals of `top_pairs_permutations`, raised before any context is opened (ValueError): given without `top_pairs`, or no number
     of permutations between 1 and 2^20."""
@@ -465,7 +509,7 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
                       pairs=None, sample_scores: bool = False, pair_support: bool = False, contrasts=None,
                       sample_tests: bool = False, sample_calls: bool = False, missing=None, valid=None, min_complete=None,
                       permutations=None, perm_seed: int = 0, perm_strata=None, top_pairs=None, top_pairs_permutations=None,
-                      top_pairs_loo=None, top_partners=None) -> DegRun:
+                      top_pairs_loo=None, top_partners=None, top_partners_permutations=None) -> DegRun:
     """identify_degs with the extras (trace, timings) kept.  `data` is a host matrix (numpy, anything np.asarray takes) or a torch
     tensor on a ROCm device, which is used in place (_ffi.device_matrix).  A column-major host matrix is read in place; a row-major one
     (numpy's default C order, column slices of a wider C-ordered array) is copied column-major on the host first, or, with REO_ROWMAJOR=1
@@ -531,7 +575,13 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
     `top_partners` (not in the reference): an int m adds "top_partners" to every comparison dict, the TopPartners of the comparison's DEGs
     against all genes (Context.top_partners: per DEG its m best partner genes, with the counts and the score of the two-gene rule), with the
     sides of `top_pairs`.  A comparison without DEGs gets an empty TopPartners.  Refused with a mask and with shard[1] > 1
-    (top_partners_plan).  None (the default): no further call, no new key."""
+    (top_partners_plan).  None (the default): no further call, no new key.
+    `top_partners_permutations` (not in the reference): an int B, together with `top_partners`, adds "top_partners_null" to every comparison
+    dict, the TopPartnersNull of B label shuffles of the two sides for the comparison's DEGs against all genes (Context.top_partners_null;
+    the rows of `top_pairs_permutations`: permuted_sides with seed perm_seed + k, within perm_strata when given; cuts: |N| of each row's
+    last found partner) -- .p_row(top_partners) is the single-step maxT p-value of every listed partner over the gene's partners.  Gamma
+    is no tie-break under the null; a DEG was selected with the same labels, so its p_row is a permutation p-value of the partner
+    search, not of the DEG call.  Without `top_partners`: ValueError.  None (the default): no further call, no new key."""
     need_pairs_for_support(pairs, pair_support)
     data, mask = missing_plan(data, missing, valid, shard=shard, contrasts=contrasts, sample_scores=sample_scores, sample_tests=sample_tests,
                               sample_calls=sample_calls, pair_support=pair_support)
@@ -540,6 +590,7 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
     top_pairs_null_plan(top_pairs, top_pairs_permutations)
     top_pairs_loo_plan(top_pairs_loo, masked=mask is not None, shard=shard)
     top_partners_plan(top_partners, masked=mask is not None, shard=shard)
+    top_partners_null_plan(top_partners, top_partners_permutations)
     if mask is not None:
         _ffi.resolve_min_complete(min_complete, (1, 1), pval_reo)   # (its refusals, before a context is opened)
     # a torch tensor on a ROCm device: a strided one is used where it is, a sparse one is made dense there (its device is the context's)
@@ -606,6 +657,9 @@ def run_identify_degs(data, group, gene_names, pval_reo, pval_deg, padj_deg, ref
                 comps[-1].update(deg_top_pairs_loo(ctx, k, treat, top_pairs_loo))
             if top_partners is not None:
                 comps[-1].update(deg_top_partners(ctx, comps[-1]["labels"], k, treat, top_partners))
+                if top_partners_permutations is not None:
+                    comps[-1].update(deg_top_partners_null(ctx, gid, k, treat, comps[-1]["top_partners"], top_partners_permutations, perm_seed,
+                                                           perm_strata))
             if permutations is not None:   # last: it uses the iteration's buffers (ref_mask is refused behind it)
                 comps[-1].update(deg_perm_null(ctx, gid, k, permutations, perm_seed, perm_strata, pval_deg, padj_deg))
         timings = ctx.timings() if profile else {}
@@ -649,7 +703,8 @@ def identify_degs_cells(cells, cell_group, gene_names, n_pseudo, pval_reo, pval_
                         profile: bool = False, pairs=None, sample_scores: bool = False, pair_support: bool = False,
                         contrasts=None, sample_tests: bool = False, sample_calls: bool = False,
                         permutations=None, perm_seed: int = 0, perm_strata=None, top_pairs=None,
-                        top_pairs_permutations=None, top_pairs_loo=None, top_partners=None) -> CellsDegRun:
+                        top_pairs_permutations=None, top_pairs_loo=None, top_partners=None,
+                        top_partners_permutations=None) -> CellsDegRun:
     """Cells to DEGs without a host trip for the profiles: `cells` is a genes x cells matrix (scipy.sparse, anything np.asarray takes, or
     a torch tensor on a ROCm device -- sparse or strided -- which is read where it is: reo_set_matrix_pseudobulk_*_dev_*),
     cell_group one label per cell.  cells_partition -> the pseudo-bulk sums written into the context's matrix (set_matrix_pseudobulk) ->
@@ -661,13 +716,14 @@ def identify_degs_cells(cells, cell_group, gene_names, n_pseudo, pval_reo, pval_
     the kept profiles.  `contrasts`: as in run_identify_degs, over the group levels of the cells (checked against the levels of cell_group
     before any context is opened, and again against those of the kept profiles).  `permutations`, `perm_seed`, `perm_strata`: as in
     run_identify_degs; perm_strata has one label per pseudo-bulk PROFILE of cells_partition (the kept ones are used).  `top_pairs`,
-    `top_pairs_permutations`, `top_pairs_loo`, `top_partners`: as in run_identify_degs."""
+    `top_pairs_permutations`, `top_pairs_loo`, `top_partners`, `top_partners_permutations`: as in run_identify_degs."""
     need_pairs_for_support(pairs, pair_support)
     perm_plan(permutations, contrasts=contrasts)
     top_pairs_plan(top_pairs)
     top_pairs_null_plan(top_pairs, top_pairs_permutations)
     top_pairs_loo_plan(top_pairs_loo)
     top_partners_plan(top_partners)
+    top_partners_null_plan(top_partners, top_partners_permutations)
     on_device = _ffi.is_device_sparse(cells) or _ffi.is_device_tensor(cells)
     if on_device:   # a torch tensor on a ROCm device, sparse or strided: summed where it is, on its own device
         device = cells.device.index if cells.device.index is not None else -1
@@ -724,6 +780,10 @@ def identify_degs_cells(cells, cell_group, gene_names, n_pseudo, pval_reo, pval_
                 comps[-1].update(deg_top_pairs_loo(ctx, k, treat, top_pairs_loo))
             if top_partners is not None:
                 comps[-1].update(deg_top_partners(ctx, comps[-1]["labels"], k, treat, top_partners))
+                if top_partners_permutations is not None:
+                    strata = None if perm_strata is None else np.asarray(perm_strata)[np.asarray(profile_kept, dtype=bool)]
+                    comps[-1].update(deg_top_partners_null(ctx, gid, k, treat, comps[-1]["top_partners"], top_partners_permutations, perm_seed,
+                                                           strata))
             if permutations is not None:   # last: it uses the iteration's buffers (ref_mask is refused behind it)
                 strata = None if perm_strata is None else np.asarray(perm_strata)[np.asarray(profile_kept, dtype=bool)]
                 comps[-1].update(deg_perm_null(ctx, gid, k, permutations, perm_seed, strata, pval_deg, padj_deg))

@@ -20,7 +20,8 @@ import numpy as np
 from . import _ffi, synth
 from .hotpath import (HEADER, need_pairs_for_support, run_identify_degs, write_pair_support_tsv, write_pairs_tsv, write_perm_null_tsv, write_perm_summary_tsv, write_sample_calls_tsv,
                       write_sample_scores_tsv, top_pairs_plan, write_top_pairs_tsv, top_pairs_null_plan, write_top_pairs_null_tsv,
-                      top_pairs_loo_plan, write_top_pairs_cv_tsv, write_top_pairs_loo_tsv, top_partners_plan, write_top_partners_tsv)
+                      top_pairs_loo_plan, write_top_pairs_cv_tsv, write_top_pairs_loo_tsv, top_partners_plan, write_top_partners_tsv,
+                      top_partners_null_plan, write_top_partners_null_tsv)
 
 log = logging.getLogger("reo_hip")
 
@@ -290,7 +291,7 @@ def reoa(fn_expr: str = "fn_expr.txt", fn_meta: str = "fn_meta.txt", *, expr_thr
          use_testdata: str = "no", seed: int = 0, device: int = -1, testdata_dir: str | None = None, align_meta: bool | None = None,
          pairs=None, sample_scores: bool = False, pair_support: bool = False, contrasts=None, sample_tests: bool = False,
          sample_calls: bool = False, permutations=None, perm_seed: int = 0, perm_strata=None, top_pairs=None,
-         top_pairs_permutations=None, top_pairs_loo=None, top_partners=None):
+         top_pairs_permutations=None, top_pairs_loo=None, top_partners=None, top_partners_permutations=None):
     """reoa(fn_expr, fn_meta; kwargs...) -- src/RankCompV3.jl:536-555.  `expr_threshold` is accepted and
     unused, as in the reference (:539).  Extra keywords: `seed` (the reference's RNG is unseeded),
     `device`, `testdata_dir` (where fn_expr.txt / fn_meta.txt of the reference's test/ directory live), `align_meta`
@@ -320,12 +321,16 @@ def reoa(fn_expr: str = "fn_expr.txt", fn_meta: str = "fn_meta.txt", *, expr_thr
     n_undecided, error, and `<stem>_<fg_name>_top_pairs_loo.tsv`, one line per fold: the sample's name, its side, votes_1 .. votes_kmax),
     `top_partners` (m: per DEG of every comparison its m best partner genes among all genes, as in run_identify_degs; additionally writes
     `<stem>_<fg_name>_top_partners.tsv`, one line per DEG and found partner: gene, rank, partner, num, score, rank_num and the four counts
-    of "the DEG above the partner")."""
+    of "the DEG above the partner"), `top_partners_permutations` (B, with `top_partners`: the label-permutation null of every DEG's best
+    partner score, as in run_identify_degs with `perm_seed` and `perm_strata`; additionally writes `<stem>_<fg_name>_top_partners_null.tsv`,
+    the columns of `_top_partners.tsv` plus p_row, the single-step maxT p-value of the partner over the DEG's partners; `_top_partners.tsv`
+    itself is unchanged)."""
     need_pairs_for_support(pairs, pair_support)
     top_pairs_plan(top_pairs)
     top_pairs_null_plan(top_pairs, top_pairs_permutations)
     top_pairs_loo_plan(top_pairs_loo)
     top_partners_plan(top_partners)
+    top_partners_null_plan(top_partners, top_partners_permutations)
     work_dir = os.path.abspath(work_dir)
     if use_testdata == "yes":  # :559-562
         d = testdata_dir or os.environ.get("REO_TESTDATA_DIR") or os.path.join(
@@ -347,7 +352,8 @@ def reoa(fn_expr: str = "fn_expr.txt", fn_meta: str = "fn_meta.txt", *, expr_thr
                             sample_scores=sample_scores, pair_support=pair_support, contrasts=contrasts,
                             sample_tests=sample_tests, sample_calls=sample_calls, permutations=permutations, perm_seed=perm_seed,
                             perm_strata=perm_strata, top_pairs=top_pairs, top_pairs_permutations=top_pairs_permutations,
-                            top_pairs_loo=top_pairs_loo, top_partners=top_partners)  # :652-662
+                            top_pairs_loo=top_pairs_loo, top_partners=top_partners,
+                            top_partners_permutations=top_partners_permutations)  # :652-662
     for p, (d, n) in enumerate(run.trace):
         log.info("INFO: iteration %d,  # DEGs %d, # non-DEGs %d", p, d, n)  # :418
     df = write_outputs(stem, prep, run, work_dir)
@@ -399,4 +405,7 @@ def write_extras(stem: str, prep: dict, run, work_dir: str = ".", pval_deg: floa
         if "top_partners" in cm:
             out.append(os.path.join(work_dir, f"{stem}_{fg}_top_partners.tsv"))
             write_top_partners_tsv(out[-1], prep["gene_names"], cm["top_partners"])
+        if "top_partners_null" in cm:
+            out.append(os.path.join(work_dir, f"{stem}_{fg}_top_partners_null.tsv"))
+            write_top_partners_null_tsv(out[-1], prep["gene_names"], cm["top_partners"], cm["top_partners_null"])
     return out
