@@ -256,9 +256,10 @@ class Incremental:
     (Float32 in Float32 arithmetic, everything else widened to Float64 with the band 0.1); from them w[g, s] = genes that g lies above -
     genes that g lies below in sample s, over ALL genes as the oracle's D sums them; and the sums of all three over the two sides.
     fold(s) subtracts the sample's bits and contribution on its side, shrinks that side by one, forms N(s), D(s) and Gamma(s) and orders
-    the eligible pairs by lexsort as top_pairs_cases.oracle does."""
+    the eligible pairs by lexsort as top_pairs_cases.oracle does.  w (S x G), when given, stands for the w of the matrix's own genes: the
+    rows of X are then some genes of a larger matrix, and w sums over all of that one's (tests/top_plane_cases.py, subset_loo)."""
 
-    def __init__(self, X, gid, ngroups, a, b, gene_mask=None):
+    def __init__(self, X, gid, ngroups, a, b, gene_mask=None, w=None):
         X = np.asarray(X)
         G, S = X.shape
         self.side = lc.sides_of(gid, ngroups, a, b)
@@ -276,13 +277,17 @@ class Incremental:
                 tie = np.abs(d) < 0.1
                 eq[:, at: at + G - 1 - i], gt[:, at: at + G - 1 - i] = tie.T, ((d > 0) & ~tie).T
                 at += G - 1 - i
-        w = np.zeros((S, G), dtype=np.int64)
-        at = 0
-        for i in range(G - 1):
-            d = gt[:, at: at + G - 1 - i].astype(np.int64) - (~gt[:, at: at + G - 1 - i] & ~eq[:, at: at + G - 1 - i])   # +1 i above j, -1 below, 0 tied
-            w[:, i] += d.sum(axis=1)
-            w[:, i + 1:] -= d
-            at += G - 1 - i
+        if w is None:
+            w = np.zeros((S, G), dtype=np.int64)
+            at = 0
+            for i in range(G - 1):
+                d = gt[:, at: at + G - 1 - i].astype(np.int64) - (~gt[:, at: at + G - 1 - i] & ~eq[:, at: at + G - 1 - i])   # +1 i above j, -1 below, 0 tied
+                w[:, i] += d.sum(axis=1)
+                w[:, i + 1:] -= d
+                at += G - 1 - i
+        else:                                                                    # X is a sub-matrix of a larger one: w comes from all of its genes
+            w = np.asarray(w, dtype=np.int64)
+            assert w.shape == (S, G)
         in_a, in_b = self.side == 1, self.side == 0
         self.gt, self.eq, self.w = gt, eq, w
         self.s_a, self.s_b = int(in_a.sum()), int(in_b.sum())
