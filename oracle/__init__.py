@@ -160,6 +160,19 @@ def bh(p):
     return out
 
 
+def iter_stats(cont, pval_deg, padj_deg):
+    """One pass of the iteration body from its tallies (oracle_iter_stats, src/RankCompV3.jl:402-417): cont is G x 9.
+    Returns (result G x 15, inds, n_nondeg); inds[i] = 1 for a non-DEG, the next pass's reference set."""
+    cont = np.ascontiguousarray(cont, dtype=np.int32)
+    G = cont.shape[0]
+    res = np.zeros((G, 15), order="F")
+    inds = np.zeros(G, dtype=np.uint8)
+    nn = lib().oracle_iter_stats(_p(cont, _i32p), G, pval_deg, padj_deg, _p(res, _f64p), _p(inds, _u8p))
+    if nn < 0:
+        raise IndexError("BoundsError in the reference")
+    return res, inds, int(nn)
+
+
 def iterate(code, ref0, pval_deg, padj_deg, n_iter, n_conv):
     code = np.ascontiguousarray(code, dtype=np.uint8)
     G = code.shape[0]
